@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the waldboost detection hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
 
 A *step* is one pass of the hot path -- octave pyramid, fused grad_hist channel pyramid and the
 dense 128-stage depth-2 cascade scan (BASELINE.json configs[1]) -- over one batch of B synthetic
@@ -15,12 +15,19 @@ own images ("weak" scaling: BASELINE configs[3] is --gpus 8 --batch 64) and ever
 ends with the RCCL all-gather of the fixed-size detection prefixes, issued on a side stream so
 that it overlaps the next round's kernels.
 
-Rank 0 prints ONE JSON line: candidate windows/s (whole job), plus
-  roofline     -- the dominant kernel's algorithmic HBM bytes per launch / its average launch
-                  duration (HIP events on the launch stream) against the 8 TB/s HBM peak
+Rank 0 prints ONE JSON line: candidate windows/s (whole job) and ms_per_step.  A plain run sets up, warms up, times
+exactly K steps (one region; --repeats R times R regions) and prints that line.  --full adds what takes runs or checks
+of its own (and times the median of 10 regions unless --repeats says otherwise):
+  parity       -- the replayed step's detections and alive counts against the oracle, bit for bit, before timing
+  kernels, roofline, issue_bound
+               -- per-kernel HIP-event durations; the dominant kernel's algorithmic HBM bytes per launch / its
+                  average launch duration against the 8 TB/s HBM peak
+  through_api  -- the same workload through Model.detect / Model.detect_stream
+  config3      -- BASELINE configs[3] through distributed.detect_sharded
   cpu_baseline -- the NumPy oracle (CPU restatement of the reference) on a bounded sample of
                   the same workload, multiprocessing.Pool over images like the reference's
                   scripts/waldboost-detect.py:64-67
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (write_outputs).
 """
 import argparse
 import json
@@ -187,6 +194,38 @@ def event_time_ms(fn, iters, torch):
     return e0.elapsed_time(e1) / iters
 
 
+DUMP_LIMIT_BYTES = 60 << 20       # --dump-outputs: array bytes in all (the .npy headers stay well inside 64 MB)
+DUMP_SEED = 20261016              # the fixed sample taken of outputs larger than that
+
+
+def write_outputs(out_dir, det, alive, limit=DUMP_LIMIT_BYTES):
+    """What one step left in its engine, as out_dir/<name>.npy: the detections in the reference's order (image, level, r,
+    c: one array per WbDet field, float64; score: float32) and alive[image, level, stage] (float64).  Past `limit` bytes,
+    a fixed seeded sample: whole images of alive (alive_images.npy: which) and rows of the detections (det_rows.npy).
+    Returns {name: array} as written."""
+    rng = np.random.default_rng(DUMP_SEED)
+    out = {}
+    alive = np.asarray(alive)
+    per_image = alive[0].size * 8 if alive.shape[0] else 0
+    if alive.shape[0] * per_image > limit // 2:
+        keep = np.sort(rng.choice(alive.shape[0], max(1, (limit // 2) // per_image), replace=False))
+        out["alive_images"] = keep.astype(np.float64)
+        alive = alive[keep]
+    out["alive"] = alive.astype(np.float64)
+    room = limit - sum(a.nbytes for a in out.values())
+    if det.size * (4 * 8 + 4) > room:
+        rows = np.sort(rng.choice(det.size, max(0, room // (5 * 8 + 4)), replace=False))
+        out["det_rows"] = rows.astype(np.float64)
+        det = det[rows]
+    for k in ("image", "level", "r", "c"):
+        out[f"det_{k}"] = det[k].astype(np.float64)
+    out["det_score"] = det["score"].astype(np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    return out
+
+
 def self_launch(n, argv):
     """`python bench.py --gpus N` with no launcher around it: start N ranks with torch.distributed.run (one process
     per GPU, rendezvous on 127.0.0.1 at a free port), pass the flags through, wait, return its exit code.  Runs before
@@ -214,22 +253,28 @@ def main():
                          "5: BASELINE configs[4] (4K, shrink 4, 12 per octave, 256 stages; 4 images per step by default)")
     ap.add_argument("--batch", type=int, default=0, help="images per step and GPU (default: 1 for --config 2 = configs[1]; "
                                                           "configs[2] is --batch 64; 4 for --config 5)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the parity gates against the oracle, per-kernel times with the roofline and "
+                         "issue bound, the rate through the Python API, BASELINE configs[3] and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (its detections and "
+                         "alive[image, level, stage]) as DIR/<name>.npy, float32 / float64, at most 64 MB")
     ap.add_argument("--no-config3", action="store_true",
-                    help="skip the configs[3] measurement (512 x 1080p cut over the ranks by shard_range, 64 images per launch, "
-                         "through distributed.detect_sharded with its end-of-batch exchange) that every line carries")
+                    help="with --full: skip the configs[3] measurement (512 x 1080p cut over the ranks by shard_range, 64 images "
+                         "per launch, through distributed.detect_sharded with its end-of-batch exchange)")
     ap.add_argument("--config3-images", type=int, default=CFG3_IMAGES, help="diagnostic: size of the configs[3] batch")
     ap.add_argument("--pool", type=int, default=4, help="distinct resident image batches cycled through")
     ap.add_argument("--streams", type=int, default=4,
                     help="HIP streams the steps are spread over (<= pool): consecutive steps work on different "
                          "images, so their kernels may overlap on the GPU like frames of a video pipeline")
-    ap.add_argument("--repeats", type=int, default=10,
+    ap.add_argument("--repeats", type=int, default=None,
                     help="the timed region of --steps steps is run this many times; `value` is the median region, "
-                         "`value_spread` carries min/max")
+                         "`value_spread` carries min/max (default: 1, so that exactly --steps steps are timed; 10 with --full)")
     ap.add_argument("--warm-ms", type=float, default=50.0,
                     help="untimed device work in front of the timed regions, in ms (as whole regions of --steps steps): the "
                          "GPU's clocks ramp for ~20 ms after the idle seconds of the parity gates")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-through-api", action="store_true", help="skip the host ndarray -> Boxes measurement (Model.detect)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-through-api", action="store_true", help="with --full: skip the host ndarray -> Boxes measurement (Model.detect)")
     ap.add_argument("--channels", choices=sorted(MODELS), default="grad_hist",
                     help="channel function of the workload; grad_hist is the BASELINE config, grad_hist_4_u1 the "
                          "reference's integer channels (same geometry, uint8 channels, its own calibrated cascade)")
@@ -260,7 +305,11 @@ def main():
     model_path = wl["models"][args.channels]
     if not args.batch:
         args.batch = wl["batch"]
-    want_cpu = not args.no_cpu_baseline and args.only == "all" and not args.dry_launch
+    if args.repeats is None:
+        args.repeats = 10 if args.full else 1
+    if args.dump_outputs and args.only != "all":
+        raise SystemExit("--dump-outputs writes what a whole step computed: it needs --only all")
+    want_cpu = args.full and not args.no_cpu_baseline and args.only == "all" and not args.dry_launch
     if args.no_jit:
         os.environ["WB_CASC_JIT"] = "0"                       # (also the engine's own after-a-few-scans policy; children inherit it)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -314,7 +363,8 @@ def main():
     # BASELINE configs[3]'s batch: THIS rank's contiguous shard of the 512 images, generated now (process pool, before
     # anything touches the GPU)
     cfg3_host = None
-    do_cfg3 = args.config == "2" and args.channels == "grad_hist" and args.only == "all" and not args.no_config3 and not args.stages
+    do_cfg3 = (args.full and args.config == "2" and args.channels == "grad_hist" and args.only == "all" and not args.no_config3
+               and not args.stages)
     if do_cfg3:
         from waldboost_amd.distributed import shard_range
         lo3, hi3 = shard_range(args.config3_images, rank, world)
@@ -324,8 +374,9 @@ def main():
 
     # the oracle's answers for the images the parity gates check (first and last image of the first and the last engine's
     # batch), computed now, in parallel
+    gated = args.full and args.only == "all" and not args.stages
     gate_refs = {}
-    if args.only == "all" and not args.stages:
+    if gated:
         Pn, Bn = max(1, args.pool), args.batch
         gate_refs = oracle_refs([(rank * Pn + j) * Bn + b for j in {0, min(Pn, args.steps) - 1} for b in {0, Bn - 1}],
                                 model_path, H, W)
@@ -440,7 +491,7 @@ def main():
                             "eval_cost": ref["n_weak"] / ref["n_loc"]})
         return {"path": path, "images": checked, "bit_exact": True}
 
-    if args.only == "all" and not args.stages:               # on EVERY rank: each checks its own engine 0 (its own images)
+    if gated:                                                # on EVERY rank: each checks its own engine 0 (its own images)
         poison(engines[0])
         steps[0]()
         torch.cuda.synchronize()
@@ -574,7 +625,7 @@ def main():
                       "engines": [dict(gate(engines[j], ""), engine=j) for j in checked]}
             for g in parity["engines"]:
                 g.pop("path")
-        if coll:
+        if coll and args.full:
             # ... and what the collective delivered: this rank's own block of the last step's slot, as every rank received
             # it, against the engine that packed it
             i_last = args.steps - 1
@@ -594,13 +645,29 @@ def main():
     # ... and for --warm-ms of device time: after idle seconds the GPU takes about 20 ms of work to reach its steady clocks
     # (twenty-step regions of 1.3 ms, timed back to back from a cold start: 0.067, 0.065, 0.064, ... 0.0595 ms per step
     # from the fifteenth on -- value_spread.ms_per_step_by_region shows whatever trend is left).  A count, not a clock:
-    # every rank replays the same number of regions (they hold collectives).
-    n_warm = max(1, int(round(args.warm_ms / max(args.steps * B * (0.06 if args.config == "2" else 0.35), 1e-3))))
-    for _ in range(n_warm):
-        if region is not None:
+    # every rank replays the same number of regions (they hold collectives).  Step by step, it is a count of steps, not of
+    # regions: a long --steps does not lengthen the warm-up.
+    step_ms = B * (0.06 if args.config == "2" else 0.35)
+    if region is not None:
+        n_warm = max(1, int(round(args.warm_ms / max(args.steps * step_ms, 1e-3))))
+        warm_steps = n_warm * args.steps
+        for _ in range(n_warm):
             run_region()
-        else:
-            run_steps(0, max(args.warmup, args.steps))
+    else:
+        warm_steps = max(args.warmup, int(np.ceil(args.warm_ms / step_ms)))
+        run_steps(0, warm_steps)
+    # ... and a timed region's form once more, untimed, between two synchronisations: the first region that starts behind
+    # the long wait for the warm-up paid ~0.1 ms more than those after it (twenty-step regions: 0.063 against 0.057 ms per
+    # step), and a plain run times ONE region.  Step by step, at most --warm-ms worth of steps.
+    torch.cuda.synchronize()
+    if region is not None:
+        run_region()
+        warm_steps += args.steps
+    else:
+        rehearsal = min(args.steps, int(np.ceil(args.warm_ms / step_ms)))
+        run_steps(0, rehearsal)
+        warm_steps += rehearsal
+    torch.cuda.synchronize()
     dts = []
     for rep in range(max(1, args.repeats)):
         torch.cuda.synchronize()
@@ -623,17 +690,29 @@ def main():
         mine = torch.tensor([float(np.median(dts)) / args.steps * 1e3, 1.0 if parity is not None else 0.0], dtype=torch.float64, device=cdev)
         allr = torch.zeros((world, 2), dtype=torch.float64, device=cdev)
         dist.all_gather_into_tensor(allr, mine.view(1, 2))
-        per_rank = {"ms_per_step": [float(x) for x in allr[:, 0].tolist()], "parity_gate_passed": [bool(x) for x in allr[:, 1].tolist()],
+        per_rank = {"ms_per_step": [float(x) for x in allr[:, 0].tolist()], "parity_gate_passed": [bool(x) for x in allr[:, 1].tolist()] if gated else None,
                     "world_size_reported": dist.get_world_size(), "backend": dist.get_backend()}
         tt = torch.tensor(dts, dtype=torch.float64, device=cdev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)            # every region: the slowest rank's time
         dts = [float(x) for x in tt.tolist()]
     dt = float(np.median(dts))
 
+    # ---- what the last timed step computed, read from the engine that ran it (before anything else uses the engines)
+    if rank == 0 and args.dump_outputs:
+        last = (args.steps - 1 if region is not None else args.warmup + max(1, args.repeats) * args.steps - 1) % P
+        e = engines[last]
+        if e.detb.max_count() > e.detb.cap:
+            raise SystemExit("bench: detection buffer overflow in the last timed step")
+        det = e.sorted_detections().cpu().numpy().view(nat.DET_DTYPE).reshape(-1)
+        alive = e._casc_state(dm)["alive"][:, :, :len(M)].cpu().numpy()
+        dumped = write_outputs(args.dump_outputs, det, alive)
+        print(f"bench: wrote {len(dumped)} arrays ({sum(a.nbytes for a in dumped.values()) / 1e6:.2f} MB) of engine {last}'s "
+              f"last step to {args.dump_outputs}", file=sys.stderr)
+
     # ---- per-kernel durations (HIP events, launch stream) and the roofline of the dominant one
     roof = None
     kern = {}
-    if rank == 0 and args.only == "all":
+    if rank == 0 and args.full and args.only == "all":
         e = engines[0]
         it = max(20, min(args.steps, 100))
         kern["octaves_ms"] = event_time_ms(e.launch_octaves, it, torch)
@@ -671,7 +750,7 @@ def main():
     # ---- the same workload through the reference's Python surface: host ndarray in, Boxes out (Model.detect,
     #      reference model.py:149-179) -- PCIe copies, kernels, ordering, boxes, synchronisation; never `value`
     through_api = None
-    if rank == 0 and args.only == "all" and not args.no_through_api and not args.stages and args.config == "2":
+    if rank == 0 and args.full and args.only == "all" and not args.no_through_api and not args.stages and args.config == "2":
         imgs = [synth_image(H, W, 7000 + i) for i in range(8)]
         for im in imgs[:3]:
             M.detect(im)
@@ -823,9 +902,11 @@ def main():
                                                                 else "hipGraph replay per step"), "only": args.only,
                        "channels_in_hbm": (("16-bit threshold ranks of the cascade (WB_DTYPE_RANK16)" if dm.rank_dtype == nat.WB_DTYPE_RANK16
                                             else "uint8 threshold ranks of the cascade (WB_DTYPE_RANK8)") if fused else spec.dtype.name),
-                       "streams": n_streams, "pool": P,
-                       "warm": f"{n_warm} untimed region(s) of {args.steps} steps right before the timed ones (--warm-ms {args.warm_ms:g})",
-                       "warm_steps_untimed": args.warmup + n_warm * (args.steps if region is not None else max(args.warmup, args.steps)),
+                       "streams": n_streams, "pool": P, "full": args.full,
+                       "warm": (f"{warm_steps // args.steps} untimed region(s) of {args.steps} steps" if region is not None
+                                else f"{warm_steps} untimed steps")
+                               + f" right before the timed ones (--warm-ms {args.warm_ms:g})",
+                       "warm_steps_untimed": args.warmup + warm_steps,
                        "cascade_kernel": (f"model-specialised (hiprtc at model load, {t_jit:.1f} s incl. cache lookup)" if jit else "generic"),
                        "collective": ("none" if not coll else
                                       "one all_gather of the K steps' packed detection prefixes at the end of every timed region" if gath_region is not None

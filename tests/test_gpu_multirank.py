@@ -200,7 +200,7 @@ def test_bench_multi_rank_region_with_its_exchange():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--force-collective", "--steps", "8", "--warmup", "2",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--force-collective", "--steps", "8", "--warmup", "2",
                         "--no-cpu-baseline", "--no-through-api", "--repeats", "2"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     assert len(r.stdout.strip().splitlines()) == 1, r.stdout

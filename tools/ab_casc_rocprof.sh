@@ -4,7 +4,7 @@ set -o pipefail
 cd "${GRAFT_REPO_ROOT:-.}"
 export TMPDIR=/tmp
 O=${1:-gpurun_out/ab_rocprof}; mkdir -p $O
-S="--no-cpu-baseline --no-through-api --no-config3 --repeats 2"
+S="--full --no-cpu-baseline --no-through-api --no-config3 --repeats 2"
 run() {
   make -C waldboost_amd/csrc clean > /dev/null 2>&1
   make -C waldboost_amd/csrc -j8 DEFS="$2" > $O/make_$1.log 2>&1 || { tail -5 $O/make_$1.log; exit 1; }
