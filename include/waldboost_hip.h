@@ -301,8 +301,8 @@ int wb_model_info(const WbModel *model, WbModelInfo *info);
  * on for that dtype; results are bit-identical to the generic kernel's -- which the call verifies before it returns: the
  * new kernel and the generic one scan a synthetic pyramid of byte tiles (8,493 windows, six passes; $WB_JIT_SELFTEST) and
  * must agree on every per-stage alive count and detection record.  WB_ERR_UNSUPPORTED for float32 channels, for models on
- * the node-walk kernel, and for a model none of whose builds passes that test; a failed compilation or a refused build
- * leaves the model on the generic kernel. */
+ * the node-walk kernel, and for a model whose build does not pass that test; a failed compilation also leaves the model
+ * on the generic kernel. */
 int wb_model_specialize(WbModel *model, int chn_dtype);
 /* ABI 8.  Make wb_cascade_launch ignore (enable = 0) or use again (1) the specialised kernels this model has loaded: with
  * them off the generic kernel scans.  For callers that cross-check a specialised kernel on their own data before they

@@ -62,7 +62,7 @@ def test_random_configuration(seed):
 
 # Seeds 558, 569 and 644 are the three of seeds 464..700 that failed in round 4 when the cascade kernel was specialised
 # before the first scan: depth-3 trees under a permissive cascade (10k-89k detections, tiles with more than 1024
-# survivors after eight stages).  The code one of the two compilers produced for them wrote a few wrong records per such
+# survivors after eight stages).  The code hiprtc produced for them wrote a few wrong records per such
 # tile; a specialised kernel is now self-tested against the generic one before use, and a model whose build fails stays on
 # the generic kernel (csrc/wb_api.hip jit_selftest).  Three passes each: the damage came and went.
 @pytest.mark.parametrize("seed", [558, 569, 644, 5, 18, 41])

@@ -78,8 +78,8 @@ def _kernel_scratch_sizes(blob):
 
 def test_no_cascade_kernel_of_the_library_uses_scratch_memory():
     """The cascade kernels keep their state in registers and LDS: `.private_segment_fixed_size` is 0 in the metadata of
-    every one of them (so is a specialised build expected to be: wb_model_specialize prefers a scratch-free build, and
-    wb_jit_compile_check fails on one with scratch).  The only kernels of the library
+    every one of them (so is a specialised build expected to be: wb_jit_compile_check fails on one with scratch).
+    The only kernels of the library
     with scratch are four instances of the channel kernel that spill two or three registers outside their loops."""
     nat.load()
     sizes = _kernel_scratch_sizes(open(nat.LIB_PATH, "rb").read())

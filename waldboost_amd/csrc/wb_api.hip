@@ -11,8 +11,10 @@
 
 int wb_cascade_prepare(int depth, int rpw, int waves);  // wb_cascade.hip
 int wb_cascade_group(int depth);                        // stages evaluated per group
+int wb_cascade_lds_bytes(int eb, int C, int rows, int pitch, int TR, int waves, int T, int lds_stages,
+                         int depth);                    // dynamic LDS of the tile kernel
 int wb_jit_get(const int32_t *words, size_t n_words, int T, int D, int rpw, int waves, int C, int rows, int pitch, int eb,
-               int lds_stages, int compiler, int allow_scratch, void **func_out);   // wb_jit.hip
+               int lds_stages, void **func_out);                                 // wb_jit.hip
 void wb_jit_release(void *func);                        // wb_jit.hip
 
 static thread_local char g_err[512] = "";
@@ -260,13 +262,10 @@ extern "C" int wb_model_create(int n_stages, const int32_t *node_off, const uint
         M->tile_rows = rpw * waves;
         M->lds_rows = M->tile_rows + m - 1;
         M->lds_stages = (n_stages * WB_STAGE_DWORDS(D) * 4 <= 16 * 1024) ? n_stages : 0;
-        // (layout: wb_cascade_tile.h, wb_lds_stab_off; 256 bytes of control words behind the stage mirror)
-        M->lds_bytes = ((C * M->lds_rows * M->lds_pitch * 4 + wb_casc_qcap(M->tile_rows, waves) * 8 + n_stages * 4 + 15) & ~15) +
-                       M->lds_stages * WB_STAGE_DWORDS(D) * 4 + 256;
-        M->lds_bytes_u8 = ((((C * M->lds_rows * M->lds_pitch + 15) & ~15) + wb_casc_qcap(M->tile_rows, waves) * 8 + n_stages * 4 + 15) & ~15) +
-                          M->lds_stages * WB_STAGE_DWORDS(D) * 4 + 256;
-        M->lds_bytes_u16 = ((((C * M->lds_rows * M->lds_pitch * 2 + 15) & ~15) + wb_casc_qcap(M->tile_rows, waves) * 8 + n_stages * 4 + 15) & ~15) +
-                           M->lds_stages * WB_STAGE_DWORDS(D) * 4 + 256;
+        auto lds = [&](int eb) { return wb_cascade_lds_bytes(eb, C, M->lds_rows, M->lds_pitch, M->tile_rows, waves, n_stages, M->lds_stages, D); };
+        M->lds_bytes = lds(0);
+        M->lds_bytes_u8 = lds(1);
+        M->lds_bytes_u16 = lds(2);
         if (M->lds_bytes <= budget || rpw <= 1) break;
     }
     if (!generic && M->lds_bytes > 160 * 1024) {
@@ -504,10 +503,9 @@ extern "C" int wb_model_use_specialized(WbModel *model, int enable) {
 // the same bytes: per-stage alive counts and the detection records (window, score bits).  The levels hold tiles of every
 // kind the kernel distinguishes -- regions of different byte statistics, so that under most cascades some tiles keep more
 // windows than the capped queue holds, some a few hundred, some a handful --, a ragged right and bottom edge, and a level
-// of a single partial tile.  Round 4 (profiles/r04/jit_selftest.txt): the code one hiprtc produced for some cascades of
-// depth-3 trees gave wrong records on nine scans of ten; nothing in the source explains it (the toolkit's own compiler, or
-// any of four unrelated build switches, gave bit-exact kernels).  A kernel that fails is not used: WB_ERR_UNSUPPORTED,
-// the model stays on the generic kernel.  WB_JIT_SELFTEST=<passes> (default 6; 0 = skip the test).
+// of a single partial tile.  (hiprtc's code for some cascades of depth-3 trees has given wrong records on nine scans of
+// ten: profiles/r04/jit_selftest.txt.)  A kernel that fails is not used: WB_ERR_UNSUPPORTED, the model stays on the
+// generic kernel.  WB_JIT_SELFTEST=<passes> (default 6; 0 = skip the test).
 static int jit_selftest(WbModel *model, int chn_dtype, void **slot) {
     static const int passes = getenv("WB_JIT_SELFTEST") ? atoi(getenv("WB_JIT_SELFTEST")) : 6;
     if (passes <= 0) return WB_OK;
@@ -665,39 +663,17 @@ extern "C" int wb_model_specialize(WbModel *model, int chn_dtype) {
         wb_set_error("wb_model_specialize: this model's specialised kernel failed its self-test earlier; it stays on the generic kernel");
         return WB_ERR_UNSUPPORTED;
     }
-    // Candidates: the build of the compiler in the process (its code is what the benchmark runs on) that keeps to registers
-    // and LDS, then its build with scratch memory; a candidate is used once it has passed the self-test.  With
-    // WB_JIT_COMPILERS=both the toolkit's compiler (wb_jit.hip: a second hiprtc in a link-map namespace of its own) is a
-    // second source of candidates, =toolkit the only one.  It is NOT on by default: its code passed where the first
-    // compiler's failed (60 scans of 60), but the compiler itself, running on that namespace's private copy of libc,
-    // crashed with a segmentation fault in about every second run of the full GPU test suite (never in a short process;
-    // the backtrace ends in libhiprtc.so.7 -> libc of the namespace).  A model whose first-compiler build fails the
-    // self-test stays on the generic kernel.
-    const char *which = getenv("WB_JIT_COMPILERS");
-    const char *only = which && strcmp(which, "both") == 0 ? nullptr : which ? which : "process";
-    int rc = WB_ERR_UNSUPPORTED;
-    char first_err[sizeof(g_err)] = "";
-    for (int allow_scratch = 0; allow_scratch < 2; ++allow_scratch) {
-        for (int compiler = 0; compiler < 2; ++compiler) {
-            if (only && strcmp(only, compiler == 0 ? "toolkit" : "process") == 0) continue;
-            if (model->jit_refused & (bit << (8 + 4 * compiler))) continue;      // (this compiler's build failed the self-test in the first round)
-            rc = wb_jit_get(ranks16 ? model->stages_bin16_host : ranks ? model->stages_bin_host : model->stages_u8_host, model->stage_words,
-                            model->n_stages, model->depth, model->rpw, model->waves, model->C, model->lds_rows, model->lds_pitch,
-                            ranks16 ? 2 : 1, model->lds_stages, compiler, allow_scratch, slot);
-            if (rc == WB_OK) {
-                rc = jit_selftest(model, chn_dtype, slot);
-                if (rc == WB_OK) return WB_OK;
-                wb_jit_release(*slot);                     // (a build that is not used is idle: wb_jit.hip unloads idle modules when it holds too many)
-                *slot = nullptr;
-                if (rc == WB_ERR_UNSUPPORTED) model->jit_refused |= bit << (8 + 4 * compiler);
-            }
-            if (getenv("WB_JIT_VERBOSE")) fprintf(stderr, "[wb_jit] compiler %d%s: %s\n", compiler, allow_scratch ? " (scratch allowed)" : "", g_err);
-            if (rc != WB_ERR_UNSUPPORTED) return rc;        // (a compiler or HIP error: report it, do not mask it with the next attempt)
-            if (!first_err[0]) snprintf(first_err, sizeof(first_err), "%s", g_err);
-        }
+    int rc = wb_jit_get(ranks16 ? model->stages_bin16_host : ranks ? model->stages_bin_host : model->stages_u8_host, model->stage_words,
+                        model->n_stages, model->depth, model->rpw, model->waves, model->C, model->lds_rows, model->lds_pitch,
+                        ranks16 ? 2 : 1, model->lds_stages, slot);
+    if (rc == WB_OK) {
+        rc = jit_selftest(model, chn_dtype, slot);
+        if (rc == WB_OK) return WB_OK;
+        wb_jit_release(*slot);                             // (a build that is not used is idle: wb_jit.hip unloads idle modules when it holds too many)
+        *slot = nullptr;
     }
-    model->jit_refused |= bit;
-    if (first_err[0]) wb_set_error("%s", first_err);
+    if (getenv("WB_JIT_VERBOSE")) fprintf(stderr, "[wb_jit] %s\n", g_err);
+    if (rc == WB_ERR_UNSUPPORTED) model->jit_refused |= bit;   // (a compiler or HIP error is reported, not remembered)
     return rc;
 }
 

@@ -564,6 +564,11 @@ int prepare_depth(int rpw, int waves) {
 
 int wb_cascade_group(int depth) { return depth >= 3 ? 2 : 4; }
 
+// dynamic LDS of the tile kernel in the layout of wb_cascade_tile.h; eb: 0 float32 tile, 1 bytes, 2 16-bit ranks
+int wb_cascade_lds_bytes(int eb, int C, int rows, int pitch, int TR, int waves, int T, int lds_stages, int depth) {
+    return (int)(wb_lds_stab_off(eb, C, rows, pitch, TR, T, waves) + (size_t)lds_stages * WB_STAGE_DWORDS(depth) * 4 + WB_LDS_CTL_BYTES);
+}
+
 int wb_cascade_prepare(int depth, int rpw, int waves) {
     switch (depth) {
         case 1: return prepare_depth<1>(rpw, waves);

@@ -74,15 +74,9 @@ __host__ __device__ constexpr size_t wb_lds_tile_bytes(int eb, int C, int rows, 
 // windows within its first eight stages (431 of 2048 survive them on the benchmark model), and the rare tile that keeps
 // more goes on DENSELY (a lane mask per row, as in phase A) eight stages at a time until its survivors fit.  Under 32 KB
 // of LDS a fifth workgroup fits a CU once waves of the resident four have left (they no longer wait at a final barrier).
-#ifndef WB_CASC_QCAP_DEFINED
-#define WB_CASC_QCAP_DEFINED
-#ifndef WB_CASC_QFULL
-#define WB_CASC_QFULL 0      // 1: the round-3 layout (A/B builds)
-#endif
 __host__ __device__ constexpr int wb_casc_qcap(int TR, int WAVES) {
-    return (WB_CASC_QFULL || TR * 64 < 64 * WAVES + 512) ? TR * 64 : 64 * WAVES + 512;
+    return TR * 64 < 64 * WAVES + 512 ? TR * 64 : 64 * WAVES + 512;
 }
-#endif
 __host__ __device__ constexpr size_t wb_lds_stab_off(int eb, int C, int rows, int pitch, int TR, int T, int WAVES) {
     return (wb_lds_tile_bytes(eb, C, rows, pitch) + (size_t)wb_casc_qcap(TR, WAVES) * 8 + (size_t)T * 4 + 15) & ~(size_t)15;
 }
@@ -99,9 +93,6 @@ __host__ __device__ constexpr size_t wb_lds_stab_off(int eb, int C, int rows, in
 #endif
 #ifndef WB_TAIL_PRIO
 #define WB_TAIL_PRIO 3       // s_setprio of a wave inside the stage-parallel tail (0 = off)
-#endif
-#ifndef WB_CASC_END_BARRIER
-#define WB_CASC_END_BARRIER 0    // 1: a workgroup barrier in front of the statistics flush instead of the arrival counter (A/B builds)
 #endif
 #ifndef WB_SEG_PREFETCH
 #define WB_SEG_PREFETCH 1    // BAKED segments: next group's gathers before this group's rejection tests
@@ -1150,17 +1141,6 @@ __device__ __forceinline__ void cascade_tile_body(const CascArgs &a, const int32
     // says so (one LDS atomic; its additions to hist are in before it counts) and
     // LEAVES; the last one to arrive flushes the sums.  The waves that carried nothing through the late stages -- most of
     // them -- used to wait here for a fifth of the workgroup's lifetime holding their wave slots.
-#if WB_CASC_END_BARRIER
-    __syncthreads();                                          // (A/B build: the round-3 ending -- every wave waits, all flush)
-    if (a.alive) {
-        uint32_t *al = a.alive + ((int64_t)b * a.n_levels + tile_d.level) * a.T;
-        for (int t = tid; t < T; t += NT) {
-            const uint32_t c = hist[t];
-            if (c) atomicAdd(al + t, c);
-        }
-    }
-    return;
-#endif
     uint32_t earlier = 0;
     if (a.dbg & 64) __syncthreads();          // diagnostic (WB_CASC_DBG=64): every wave stays until all are done, in the SAME binary
     // (LDS serves a wave's operations in order: this wave's additions to hist are performed before its arrival is; the

@@ -789,7 +789,6 @@ __device__ __forceinline__ void resample_tile(const ChanArgs &a, const WbLevel &
 
 // (launch bound: 4 workgroups = 4 waves per SIMD is what the 39 KB of LDS admit; without it the register
 // allocator may trade that occupancy for a few more registers -- measured: 138 VGPRs, 3 waves per SIMD, +17 % time)
-// (NT threads per workgroup: 256 for the 16 x 64 tile, 512 for the 32 x 64 tile -- the same 4 waves per SIMD either way)
 template <typename T, int S, int TU, int TV, bool SMOOTH, bool FAST, int NT>
 __global__ __launch_bounds__(NT, sizeof(T) == 8 ? 1 : S == 4 ? (sizeof(T) == 1 ? WB_CHAN_S4_WAVES : 1) : 4) void channels_kernel(ChanArgs a) {
     using G = TileGeom<S, TU, TV, SMOOTH, NT>;
@@ -974,39 +973,29 @@ __global__ __launch_bounds__(NT, sizeof(T) == 8 ? 1 : S == 4 ? (sizeof(T) == 1 ?
     // thread has left step 2 -- right behind it
     constexpr int LUT_VECS = WB_BIN_LUT_BYTES / 16, LUT16_VECS = WB_BIN16_LUT_BYTES / 16;
     auto ranks_wide_tag = [](const ChanArgs &aa) { return aa.rank != nullptr && aa.rank_wide != 0; };
-    static_assert(LUT_VECS == 768 && (NT == 256 || NT == 512), "three vectors per thread (256 threads), one or two (512)");
+    static_assert(LUT_VECS == 768 && NT == 256, "three vectors per thread");
     const bool ranks = a.rank != nullptr;
     uint4 lut0 = make_uint4(0, 0, 0, 0), lut1 = lut0, lut2 = lut0, lut3 = lut0, lut4 = lut0;
     const bool wide_lut = ranks_wide_tag(a);
     if (ranks) {
         lut0 = a.rank_lut[tid];
-        if (NT == 256 || tid < 256) lut1 = a.rank_lut[tid + NT];
-        if (NT == 256) lut2 = a.rank_lut[tid + 512];
+        lut1 = a.rank_lut[tid + 256];
+        lut2 = a.rank_lut[tid + 512];
         if (wide_lut) {                                       // (the 16-bit tables: 1280 vectors)
-            static_assert(LUT16_VECS == 1280, "five vectors per thread (256 threads)");
-            if (NT == 256) {
-                lut3 = a.rank_lut[tid + 768];
-                lut4 = a.rank_lut[tid + 1024];
-            } else {
-                if (tid >= 256) lut1 = a.rank_lut[tid + 512];     // 768 .. 1023 (threads 256..511 held nothing there)
-                if (tid < 256) lut2 = a.rank_lut[tid + 1024];     // 1024 .. 1279
-            }
+            static_assert(LUT16_VECS == 1280, "five vectors per thread");
+            lut3 = a.rank_lut[tid + 768];
+            lut4 = a.rank_lut[tid + 1024];
         }
     }
     __syncthreads();
     if (ranks) {
         uint4 *lut = reinterpret_cast<uint4 *>(lut_lds);
         lut[tid] = lut0;
-        if (NT == 256 || tid < 256) lut[tid + NT] = lut1;
-        if (NT == 256) lut[tid + 512] = lut2;
+        lut[tid + 256] = lut1;
+        lut[tid + 512] = lut2;
         if (wide_lut) {
-            if (NT == 256) {
-                lut[tid + 768] = lut3;
-                lut[tid + 1024] = lut4;
-            } else {
-                if (tid >= 256) lut[tid + 512] = lut1;
-                if (tid < 256) lut[tid + 1024] = lut2;
-            }
+            lut[tid + 768] = lut3;
+            lut[tid + 1024] = lut4;
         }
     }
     WB_CSTAMP(5);
@@ -1331,27 +1320,22 @@ __global__ void selftest_projection_kernel(ChanArgs a, uint32_t *mismatches) {
         if (__float_as_uint(f[k]) != __float_as_uint(r[k])) atomicAdd(mismatches, 1u);
 }
 
-template <typename T, int S, int TU, int TV, bool FAST, int NT = 256>
+template <typename T, int S, int TU, int TV, bool FAST>
 void launch_variant(hipStream_t st, dim3 grid, const ChanArgs &a, bool smooth) {
     // diagnostic (WB_CHAN_XLDS=bytes): extra dynamic LDS per workgroup lowers the workgroups per CU, to tell a
     // latency-bound kernel (time ~ 1 / residency) from a throughput-bound one (time unchanged)
     static const size_t xlds = getenv("WB_CHAN_XLDS") ? (size_t)atoi(getenv("WB_CHAN_XLDS")) : 0;
     if (smooth)
-        hipLaunchKernelGGL((channels_kernel<T, S, TU, TV, true, FAST, NT>), grid, dim3(NT), xlds, st, a);
+        hipLaunchKernelGGL((channels_kernel<T, S, TU, TV, true, FAST, 256>), grid, dim3(256), xlds, st, a);
     else
-        hipLaunchKernelGGL((channels_kernel<T, S, TU, TV, false, FAST, NT>), grid, dim3(NT), xlds, st, a);
+        hipLaunchKernelGGL((channels_kernel<T, S, TU, TV, false, FAST, 256>), grid, dim3(256), xlds, st, a);
 }
 
 template <typename T, bool FAST>
-int launch_dtype(hipStream_t st, dim3 grid, const ChanArgs &a, int shrink, bool smooth, bool tile32) {
+int launch_dtype(hipStream_t st, dim3 grid, const ChanArgs &a, int shrink, bool smooth) {
     switch (shrink) {
         case 1: launch_variant<T, 1, 16, 64, FAST>(st, grid, a, smooth); break;
-        case 2:
-            if (tile32)
-                launch_variant<T, 2, 32, 64, FAST, 512>(st, grid, a, smooth);
-            else
-                launch_variant<T, 2, 16, 64, FAST>(st, grid, a, smooth);
-            break;
+        case 2: launch_variant<T, 2, 16, 64, FAST>(st, grid, a, smooth); break;
         case 4: launch_variant<T, 4, 8, WB_CHAN_S4_TV, FAST>(st, grid, a, smooth); break;
         default:
             wb_set_error("wb_channels_launch: shrink=%d unsupported (1, 2; 4 as an extension)", shrink);
@@ -1569,15 +1553,6 @@ int launch_u1(hipStream_t st, dim3 grid, const ChanArgs &a, int shrink, bool smo
     return WB_OK;
 }
 
-// experiment (WB_CHAN_TILE32=1): grad_hist at shrink 2 on a 32 x 64 tile of 512 threads -- 14 % of the resized pixels a
-// workgroup computes are halo instead of 24 %, 5 % fewer vector instructions per image, and yet 39.6 against 33.0 us
-// per image at batch 64 (47.3 -> 51.5 at batch 1): two workgroups of eight waves per CU overlap their load and
-// compute phases worse than four of four.  Kept for A/B runs; the default is the 16 x 64 tile.
-bool tile32() {
-    static const bool t32 = getenv("WB_CHAN_TILE32") != nullptr;
-    return t32;
-}
-
 // the canonical constants np.cos/np.sin(np.linspace(0, pi, 5)[:-1]) the integer fast path is proven for
 const double kCanonCs[4] = {1.0, 0x1.6a09e667f3bcdp-1, 0x1.1a62633145c07p-54, -0x1.6a09e667f3bccp-1};
 const double kCanonSn[4] = {0.0, 0x1.6a09e667f3bccp-1, 1.0, 0x1.6a09e667f3bcdp-1};
@@ -1756,9 +1731,7 @@ extern "C" int wb_pool_smooth_launch(void *stream, const void *in, int chn_dtype
 extern "C" int wb_channels_tile(int channel_func, int shrink, int *tile_u, int *tile_v) {
     WB_REQUIRE(tile_u && tile_v, "wb_channels_tile: null pointer");
     if (shrink == 1 || shrink == 2) {
-        // (see tile32(): the 32 x 64 tile of 512 threads is an opt-in experiment)
-        const bool big = shrink == 2 && channel_func == WB_CHN_GRAD_HIST && tile32();
-        *tile_u = big ? 32 : 16;
+        *tile_u = 16;
         *tile_v = 64;
     } else if (shrink == 4) {
         *tile_u = 8;
@@ -1806,14 +1779,14 @@ void fill_patches(const WbLevel *levels, const WbTile *tiles, int n_tiles, WbTil
     }
 }
 template <bool FULL_ROWS>
-int fill_patches_for(int shrink, bool smooth, bool big, const WbLevel *levels, const WbTile *tiles, int n_tiles, WbTilePatch *out) {
+int fill_patches_for(int shrink, bool smooth, const WbLevel *levels, const WbTile *tiles, int n_tiles, WbTilePatch *out) {
     constexpr int TV4 = FULL_ROWS ? 32 : WB_CHAN_S4_TV;      // (the uint8 channel functions keep the 8 x 32 tile)
 #define WB_FP(S, TU, TV)                                                                  \
     if (smooth) fill_patches<TileGeom<S, TU, TV, true>, FULL_ROWS>(levels, tiles, n_tiles, out); \
     else fill_patches<TileGeom<S, TU, TV, false>, FULL_ROWS>(levels, tiles, n_tiles, out);
     switch (shrink) {
         case 1: WB_FP(1, 16, 64) return WB_OK;
-        case 2: if (big) { WB_FP(2, 32, 64) } else { WB_FP(2, 16, 64) } return WB_OK;
+        case 2: WB_FP(2, 16, 64) return WB_OK;
         case 4: WB_FP(4, 8, TV4) return WB_OK;
     }
 #undef WB_FP
@@ -1829,9 +1802,9 @@ extern "C" int wb_channels_tile_patches(int channel_func, int shrink, int smooth
         WB_REQUIRE(tiles_host[i].level >= 0 && tiles_host[i].level < n_levels, "wb_channels_tile_patches: tile %d names level %d of %d", i,
                    tiles_host[i].level, n_levels);
     if (channel_func == WB_CHN_GRAD_HIST)
-        return fill_patches_for<false>(shrink, smooth != 0, tile32(), levels_host, tiles_host, n_tiles, out_host);
+        return fill_patches_for<false>(shrink, smooth != 0, levels_host, tiles_host, n_tiles, out_host);
     if (channel_func == WB_CHN_GRAD_HIST_4_U1 || channel_func == WB_CHN_GRAD_MAG_U1)
-        return fill_patches_for<true>(shrink, smooth != 0, false, levels_host, tiles_host, n_tiles, out_host);
+        return fill_patches_for<true>(shrink, smooth != 0, levels_host, tiles_host, n_tiles, out_host);
     wb_set_error("wb_channels_tile_patches: channel function %d takes no patch table", channel_func);
     return WB_ERR_UNSUPPORTED;
 }
@@ -1925,13 +1898,13 @@ extern "C" int wb_channels_launch_x(void *stream, const void *img, int64_t img_s
     if (dtype == WB_DTYPE_U8) {
         // integer gradients + canonical constants: exact fp32 projection (see project_int)
         static const bool no_fast = getenv("WB_CHAN_NO_FAST") != nullptr;
-        if (canonical_constants(cs_sn) && !no_fast) return launch_dtype<uint8_t, true>(st, grid, a, shrink, smooth != 0, tile32());
-        return launch_dtype<uint8_t, false>(st, grid, a, shrink, smooth != 0, tile32());
+        if (canonical_constants(cs_sn) && !no_fast) return launch_dtype<uint8_t, true>(st, grid, a, shrink, smooth != 0);
+        return launch_dtype<uint8_t, false>(st, grid, a, shrink, smooth != 0);
     }
-    if (dtype == WB_DTYPE_F32) return launch_dtype<float, false>(st, grid, a, shrink, smooth != 0, tile32());
+    if (dtype == WB_DTYPE_F32) return launch_dtype<float, false>(st, grid, a, shrink, smooth != 0);
     if (wb_dtype_held_f64(dtype)) {
         a.src_int = wb_cast_mode(dtype);
-        return launch_dtype<double, false>(st, grid, a, shrink, smooth != 0, tile32());
+        return launch_dtype<double, false>(st, grid, a, shrink, smooth != 0);
     }
     wb_set_error("wb_channels_launch: unsupported image dtype code %d", dtype);
     return WB_ERR_UNSUPPORTED;

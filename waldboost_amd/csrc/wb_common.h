@@ -84,20 +84,6 @@ __device__ inline double wb_round_f16(double x) {
 #define WB_BIN16_CELLS 512
 #define WB_BIN16_LUT_BYTES (4 * WB_BIN16_SLOTS * 4 + 4 * WB_BIN16_CELLS * 2)   // float S[4][1024], then uint16 base[4][512]
 
-// entries of the cascade workgroup's survivor queue (wb_cascade_tile.h: the same definition, for the hiprtc build)
-#ifndef WB_CASC_QCAP_DEFINED
-#define WB_CASC_QCAP_DEFINED
-#ifndef WB_CASC_QFULL
-#define WB_CASC_QFULL 0
-#endif
-__host__ __device__ constexpr int wb_casc_qcap(int TR, int WAVES) {
-    return (WB_CASC_QFULL || TR * 64 < 64 * WAVES + 512) ? TR * 64 : 64 * WAVES + 512;
-}
-#endif
-#ifndef WB_CASC_END_BARRIER
-#define WB_CASC_END_BARRIER 0
-#endif
-
 // The canonical stage record the cascade kernels read with scalar loads:
 //   int   off[NI]   LDS byte offset of each internal node's feature (BFS order)
 //   float thr[NI]
@@ -152,7 +138,7 @@ struct WbModel {
     size_t stage_words;                          // (n_stages + G) * stage_dwords
     void *jit_u8, *jit_bin;
     int jit_off;                // 1 = wb_cascade_launch ignores the loaded specialised kernels (wb_model_use_specialized)
-    int jit_refused;            // bit per byte-tile kind (1 uint8, 2 ranks, 4 16-bit ranks): its specialised kernel was built and failed the self-test
+    int jit_refused;            // bit per byte-tile kind (1 uint8, 2 ranks, 4 16-bit ranks): its specialised kernel failed the self-test, no retry
     // trees deeper than WB_CASC_MAX_DEPTH: generic node-walk kernel on the reference's own flat arrays
     int generic;                // 1 = use cascade_generic_kernel
     int32_t *g_node_off;        // [n_stages + 1]

@@ -8,10 +8,6 @@
 // for a model that is scanned often enough to be worth ~2 s of compilation.  Compiled code objects are kept in
 // the process and in a cache directory ($WB_JIT_CACHE, default ~/.cache/waldboost_amd), keyed by a hash of the
 // generated source, the target and the hiprtc version.
-#ifndef _GNU_SOURCE
-#define _GNU_SOURCE        // dlmopen
-#endif
-#include <dlfcn.h>
 #include <hip/hiprtc.h>
 #include <stdlib.h>
 #include <string.h>
@@ -24,7 +20,6 @@
 #include <map>
 #include <mutex>
 #include <string>
-#include <type_traits>
 #include <vector>
 
 #include "wb_common.h"
@@ -42,82 +37,11 @@ struct JitKernel {
     hipFunction_t func = nullptr;
     int users = 0;                            // models holding the function (wb_jit_get / wb_jit_release)
     uint64_t released = 0;                    // when the last of them let go (a counter): the oldest idle module goes first
-    int scratch = 0;                          // bytes of scratch memory per lane the build asks for
 };
 
 std::mutex g_mu;
 std::map<uint64_t, JitKernel> g_loaded;      // per process: hash -> loaded module
 uint64_t g_release_clock = 0;
-
-// Two compilers can stand behind a specialised kernel:
-//   0  the hiprtc the process already holds -- the library links libhiprtc.so.7; under PyTorch that name resolves to the
-//      copy its wheel bundles (ROCm 7.0 there), under rocprofv3 to the toolkit's.  The default, and the only one by default;
-//   1  the hiprtc of the ROCm toolkit the library was built with (WB_ROCM_LIB_DIR, set by the Makefile from hipcc's
-//      location; WB_HIPRTC_LIB=<file> picks another), for WB_JIT_COMPILERS=both / toolkit.  A second libhiprtc +
-//      libamd_comgr with the sonames of loaded ones can only live in a link-map namespace of its own: dlmopen(LM_ID_NEWLM),
-//      on first use -- which also gives it a private copy of libc, and that is where it crashed in long processes.
-// Round 4: compiler 0's code for some cascades of depth-3 trees wrote wrong records on nine scans of ten (tests/
-// test_gpu_fuzz.py seeds 558, 569, 644; profiles/r04/jit_selftest.txt) and fails the self-test; compiler 1's code for the
-// same source passed 60 of 60.  wb_model_specialize trusts a build only after the self-test, whichever compiler made it.
-struct Rtc {
-    decltype(&hiprtcCreateProgram) create = &hiprtcCreateProgram;
-    decltype(&hiprtcCompileProgram) compile = &hiprtcCompileProgram;
-    decltype(&hiprtcGetProgramLogSize) log_size = &hiprtcGetProgramLogSize;
-    decltype(&hiprtcGetProgramLog) log = &hiprtcGetProgramLog;
-    decltype(&hiprtcGetCodeSize) code_size = &hiprtcGetCodeSize;
-    decltype(&hiprtcGetCode) code = &hiprtcGetCode;
-    decltype(&hiprtcDestroyProgram) destroy = &hiprtcDestroyProgram;
-    decltype(&hiprtcGetErrorString) error_string = &hiprtcGetErrorString;
-    decltype(&hiprtcVersion) version = &hiprtcVersion;
-    std::string origin = "process";
-    bool ok = true;
-};
-
-const Rtc &rtc_process() {
-    static const Rtc r;
-    return r;
-}
-
-const Rtc &rtc_toolkit() {
-    static const Rtc r = [] {
-        Rtc y;
-        y.ok = false;
-        const char *env = getenv("WB_HIPRTC_LIB");
-#ifdef WB_ROCM_LIB_DIR
-        const std::string path = env && *env ? std::string(env) : std::string(WB_ROCM_LIB_DIR) + "/libhiprtc.so.7";
-#else
-        const std::string path = env && *env ? std::string(env) : std::string();
-#endif
-        y.origin = path;
-        if (path.empty()) return y;
-        void *h = dlmopen(LM_ID_NEWLM, path.c_str(), RTLD_NOW | RTLD_LOCAL);
-        if (!h) {
-            if (getenv("WB_JIT_VERBOSE")) fprintf(stderr, "[wb_jit] %s: %s\n", path.c_str(), dlerror());
-            return y;
-        }
-        bool ok = true;
-        auto sym = [&](auto &fp, const char *name) {
-            void *p = dlsym(h, name);
-            if (!p) ok = false;
-            else fp = reinterpret_cast<std::remove_reference_t<decltype(fp)>>(p);
-        };
-        sym(y.create, "hiprtcCreateProgram");
-        sym(y.compile, "hiprtcCompileProgram");
-        sym(y.log_size, "hiprtcGetProgramLogSize");
-        sym(y.log, "hiprtcGetProgramLog");
-        sym(y.code_size, "hiprtcGetCodeSize");
-        sym(y.code, "hiprtcGetCode");
-        sym(y.destroy, "hiprtcDestroyProgram");
-        sym(y.error_string, "hiprtcGetErrorString");
-        sym(y.version, "hiprtcVersion");
-        if (!ok && getenv("WB_JIT_VERBOSE")) fprintf(stderr, "[wb_jit] %s lacks a hiprtc entry point\n", path.c_str());
-        y.ok = ok;
-        return y;
-    }();
-    return r;
-}
-
-const Rtc &rtc_of(int which) { return which == 0 ? rtc_process() : rtc_toolkit(); }
 
 uint64_t fnv1a(const void *p, size_t n, uint64_t h = 1469598103934665603ull) {
     const unsigned char *b = static_cast<const unsigned char *>(p);
@@ -157,10 +81,9 @@ std::string make_source(const int32_t *words, size_t n_words, int T, int D, int 
     }
     s += "\n#define WB_JIT_SEGMENTS(X)" + segment_list(T) + "\n";
     s += "#define WB_JIT_LDS_STAGES " + std::to_string(lds_stages < 0 ? T : lds_stages) + "\n";
-    // (the ending and the occupancy floor can be overridden per build through WB_JIT_DEFS: diagnostics)
-    s += "#define WB_JIT_WAVES " + std::to_string(waves) + "\n#define WB_CASC_QFULL " + std::to_string((int)WB_CASC_QFULL) +
-         "\n#ifndef WB_CASC_END_BARRIER\n#define WB_CASC_END_BARRIER " + std::to_string((int)WB_CASC_END_BARRIER) +
-         "\n#endif\n#ifndef WB_JIT_OCC_MIN\n#define WB_JIT_OCC_MIN " + std::to_string(occ_min) + "\n#endif\n#ifndef WB_JIT_ATTR_EXTRA\n#define WB_JIT_ATTR_EXTRA\n#endif\n";
+    // (the occupancy floor can be overridden per build through WB_JIT_DEFS: diagnostics)
+    s += "#define WB_JIT_WAVES " + std::to_string(waves) + "\n#ifndef WB_JIT_OCC_MIN\n#define WB_JIT_OCC_MIN " + std::to_string(occ_min) +
+         "\n#endif\n#ifndef WB_JIT_ATTR_EXTRA\n#define WB_JIT_ATTR_EXTRA\n#endif\n";
     s += "#define WB_JIT_T " + std::to_string(T) + "\n#define WB_JIT_C " + std::to_string(C) + "\n#define WB_JIT_ROWS " +
          std::to_string(rows) + "\n#define WB_JIT_PITCH " + std::to_string(pitch) + "\n";
     s += "#include \"wb_cascade_tile.h\"\n";
@@ -233,13 +156,13 @@ void write_file_atomic(const std::string &dir, const std::string &path, const st
 }
 
 // source -> code object for `arch` (no HIP runtime call: works without a GPU)
-int compile(const Rtc &R, const std::string &src, const char *arch, std::vector<char> &code, std::string &log) {
+int compile(const std::string &src, const char *arch, std::vector<char> &code, std::string &log) {
     hiprtcProgram prog;
     const char *hdr_src[] = {kTileSrc};
     const char *hdr_name[] = {"wb_cascade_tile.h"};
-    hiprtcResult r = R.create(&prog, src.c_str(), "wb_casc_jit.hip", 1, hdr_src, hdr_name);
+    hiprtcResult r = hiprtcCreateProgram(&prog, src.c_str(), "wb_casc_jit.hip", 1, hdr_src, hdr_name);
     if (r != HIPRTC_SUCCESS) {
-        log = std::string("hiprtcCreateProgram: ") + R.error_string(r);
+        log = std::string("hiprtcCreateProgram: ") + hiprtcGetErrorString(r);
         return WB_ERR_HIP;
     }
     const std::string a = std::string("--offload-arch=") + arch;
@@ -258,34 +181,34 @@ int compile(const Rtc &R, const std::string &src, const char *arch, std::vector<
     }
     std::vector<const char *> opts = {a.c_str(), "-O3", "-std=c++17", "-ffp-contract=off", "-Wno-pragma-once-outside-header", "-Wno-inline-asm"};
     for (const std::string &x : extra) opts.push_back(x.c_str());
-    r = R.compile(prog, (int)opts.size(), opts.data());
+    r = hiprtcCompileProgram(prog, (int)opts.size(), opts.data());
     size_t ls = 0;
-    if (R.log_size(prog, &ls) == HIPRTC_SUCCESS && ls > 1) {
+    if (hiprtcGetProgramLogSize(prog, &ls) == HIPRTC_SUCCESS && ls > 1) {
         log.resize(ls);
-        (void)R.log(prog, &log[0]);
+        (void)hiprtcGetProgramLog(prog, &log[0]);
     }
     if (getenv("WB_JIT_VERBOSE") && !log.empty()) fprintf(stderr, "[wb_jit] %s\n", log.c_str());
     if (r != HIPRTC_SUCCESS) {
         const size_t at = log.find("error:");                     // (warnings first: show the first error)
         if (at != std::string::npos) log = log.substr(at > 120 ? at - 120 : 0);
-        log = std::string("hiprtcCompileProgram: ") + R.error_string(r) + "\n" + log;
-        (void)R.destroy(&prog);
+        log = std::string("hiprtcCompileProgram: ") + hiprtcGetErrorString(r) + "\n" + log;
+        (void)hiprtcDestroyProgram(&prog);
         return WB_ERR_HIP;
     }
     size_t cs = 0;
-    r = R.code_size(prog, &cs);
+    r = hiprtcGetCodeSize(prog, &cs);
     if (r == HIPRTC_SUCCESS) {
         code.resize(cs);
-        r = R.code(prog, code.data());
+        r = hiprtcGetCode(prog, code.data());
     }
-    (void)R.destroy(&prog);
+    (void)hiprtcDestroyProgram(&prog);
     if (const char *d = getenv("WB_JIT_DUMP_DIR")) {            // diagnostic: the generated source and the code object
         const std::string base = std::string(d) + "/wb_casc_jit";
         if (FILE *f = fopen((base + ".hip").c_str(), "w")) { fwrite(src.data(), 1, src.size(), f); fclose(f); }
         if (FILE *f = fopen((base + ".co").c_str(), "wb")) { fwrite(code.data(), 1, code.size(), f); fclose(f); }
     }
     if (r != HIPRTC_SUCCESS || code.empty()) {
-        log = std::string("hiprtcGetCode: ") + R.error_string(r);
+        log = std::string("hiprtcGetCode: ") + hiprtcGetErrorString(r);
         return WB_ERR_HIP;
     }
     return WB_OK;
@@ -311,13 +234,10 @@ int scratch_bytes(const std::vector<char> &code) {
 
 // Scratch memory: every cascade kernel of the library keeps its state in registers and LDS, and a specialised build is
 // expected to.  What used to send two lane addresses of a depth-3 or 1024-stage build to scratch is dealt with in the
-// source (wb_cascade_tile.h: relane, WB_INLINE_LAMBDA).  A build that asks for scratch anyway is not wrong -- it was
-// suspected in round 4 and cleared (profiles/r04/jit_selftest.txt) -- but second choice: wb_model_specialize takes it only
-// when neither compiler has a scratch-free build that passes the self-test (the toolkit's compiler spills 60 bytes per
-// lane in the 128-stage benchmark kernel; under rocprofv3, whose libraries put that compiler into the process first, this
-// is the build that runs).  wb_jit_compile_check (the CPU suite) is strict: scratch fails the check.
-int build_checked(const Rtc &R, const std::string &src, const char *arch, std::vector<char> &code, std::string &log) {
-    const int rc = compile(R, src, arch, code, log);
+// source (wb_cascade_tile.h: relane, WB_INLINE_LAMBDA).  wb_model_specialize accepts a build that asks for scratch anyway
+// (its self-test decides); wb_jit_compile_check (the CPU suite) is strict: scratch fails the check.
+int build_checked(const std::string &src, const char *arch, std::vector<char> &code, std::string &log) {
+    const int rc = compile(src, arch, code, log);
     if (rc != WB_OK) return rc;
     const int sb = scratch_bytes(code);
     if (sb == 0) return WB_OK;
@@ -334,37 +254,25 @@ void evict_idle_modules();
 }
 
 // Build (or fetch) the specialised kernel for one stage table of `M`.  words: (T + G) records of SD dwords as uploaded.
-// compiler: 0 = the hiprtc in the process, 1 = the toolkit's (see Rtc above); WB_ERR_UNSUPPORTED when that one cannot be had,
-// and when its build asks for scratch memory while allow_scratch is 0 (the code object stays in the cache either way).
 int wb_jit_get(const int32_t *words, size_t n_words, int T, int D, int rpw, int waves, int C, int rows, int pitch, int eb, int lds_stages,
-               int compiler, int allow_scratch, void **func_out) {
+               void **func_out) {
     *func_out = nullptr;
-    const Rtc &R = rtc_of(compiler);
-    if (!R.ok) {
-        wb_set_error("wb_model_specialize: the toolkit's hiprtc (%s) could not be loaded", R.origin.c_str());
-        return WB_ERR_UNSUPPORTED;
-    }
     hipDeviceProp_t prop;
     int dev = 0;
     WB_HIP_CHECK(hipGetDevice(&dev));
     WB_HIP_CHECK(hipGetDeviceProperties(&prop, dev));
     const std::string src = make_source(words, n_words, T, D, rpw, waves, C, rows, pitch, eb, lds_stages);
     int rtc_major = 0, rtc_minor = 0;
-    (void)R.version(&rtc_major, &rtc_minor);
+    (void)hiprtcVersion(&rtc_major, &rtc_minor);
     uint64_t h = fnv1a(src.data(), src.size());
     h = fnv1a(kTileSrc, sizeof(kTileSrc), h);
     h = fnv1a(prop.gcnArchName, strlen(prop.gcnArchName), h);
     h = fnv1a(&rtc_major, sizeof(int), fnv1a(&rtc_minor, sizeof(int), h));
-    h = fnv1a(R.origin.data(), R.origin.size(), h);
     h = fnv1a(&dev, sizeof(int), h);                         // (a module is loaded per device)
     if (const char *e = getenv("WB_JIT_DEFS")) h = fnv1a(e, strlen(e), h);
     std::lock_guard<std::mutex> lock(g_mu);
     auto it = g_loaded.find(h);
     if (it != g_loaded.end()) {
-        if (it->second.scratch != 0 && !allow_scratch) {
-            wb_set_error("wb_model_specialize: this build asks for scratch memory (%d bytes per lane)", it->second.scratch);
-            return WB_ERR_UNSUPPORTED;
-        }
         ++it->second.users;
         *func_out = it->second.func;
         return WB_OK;
@@ -375,17 +283,12 @@ int wb_jit_get(const int32_t *words, size_t n_words, int T, int D, int rpw, int 
     std::vector<char> code;
     if (path.empty() || !read_file(path, code) || !plausible_code_object(path, code)) {
         std::string log;
-        const int rc = compile(R, src, prop.gcnArchName, code, log);
+        const int rc = compile(src, prop.gcnArchName, code, log);
         if (rc != WB_OK) {
             wb_set_error("wb_model_specialize: %.400s", log.c_str());
             return rc;
         }
         if (!path.empty()) write_file_atomic(dir, path, code);
-    }
-    const int sb = scratch_bytes(code);
-    if (sb != 0 && !allow_scratch) {
-        wb_set_error("wb_model_specialize: this build asks for scratch memory (%d bytes per lane)", sb);
-        return WB_ERR_UNSUPPORTED;
     }
     JitKernel k;
     hipError_t e = hipModuleLoadData(&k.module, code.data());
@@ -396,7 +299,6 @@ int wb_jit_get(const int32_t *words, size_t n_words, int T, int D, int rpw, int 
         return WB_ERR_HIP;
     }
     k.users = 1;
-    k.scratch = sb;
     g_loaded[h] = k;
     evict_idle_modules();
     *func_out = k.func;
@@ -468,13 +370,7 @@ extern "C" int wb_jit_compile_check2(int depth, int n_stages, int elem_bytes, co
     const int lds_stages = n_stages * SD * 4 <= 16 * 1024 ? n_stages : 0;
     std::vector<char> code;
     std::string log;
-    // (the compiler in the process, or -- WB_JIT_CHECK_COMPILER=1 -- the toolkit's)
-    const Rtc &R = rtc_of(getenv("WB_JIT_CHECK_COMPILER") ? atoi(getenv("WB_JIT_CHECK_COMPILER")) : 0);
-    if (!R.ok) {
-        wb_set_error("wb_jit_compile_check: the toolkit's hiprtc (%s) could not be loaded", R.origin.c_str());
-        return WB_ERR_UNSUPPORTED;
-    }
-    const int rc = build_checked(R, make_source(words.data(), words.size(), n_stages, depth, 4, 8, 4, 4 * 8 + 11, WB_CASC_TC + 12, elem_bytes, lds_stages),
+    const int rc = build_checked(make_source(words.data(), words.size(), n_stages, depth, 4, 8, 4, 4 * 8 + 11, WB_CASC_TC + 12, elem_bytes, lds_stages),
                                  arch, code, log);
     if (rc != WB_OK) {
         wb_set_error("wb_jit_compile_check: %.400s", log.c_str());
