@@ -111,6 +111,11 @@ typedef const volatile __attribute__((address_space(3))) unsigned char *LdsVolBy
 __device__ __forceinline__ uint8_t lds_byte_vol(const unsigned char *patch, int off) {
     return *((LdsVolBytePtr)patch + off);
 }
+// ... and two bytes at an even offset (one aligned ds_read_u16; volatile for the same reason: never merged with the next pair)
+typedef const volatile __attribute__((address_space(3))) uint16_t *LdsVolU16Ptr;
+__device__ __forceinline__ uint32_t lds_u16_vol(const unsigned char *base, int off) {
+    return *(LdsVolU16Ptr)((LdsVolBytePtr)base + off);
+}
 
 // scipy's order-1 resample of one output pixel: fp64, taps and additions in NI_ZoomShift's order
 __device__ inline double resample_f64(double v00, double v01, double v10, double v11, const Tap &tr, const Tap &tc) {
@@ -241,16 +246,14 @@ __device__ inline float scalar_only(float v) {
 // reference channels.py:78-83: nine-term sum in source order; numba promotes int64*float32 to
 // fp64, so the sum is fp64; "/16" and one rounding to fp32 on the store.
 // 2*x and 4*x are exact, so fma(2, b, acc) rounds exactly like acc + 2*b: same bits, half the ops.
+// The chain row by row (the top, middle and bottom row's three terms), for callers that stream the rows.
+__device__ inline double smooth_top(double a, double b, double c) { return __builtin_fma(2.0, b, a) + c; }
+__device__ inline double smooth_mid(double s, double d, double e, double f) {
+    return __builtin_fma(2.0, f, __builtin_fma(4.0, e, __builtin_fma(2.0, d, s)));
+}
+__device__ inline float smooth_bot(double s, double g, double h, double i) { return (float)((__builtin_fma(2.0, h, s + g) + i) * 0.0625); }
 __device__ inline float smooth9(double a, double b, double c, double d, double e, double f, double g, double h, double i) {
-    double s = __builtin_fma(2.0, b, a);
-    s = s + c;
-    s = __builtin_fma(2.0, d, s);
-    s = __builtin_fma(4.0, e, s);
-    s = __builtin_fma(2.0, f, s);
-    s = s + g;
-    s = __builtin_fma(2.0, h, s);
-    s = s + i;
-    return (float)(s * 0.0625);
+    return smooth_bot(smooth_mid(smooth_top(a, b, c), d, e, f), g, h, i);
 }
 
 // grad_hist projection of one pixel: out[k] = | fp32( fp64(gx)*cos_k - fp64(gy)*sin_k ) |
@@ -787,22 +790,30 @@ __device__ __forceinline__ void resample_tile(const ChanArgs &a, const WbLevel &
     }
 }
 
-// (launch bound: 4 workgroups = 4 waves per SIMD is what the 39 KB of LDS admit; without it the register
-// allocator may trade that occupancy for a few more registers -- measured: 138 VGPRs, 3 waves per SIMD, +17 % time)
+// (launch bound: 4 workgroups = 4 waves per SIMD is what the 39 KB of LDS of a float R admit; without it the register
+// allocator may trade that occupancy for a few more registers -- measured: 138 VGPRs, 3 waves per SIMD, +17 % time.
+// Shrink 2 on uint8 images with the smooth -- the detection path -- is held to five: 26 KB of LDS, <= 96 VGPRs)
 template <typename T, int S, int TU, int TV, bool SMOOTH, bool FAST, int NT>
-__global__ __launch_bounds__(NT, sizeof(T) == 8 ? 1 : S == 4 ? (sizeof(T) == 1 ? WB_CHAN_S4_WAVES : 1) : 4) void channels_kernel(ChanArgs a) {
+__global__ __launch_bounds__(NT, sizeof(T) == 8 ? 1
+                                 : S == 4  ? (sizeof(T) == 1 ? WB_CHAN_S4_WAVES : 1)
+                                 : (S == 2 && sizeof(T) == 1 && SMOOTH && FAST) ? 5
+                                                                               : 4) void channels_kernel(ChanArgs a) {
     using G = TileGeom<S, TU, TV, SMOOTH, NT>;
     constexpr int HS = G::HS, SV = G::SV, RH = G::RH, RW = G::RW, P = G::P;
     constexpr int PATCH_BYTES = sizeof(T) == 1 ? G::PATCH_BYTES : 0;
     constexpr int UNI_MIN = G::SH_BYTES > PATCH_BYTES ? G::SH_BYTES : PATCH_BYTES;
-    constexpr int UNI_LUT = (S == 4 && sizeof(T) == 1 && WB_CHAN_S4_BYTES) ? ((G::SH_BYTES + 15) & ~15) + WB_BIN16_LUT_BYTES : 0;
-    constexpr int UNI_BYTES = UNI_MIN > UNI_LUT ? UNI_MIN : UNI_LUT;
-    // Shrink 4, uint8 images (round 4): R holds the resized pixels as BYTES (they are integers 0..255) -- 5.9 KB instead of
-    // 23 KB, and the rank tables are parked behind the shrunk tile in `uni` (the dead source patch) instead of in R: 31 KB of
+    // uint8 images at shrink 2 and 4: R holds the resized pixels as BYTES (they are integers 0..255) -- a quarter of the LDS,
+    // and the rank tables no longer fit in R: they go to `uni`.
+    // Shrink 4 (round 4): 5.9 KB instead of 23 KB, the tables parked behind the shrunk tile (the dead source patch): 31 KB of
     // LDS per workgroup = five per CU instead of three.  The kernel at this shrink is latency-bound (16 resized pixels per
     // output: three workgroups kept the vector ALUs 42 % busy), so residency is what it wants; the price is one conversion
     // per R store and 36 per shrunk pixel's patch read.
-    constexpr bool RBYTES = S == 4 && sizeof(T) == 1 && WB_CHAN_S4_BYTES;
+    // Shrink 2 (round 5): 5.2 KB instead of 20.4 KB; the tables do not fit behind the 19 KB shrunk tile, so they go OVER it,
+    // once every thread has read its Sh values (one more barrier): 26 KB of LDS instead of 40 KB per workgroup.
+    constexpr bool RBYTES = sizeof(T) == 1 && (S == 2 || (S == 4 && WB_CHAN_S4_BYTES));
+    constexpr bool LUT_OVER_SH = RBYTES && S == 2;
+    constexpr int UNI_LUT = !RBYTES ? 0 : LUT_OVER_SH ? WB_BIN16_LUT_BYTES : ((G::SH_BYTES + 15) & ~15) + WB_BIN16_LUT_BYTES;
+    constexpr int UNI_BYTES = UNI_MIN > UNI_LUT ? UNI_MIN : UNI_LUT;
     using RT = typename std::conditional<RBYTES, uint8_t, float>::type;
     constexpr int RP = RPitch<RT, RW>::value;
     constexpr bool LUT_IN_UNI = RBYTES;
@@ -812,7 +823,7 @@ __global__ __launch_bounds__(NT, sizeof(T) == 8 ? 1 : S == 4 ? (sizeof(T) == 1 ?
     __shared__ __attribute__((aligned(16))) unsigned char Rraw[R_BYTES];
     RT *R = reinterpret_cast<RT *>(Rraw);
     __shared__ __attribute__((aligned(16))) unsigned char uni[UNI_BYTES];
-    unsigned char *lut_lds = LUT_IN_UNI ? uni + ((G::SH_BYTES + 15) & ~15) : Rraw;
+    unsigned char *lut_lds = LUT_OVER_SH ? uni : LUT_IN_UNI ? uni + ((G::SH_BYTES + 15) & ~15) : Rraw;
     __shared__ uint32_t odd_values;      // set when a shrunk value lies outside the exact-sum range (see step 3)
     __shared__ float4 rowtab[sizeof(T) == 1 ? RH + RW % 64 : 1];   // row taps of the tile, taps of the RW % 64 last columns (uint8 images, staged patch)
     F4 *Sh = reinterpret_cast<F4 *>(uni);
@@ -844,6 +855,40 @@ __global__ __launch_bounds__(NT, sizeof(T) == 8 ? 1 : S == 4 ? (sizeof(T) == 1 ?
     // ---- step 2: gradients -> 4 oriented channels -> shrink, one shrunk pixel per call
     //      Rp: the pixel's (S + 2) x (S + 2) patch of R, Shp: where its shrunk value goes
     auto shrunk_pixel = [&](const int ro, const int so) {     // (offsets, not pointers: R's alignment stays visible -- 8-byte reads)
+        float ch[S][S][4], gxs[S][S], gys[S][S];
+        constexpr bool TWO_PASS = FAST && S > 1;          // ordinary values first, residues only where they can show
+        if constexpr (RBYTES && S == 2) {
+            // The 4 x 4 patch starts at the even column 2j of a dword-padded row: a patch row is two aligned 16-bit reads
+            // (volatile: never merged into one dword read at a 2-byte boundary, which LDS serves slowly) and four byte
+            // conversions.  The gradients are then formed differences first -- the centre row / column of a [-1,0,1] pass
+            // has weight 0 -- and [1,2,1] pass second: on pixels 0..255 every partial sum is an integer of magnitude <= 1020,
+            // exact in fp32 in either order, so gx and gy are the values the passes below give (zeros included: +0 both ways).
+            float pt[P][P];
+#pragma unroll
+            for (int y = 0; y < P; ++y) {
+                const uint32_t lo = lds_u16_vol(Rraw, ro + y * RP), hi = lds_u16_vol(Rraw, ro + y * RP + 2);
+                pt[y][0] = (float)(lo & 0xffu);
+                pt[y][1] = (float)(lo >> 8);
+                pt[y][2] = (float)(hi & 0xffu);
+                pt[y][3] = (float)(hi >> 8);
+            }
+            float ex[P][S], dy[S][P];     // column differences (for gx), row differences (for gy)
+#pragma unroll
+            for (int r = 0; r < P; ++r)
+#pragma unroll
+                for (int x = 0; x < S; ++x) ex[r][x] = scalar_only(pt[r][x] - pt[r][x + 2]);
+#pragma unroll
+            for (int y = 0; y < S; ++y)
+#pragma unroll
+                for (int c = 0; c < P; ++c) dy[y][c] = scalar_only(pt[y][c] - pt[y + 2][c]);
+#pragma unroll
+            for (int y = 0; y < S; ++y)
+#pragma unroll
+                for (int x = 0; x < S; ++x) {
+                    gxs[y][x] = scalar_only(Src<T>::hpass(ex[y][x], ex[y + 1][x], ex[y + 2][x]));
+                    gys[y][x] = scalar_only(Src<T>::hpass(dy[y][x], dy[y][x + 1], dy[y][x + 2]));
+                }
+        } else {
         float pt[P][P];
         if constexpr (RBYTES) {
             // six bytes per patch row = two aligned dwords (the patch starts at column S * j = 4 j of a dword-padded row)
@@ -877,16 +922,19 @@ __global__ __launch_bounds__(NT, sizeof(T) == 8 ? 1 : S == 4 ? (sizeof(T) == 1 ?
 #pragma unroll
             for (int x = 0; x < S; ++x) hr[y][x] = scalar_only(Src<T>::hpass(pt[y][x], pt[y][x + 1], pt[y][x + 2]));
 
-        float ch[S][S][4], gxs[S][S], gys[S][S];
-        constexpr bool TWO_PASS = FAST && S > 1;          // ordinary values first, residues only where they can show
 #pragma unroll
         for (int y = 0; y < S; ++y)
 #pragma unroll
             for (int x = 0; x < S; ++x) {
-                const float gx = scalar_only(Src<T>::dpass(hc[y][x], hc[y][x + 1], hc[y][x + 2]));
-                const float gy = scalar_only(Src<T>::dpass(hr[y][x], hr[y + 1][x], hr[y + 2][x]));
-                gxs[y][x] = gx;
-                gys[y][x] = gy;
+                gxs[y][x] = scalar_only(Src<T>::dpass(hc[y][x], hc[y][x + 1], hc[y][x + 2]));
+                gys[y][x] = scalar_only(Src<T>::dpass(hr[y][x], hr[y + 1][x], hr[y + 2][x]));
+            }
+        }
+#pragma unroll
+        for (int y = 0; y < S; ++y)
+#pragma unroll
+            for (int x = 0; x < S; ++x) {
+                const float gx = gxs[y][x], gy = gys[y][x];
                 if constexpr (TWO_PASS)
                     project_ordinary(gx, gy, a, ch[y][x]);
                 else if constexpr (FAST)
@@ -970,7 +1018,8 @@ __global__ __launch_bounds__(NT, sizeof(T) == 8 ? 1 : S == 4 ? (sizeof(T) == 1 ?
         }
     }
     // rank tables of the model (12 KiB, L2-resident): requested before the barrier, parked in R -- dead once every
-    // thread has left step 2 -- right behind it
+    // thread has left step 2 -- right behind it (float R), behind the shrunk tile (shrink 4, byte R), or over the shrunk
+    // tile once the smooth has read it (shrink 2, byte R: the loads are in flight across the smooth)
     constexpr int LUT_VECS = WB_BIN_LUT_BYTES / 16, LUT16_VECS = WB_BIN16_LUT_BYTES / 16;
     auto ranks_wide_tag = [](const ChanArgs &aa) { return aa.rank != nullptr && aa.rank_wide != 0; };
     static_assert(LUT_VECS == 768 && NT == 256, "three vectors per thread");
@@ -981,23 +1030,28 @@ __global__ __launch_bounds__(NT, sizeof(T) == 8 ? 1 : S == 4 ? (sizeof(T) == 1 ?
         lut0 = a.rank_lut[tid];
         lut1 = a.rank_lut[tid + 256];
         lut2 = a.rank_lut[tid + 512];
-        if (wide_lut) {                                       // (the 16-bit tables: 1280 vectors)
-            static_assert(LUT16_VECS == 1280, "five vectors per thread");
+        if (wide_lut && !LUT_OVER_SH) {                       // (the 16-bit tables: 1280 vectors)
             lut3 = a.rank_lut[tid + 768];
             lut4 = a.rank_lut[tid + 1024];
         }
     }
-    __syncthreads();
-    if (ranks) {
+    static_assert(LUT16_VECS == 1280, "five vectors per thread");
+    auto park_tables = [&]() {
         uint4 *lut = reinterpret_cast<uint4 *>(lut_lds);
         lut[tid] = lut0;
         lut[tid + 256] = lut1;
         lut[tid + 512] = lut2;
         if (wide_lut) {
+            if constexpr (LUT_OVER_SH) {                      // (requested only here: 8 registers fewer across the smooth)
+                lut3 = a.rank_lut[tid + 768];
+                lut4 = a.rank_lut[tid + 1024];
+            }
             lut[tid + 768] = lut3;
             lut[tid + 1024] = lut4;
         }
-    }
+    };
+    __syncthreads();
+    if (!LUT_OVER_SH && ranks) park_tables();
     WB_CSTAMP(5);
 
     if (a.dbg & 2) return;
@@ -1047,20 +1101,24 @@ __global__ __launch_bounds__(NT, sizeof(T) == 8 ? 1 : S == 4 ? (sizeof(T) == 1 ?
                 }
             }
         } else {
-            double w[RPT + 2][3][4];
+            // the rows streamed: each output's chain takes its three rows in order (smooth9 row by row), so a row is widened
+            // once, used by the up to three outputs whose window holds it, and dropped -- the tile's 72 widened values are
+            // never live at once (with the rank tables in flight across the smooth they did not fit the registers; the
+            // scheduling barrier keeps the compiler from hoisting every row's reads to the top again)
+            double s[RPT][4];
 #pragma unroll
-            for (int y = 0; y < RPT + 2; ++y)
+            for (int r = 0; r < RPT + 2; ++r) {
+                __builtin_amdgcn_sched_barrier(0);
+                const F4 c0 = Sh[(i0 + r) * SV + j], c1 = Sh[(i0 + r) * SV + j + 1], c2 = Sh[(i0 + r) * SV + j + 2];
+                const float a0[4] = {c0.x, c0.y, c0.z, c0.w}, a1[4] = {c1.x, c1.y, c1.z, c1.w}, a2[4] = {c2.x, c2.y, c2.z, c2.w};
 #pragma unroll
-                for (int x = 0; x < 3; ++x) {
-                    F4 c = Sh[(i0 + y) * SV + (j + x)];
-                    w[y][x][0] = (double)c.x; w[y][x][1] = (double)c.y; w[y][x][2] = (double)c.z; w[y][x][3] = (double)c.w;
+                for (int k = 0; k < 4; ++k) {
+                    const double v0 = a0[k], v1 = a1[k], v2 = a2[k];
+                    if (r >= 2) o[r - 2][k] = smooth_bot(s[r - 2][k], v0, v1, v2);
+                    if (r >= 1 && r - 1 < RPT) s[r - 1][k] = smooth_mid(s[r - 1][k], v0, v1, v2);
+                    if (r < RPT) s[r][k] = smooth_top(v0, v1, v2);
                 }
-#pragma unroll
-            for (int y = 0; y < RPT; ++y)
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    o[y][k] = smooth9(w[y][0][k], w[y][1][k], w[y][2][k], w[y + 1][0][k], w[y + 1][1][k], w[y + 1][2][k],
-                                      w[y + 2][0][k], w[y + 2][1][k], w[y + 2][2][k]);
+            }
         }
     } else {
 #pragma unroll
@@ -1068,6 +1126,10 @@ __global__ __launch_bounds__(NT, sizeof(T) == 8 ? 1 : S == 4 ? (sizeof(T) == 1 ?
             F4 c = Sh[(i0 + y) * SV + j];
             o[y][0] = c.x; o[y][1] = c.y; o[y][2] = c.z; o[y][3] = c.w;
         }
+    }
+    if (LUT_OVER_SH && ranks) {
+        __syncthreads();                                      // every thread holds its Sh values: the tables go over them
+        park_tables();
     }
     WB_CSTAMP(6);
 #pragma unroll
