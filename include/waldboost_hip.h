@@ -38,6 +38,9 @@
  *   reference waldboost/samples.py:14-43 (gather_samples), waldboost/model.py:181-214 (Model.predict),
  *        waldboost/training.py:73-83 (DTree.apply/predict): the training-time callers of the hot path
  *        -> wb_gather_samples_launch, wb_samples_predict_launch, wb_tree_apply_launch
+ *   reference waldboost/testing.py:46 (bbx.non_max_suppression on a detector's result) and
+ *        scripts/waldboost-detect.py:36 (detect(..., iou_threshold=0.2, score_threshold=0, separate=False))
+ *        -> wb_nms_launch, wb_nms_ordered_launch; wb_nms_finish_launch (on the buffer wb_det_finish_sorted_launch / wb_det_order_batch_launch left)
  */
 #ifndef WALDBOOST_HIP_H
 #define WALDBOOST_HIP_H
@@ -438,6 +441,61 @@ int wb_tree_apply_launch(void *stream, const void *X, int x_dtype, int64_t n_sam
  *   inv_scale  dev float[n_levels] = float32(1.0/scale) computed on the host in fp64 */
 int wb_boxes_launch(void *stream, const WbDet *det, int64_t n_det, const float *inv_scale,
                     int m, int n, float *boxes /* [n_det][4] */, float *scores /* [n_det] */);
+
+/* Greedy non-maximum suppression (reference testing.py:46 bbx.non_max_suppression; scripts/waldboost-detect.py:36).
+ * New symbols of ABI 8 (the version number did not change: nothing that existed did).
+ *   * when use_score_threshold != 0, boxes with `not (score >= score_threshold)` are dropped first;
+ *   * the boxes are visited by score, highest first; -0.0 and +0.0 are equal; boxes of equal score in INPUT ORDER
+ *     (NumPy: np.argsort(-scores, kind="stable")).  Scores must not be NaN;
+ *   * a box is kept unless an already kept box of the same group has iou > iou_threshold with it (strict; a double);
+ *   * iou in float64 on the float32 coordinates: iw = max(min(ax2, bx2) - max(ax1, bx1), 0), ih alike, inter = iw * ih,
+ *     areas (x2 - x1) * (y2 - y1), union = area_a + area_b - inter, inter / union, 0 where union <= 0 -- every operation
+ *     rounded on its own, the divide correctly rounded;
+ *   * keep[i] = 1 for a kept box, 0 otherwise, in input order; n_keep[0] = their number.
+ *   boxes    dev float32 [n][4] XYXY, 16-byte aligned;  scores dev float32 [n];  group dev int32 [n] or NULL (one group)
+ *   scratch  dev, 16-byte aligned, wb_nms_scratch_bytes(n) bytes: per box 25 bytes (box, group, input index and dropped
+ *            flag in visiting order), 16 bytes per 64 boxes (two bitmaps), 16 bytes of counters, rounded up to 256, then the
+ *            suppression matrix of one BAND of rows: rows x ceil(n / 64) 64-bit words (upper triangle used).  A band is
+ *            min(4096, n rounded up to 64) rows -- less, in multiples of 64, when that exceeds 64 MiB or when the caller
+ *            hands in less: any size of at least the fixed part + 64 rows works, more bands are more launches.
+ *   keep     dev uint8 [n];  n_keep dev uint32 [1]
+ * wb_nms_launch finds the visiting order itself, by counting for every box the boxes in front of it: n * n comparisons,
+ * 0.22 ms measured at 3 000 boxes (12 workgroups, each thread walking all boxes); a thread's walk grows with n, so some
+ * 5 ms are to be expected at its limit of 2^16 boxes (WB_ERR_UNSUPPORTED above).
+ * wb_nms_ordered_launch takes the visiting order from the caller: order dev uint32 [n], a permutation of 0 .. n - 1 -- the
+ * stable descending sort of the scores (an entry >= n is skipped: that position visits nothing); n up to 2^26, what a
+ * finish buffer's key can count.  What remains is the greedy algorithm's own cost: n * n / 2 float64 IoU tests (27 us at
+ * 3 000 boxes) in bands of at most 4096 rows, three launches per band, the scan of a band on ONE wave (0.25 ms at 3 000
+ * boxes, 1 700 of them kept).  10^5 boxes are 25 bands; 2^20 boxes are 5 * 10^11 tests in 2 048 bands of 512 rows (a
+ * row is 128 KiB there) -- seconds, by that arithmetic, not by measurement; sizes beyond that are accepted for completeness, not because they are quick, and want
+ * 8 * 64 * ceil(n / 64) bytes of matrix at the least.  wb_nms_scratch_bytes answers for both (n up to 2^26).
+ * Three launches up to 4096 boxes.  No host synchronisation. */
+int wb_nms_scratch_bytes(int64_t n, size_t *bytes);
+int wb_nms_launch(void *stream, const float *boxes, const float *scores, const int32_t *group, int64_t n,
+                  double iou_threshold, int use_score_threshold, float score_threshold, void *scratch,
+                  size_t scratch_bytes, uint8_t *keep, uint32_t *n_keep);
+int wb_nms_ordered_launch(void *stream, const float *boxes, const float *scores, const int32_t *group, const uint32_t *order,
+                          int64_t n, double iou_threshold, int use_score_threshold, float score_threshold, void *scratch,
+                          size_t scratch_bytes, uint8_t *keep, uint32_t *n_keep);
+
+/* The same on a finish buffer, right behind the launch that wrote it and before the read-back:
+ *   fin      dev: one image's block header[4] | keys | boxes | scores of capacity out_capacity as
+ *            wb_det_finish_sorted_launch / wb_det_finish_launch wrote it; n_images > 1: image b's block at
+ *            fin + b * (16 + 28 * out_capacity) bytes (wb_det_order_batch_launch's `out + 16`).  Not modified.
+ *            header[3] == 1: the sections are in key order and the input order is the position; header[3] == 0: packed
+ *            order, the input order is the KEY order (ties between equal scores go to the smaller key; equal keys, which
+ *            no launch of this library writes, to the smaller position).  (The header[3]
+ *            of wb_det_finish_launch is the shard capacity: for such a buffer the caller stores 0 there first.)
+ *   result   dev, 4-byte aligned: per image 16 + out_capacity bytes:  uint32 info[4] = (kept boxes, boxes NMS ran over,
+ *            done, 0) | uint8 keep[out_capacity], keep[i] for the box at position i of the sections.  done = 0: the image
+ *            has more detections than the block holds or than 4096 -- nothing else was written for it (use
+ *            wb_nms_launch on the complete result then).
+ *   scratch  dev, 16-byte aligned, wb_nms_finish_scratch_bytes(out_capacity, n_images) bytes
+ * out_capacity a multiple of 4.  One group.  Three launches for all images, no host synchronisation. */
+int wb_nms_finish_scratch_bytes(uint32_t out_capacity, int n_images, size_t *bytes);
+int wb_nms_finish_launch(void *stream, const void *fin, uint32_t out_capacity, int n_images, double iou_threshold,
+                         int use_score_threshold, float score_threshold, void *scratch, size_t scratch_bytes,
+                         void *result);
 
 /* Device self-test: the uint8 fast path of the orientation projection (fp32 arithmetic that is
  * proven equal to the reference's fp64 formula for integer gradients) is compared with the fp64

@@ -6,7 +6,7 @@ All compute runs in hand-written HIP kernels (csrc/) through the C ABI in
 include/waldboost_hip.h; there is no CPU fallback.
 """
 from . import channels, fpga, model_pb2, samples, testing
-from .boxes import Boxes, concatenate
+from .boxes import Boxes, concatenate, non_max_suppression
 from .model import Model
 from .samples import SamplePool
 from .training import DTree
@@ -23,16 +23,22 @@ def save_model(model, filename):
 
 save = save_model
 
-def detect(image, *models, channel_opts=None, response_scale=None):
+def detect(image, *models, channel_opts=None, response_scale=None, iou_threshold=None, score_threshold=None, separate=False):
     """Detect objects with several models sharing one channel pyramid (reference
     waldboost/__init__.py:75-130): returns Boxes with 'scores' (multiplied by response_scale[k]) and
     'label' (index of the model that fired).  Order: pyramid level, then model, then row-major
     window order -- as the reference's nested loops produce it.  The reference's `np.int` label
-    dtype (removed in NumPy 1.24) is int64 here."""
+    dtype (removed in NumPy 1.24) is int64 here.
+    iou_threshold, score_threshold, separate: non-maximum suppression of that result (the reference's detection script,
+    scripts/waldboost-detect.py:36; semantics: non_max_suppression), on the scaled scores; separate=True: boxes of
+    different models never suppress each other ('label' is the group), False: all boxes are one group.  None: no
+    suppression."""
     import numpy as np
     from . import engine as _engine
+    from .model import _nms_args
     if not models:
         raise ValueError("detect needs at least one model")
+    nms = _nms_args(iou_threshold, score_threshold)
     channel_opts = channel_opts or models[0].channel_opts
     if response_scale is None:
         response_scale = [1] * len(models)
@@ -81,10 +87,12 @@ def detect(image, *models, channel_opts=None, response_scale=None):
     out = Boxes(boxes.reshape(-1, 4).astype(np.float32, copy=False))
     out.set_field("scores", scores.astype(np.float32, copy=False))
     out.set_field("label", label[order])
+    if nms is not None:
+        out = non_max_suppression(out, nms[0], nms[1], group=out.get_field("label") if separate else None)
     return out
 
 
 default_channel_opts = dict(shrink=2, n_per_oct=8, smooth=1, channels=channels.grad_hist)
 
-__all__ = ["Model", "DTree", "Boxes", "concatenate", "SamplePool", "channels", "fpga", "samples", "testing", "detect", "load", "load_model", "save", "save_model",
+__all__ = ["Model", "DTree", "Boxes", "concatenate", "non_max_suppression", "SamplePool", "channels", "fpga", "samples", "testing", "detect", "load", "load_model", "save", "save_model",
            "default_channel_opts"]

@@ -90,6 +90,11 @@ SYMBOLS = {
     "wb_det_order_batch_launch": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_size_t,
                                             _P, C.c_uint32]),
     "wb_selftest_projection": (C.c_int, [_P, _P]),
+    "wb_nms_scratch_bytes": (C.c_int, [C.c_int64, C.POINTER(C.c_size_t)]),
+    "wb_nms_launch": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_double, C.c_int, C.c_float, _P, C.c_size_t, _P, _P]),
+    "wb_nms_ordered_launch": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_double, C.c_int, C.c_float, _P, C.c_size_t, _P, _P]),
+    "wb_nms_finish_scratch_bytes": (C.c_int, [C.c_uint32, C.c_int, C.POINTER(C.c_size_t)]),
+    "wb_nms_finish_launch": (C.c_int, [_P, _P, C.c_uint32, C.c_int, C.c_double, C.c_int, C.c_float, _P, C.c_size_t, _P]),
 }
 
 _lib = None

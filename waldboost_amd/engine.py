@@ -957,7 +957,54 @@ class PyramidEngine:
                   "wb_det_finish_sorted_launch")
         stt["h_final"].copy_(stt["final"], non_blocking=True)
 
-    def fetch_final(self, dm, stt, enqueued=False, stream=None):
+    def _nms_buffers(self, holder, rows, n_images):
+        """Result block, its page-locked copy and the scratch of wb_nms_finish_launch for `n_images` finish blocks of
+        `rows` rows, kept in `holder` (a scan state, the batch's order buffers); None when the rows do not fit the
+        launch (then the caller suppresses the complete result with boxes.nms_keep_mask)."""
+        import ctypes as C
+        import torch
+        if rows < 4 or rows % 4:
+            return None
+        nb = holder.get("nms")
+        if nb is None or nb["rows"] != rows or nb["images"] != n_images:
+            need = C.c_size_t()
+            nat.check(self.lib.wb_nms_finish_scratch_bytes(rows, n_images, C.byref(need)), "wb_nms_finish_scratch_bytes")
+            nb = holder["nms"] = dict(rows=rows, images=n_images,
+                                      scratch=torch.empty(need.value, dtype=torch.uint8, device=self.dev),
+                                      res=torch.empty(n_images * (16 + rows), dtype=torch.uint8, device=self.dev),
+                                      h_res=torch.empty(n_images * (16 + rows), dtype=torch.uint8).pin_memory())
+            nb["h"] = nb["h_res"].numpy().reshape(n_images, 16 + rows)
+        return nb
+
+    def _nms_enqueue(self, holder, fin_ptr, rows, n_images, nms):
+        """wb_nms_finish_launch on the finish block(s) at `fin_ptr` + the copy of its keep flags into page-locked memory,
+        in the current stream, behind the launch that wrote the blocks (no synchronisation).
+        nms: (iou_threshold, score_threshold or None)."""
+        import ctypes as C
+        nb = self._nms_buffers(holder, rows, n_images)
+        if nb is None:
+            return
+        iou_t, score_t = nms
+        nat.check(self.lib.wb_nms_finish_launch(nat.stream_ptr(), C.c_void_p(fin_ptr), rows, n_images, float(iou_t),
+                                                0 if score_t is None else 1, 0.0 if score_t is None else float(score_t),
+                                                nat.ptr(nb["scratch"]), nb["scratch"].numel(), nat.ptr(nb["res"])),
+                  "wb_nms_finish_launch")
+        nb["h_res"].copy_(nb["res"], non_blocking=True)
+
+    @staticmethod
+    def _nms_keep(holder, b, rows, total):
+        """Image b's keep flags (bool [total]) from the read-back of _nms_enqueue; None when the device did not
+        suppress this image (more detections than a block holds)."""
+        nb = holder.get("nms")
+        if nb is None or nb["rows"] != rows:
+            return None
+        row = nb["h"][b]
+        info = row[:16].view(np.uint32)
+        if int(info[2]) != 1 or int(info[1]) != total:
+            return None
+        return row[16:16 + total].astype(bool)
+
+    def fetch_final(self, dm, stt, enqueued=False, stream=None, nms=None):
         """fetch() for Model.detect on ONE image: wb_det_finish_launch leaves sort keys, boxes and scores of all
         valid records behind one header; they come back with ONE copy and ONE event wait together with alive[B, L, T].
         Returns (keys uint64 [n] (level << 54 | r << 40 | c << 26 | position), boxes float32 [rows, 4], scores
@@ -967,13 +1014,19 @@ class PyramidEngine:
         detections): use fetch() then.  Grows the detection buffer and scans again if a shard overflowed.
         enqueued: the launch and the copies are already in the stream (detect_run's graph replay).
         stream: that stream, when it is not the current one -- then only the wait happens here, and False is returned
-        if more than a wait is needed (the caller comes back on that stream)."""
+        if more than a wait is needed (the caller comes back on that stream).
+        nms: (iou_threshold, score_threshold or None) -- non-maximum suppression ran (enqueued) or runs (not enqueued)
+        on the finish buffer behind the launch that wrote it, a scan repeated after an overflow included; the result then
+        has a sixth member: the keep flags (bool [n], positions of the finish buffer), or None when the device did not
+        suppress (the caller then suppresses the complete result)."""
         if not self._final_ready():
             return None
         P, T = self._FETCH_ROWS, dm.n_stages
         while True:
             if not enqueued:
                 self._final_enqueue(dm, stt)
+                if nms is not None:
+                    self._nms_enqueue(stt, stt["final"].data_ptr(), self._FETCH_ROWS, 1, nms)
             enqueued = False
             if stream is None:
                 self._fetch_ev.record()
@@ -992,6 +1045,8 @@ class PyramidEngine:
         if total > P:
             return None
         alive = stt["h_alive"][:, :, :T].astype(np.int64)
+        if nms is not None:
+            return keys[:total], boxes, scores, alive, bool(hdr[3]), self._nms_keep(stt, 0, P, total)
         return keys[:total], boxes, scores, alive, bool(hdr[3])
 
     _ORDER_ROWS = 4096               # per image: what wb_det_order_batch_launch orders (more: the caller's other path)
@@ -1024,7 +1079,7 @@ class PyramidEngine:
                     self._inv_scales_d = torch.from_numpy(self.inv_scales()).to(self.dev)
         return self._order["fits"]
 
-    def order_batch_enqueue(self, dm, stt):
+    def order_batch_enqueue(self, dm, stt, nms=None):
         """wb_det_order_batch_launch on the last scan's detections + the read-back copies (ordered results, alive[B, L, T])
         into page-locked memory + an event, all in the current stream, no synchronisation: what fetch_ordered_batch
         waits for.  Enqueued right behind the step, the results are on the host by the time they are asked for.
@@ -1042,10 +1097,12 @@ class PyramidEngine:
                   "wb_det_order_batch_launch")
         od["h_out"].copy_(od["out"], non_blocking=True)
         self._h_alive.copy_(stt["alive"], non_blocking=True)
+        if nms is not None:                                   # (every image's block suppressed in the same three launches)
+            self._nms_enqueue(od, od["out"].data_ptr() + 16, self._ORDER_ROWS, self.batch, nms)
         od["ev"].record()
         return True
 
-    def fetch_ordered_batch(self, dm, stt, enqueued=False):
+    def fetch_ordered_batch(self, dm, stt, enqueued=False, nms=None):
         """fetch() for a batch whose results are wanted image by image in the reference's order (Model.detect_stream's
         batches): wb_det_order_batch_launch splits the shards' records by image and orders every image's keys, boxes
         and scores on the device; they come back with ONE copy and ONE event wait together with alive[B, L, T].
@@ -1053,10 +1110,12 @@ class PyramidEngine:
         Grows the detection buffer and scans again if a shard overflowed.
         Returns ([(keys uint64 [n_b], boxes float32 [n_b, 4], scores float32 [n_b]) per image], alive int64 [B, L, T])
         -- views of the page-locked read-back buffer: copy what is kept -- or None when this form does not apply (a
-        pyramid beyond the sort key's bit fields, an image with more than _ORDER_ROWS detections): use fetch() then."""
+        pyramid beyond the sort key's bit fields, an image with more than _ORDER_ROWS detections): use fetch() then.
+        nms: as for order_batch_enqueue (with enqueued, what it was given there); every image's tuple then has a fourth
+        member, its keep flags (bool [n_b]) or None."""
         T = dm.n_stages
         while True:
-            if not enqueued and not self.order_batch_enqueue(dm, stt):
+            if not enqueued and not self.order_batch_enqueue(dm, stt, nms):
                 return None
             enqueued = False
             od = self._order
@@ -1072,7 +1131,10 @@ class PyramidEngine:
             n_b = int(hdr[0])
             if int(hdr[1]) > self._ORDER_ROWS or int(hdr[3]) != 1:
                 return None
-            out.append((keys[:n_b], boxes[:n_b], scores[:n_b]))
+            if nms is not None:
+                out.append((keys[:n_b], boxes[:n_b], scores[:n_b], self._nms_keep(od, len(out), self._ORDER_ROWS, n_b)))
+            else:
+                out.append((keys[:n_b], boxes[:n_b], scores[:n_b]))
         return out, self._h_alive.numpy()[:, :, :T].astype(np.int64)
 
     def live_check(self, dm):
@@ -1104,14 +1166,17 @@ class PyramidEngine:
                 return                                                # (stays off)
             dm.use_specialized(True)
 
-    def detect_run(self, dm):
+    def detect_run(self, dm, nms=None):
         """Model.detect's whole device sequence for the resident image -- one memset, octaves, channels, cascade,
         wb_det_finish_sorted_launch (which also carries alive[] behind the scores), the ONE read-back copy -- and its one synchronisation; from the second call with the
         same cascade on it is replayed as ONE hipGraph (one enqueue instead of seven, no gaps between the kernels).
-        Returns what fetch_final returns, or None (then: run(dm) has happened, use fetch())."""
-        return self.detect_collect(dm, self.detect_enqueue(dm))
+        Returns what fetch_final returns, or None (then: run(dm) has happened, use fetch()).
+        nms: (iou_threshold, score_threshold or None) -- the same step, eager or replayed, then wb_nms_finish_launch and the
+        copy of its keep flags enqueued behind it, in front of the one wait: the plain step's graph is shared, a new
+        threshold captures nothing."""
+        return self.detect_collect(dm, self.detect_enqueue(dm, nms), nms=nms)
 
-    def detect_enqueue(self, dm):
+    def detect_enqueue(self, dm, nms=None):
         """detect_run up to, not including, its wait: everything is in the current stream when this returns (the image
         must stay resident until detect_collect, on the same stream, has run).  Returns a token for detect_collect."""
         import torch
@@ -1136,9 +1201,11 @@ class PyramidEngine:
         if g is None:
             self.run(dm)
             self._final_enqueue(dm, stt)
-            return stt
-        self.ensure_clean_keys()
-        g.replay()
+        else:
+            self.ensure_clean_keys()
+            g.replay()
+        if nms is not None:
+            self._nms_enqueue(stt, stt["final"].data_ptr(), self._FETCH_ROWS, 1, nms)
         return stt
 
     def batch_enqueue(self, dm):
@@ -1229,18 +1296,18 @@ class PyramidEngine:
             st["fails"] = 0
         return out
 
-    def detect_collect(self, dm, token, stream=None):
+    def detect_collect(self, dm, token, stream=None, nms=None):
         """The wait and the read-back that end detect_run, for a token of detect_enqueue.
         stream: the stream detect_enqueue ran on, when that is not the current one."""
         import torch
         if stream is None:
-            return None if token is None else self.fetch_final(dm, token, enqueued=True)
+            return None if token is None else self.fetch_final(dm, token, enqueued=True, nms=nms)
         if token is not None:
-            fin = self.fetch_final(dm, token, enqueued=True, stream=stream)
+            fin = self.fetch_final(dm, token, enqueued=True, stream=stream, nms=nms)
             if fin is not False:
                 return fin
         with torch.cuda.stream(stream):                       # (the rare ways out: launches and copies of their own)
-            return None if token is None else self.fetch_final(dm, token, enqueued=False)
+            return None if token is None else self.fetch_final(dm, token, enqueued=False, nms=nms)
 
     def sorted_detections(self, n=None):
         """Detections ordered by (image, level, r, c) as an int32 [n, 4] tensor of WbDet records."""

@@ -13,7 +13,7 @@ from . import _native as nat
 from . import channels as _channels
 from . import engine as _engine
 from . import model_pb2
-from .boxes import Boxes, concatenate
+from .boxes import Boxes, concatenate, nms_keep_mask, non_max_suppression
 from .channels import channel_pyramid
 from .compare import channel_tensor
 from .training import DTree, _REBINDS
@@ -41,6 +41,37 @@ def symbol_from_name(name: str):
     except KeyError:
         raise ValueError(f"unknown channel function {name!r} in model file "
                          f"(known: {sorted(_channels.CHANNEL_FUNCS)})") from None
+
+
+def _nms_args(iou_threshold, score_threshold):
+    """(iou_threshold, score_threshold or None) of a detect call, or None for the plain call."""
+    if iou_threshold is None:
+        if score_threshold is not None:
+            raise ValueError("score_threshold is part of non-maximum suppression: give an iou_threshold too "
+                             "(1.0 suppresses nothing)")
+        return None
+    iou_threshold = float(iou_threshold)
+    if not iou_threshold >= 0.0:
+        raise ValueError("iou_threshold must be a number >= 0")
+    if score_threshold is not None:
+        score_threshold = float(np.float32(score_threshold))
+        if score_threshold != score_threshold:
+            raise ValueError("score_threshold is NaN")
+    return iou_threshold, score_threshold
+
+
+def _apply_nms(res, nms, keep=None):
+    """The rows of a detect_raw result that non-maximum suppression keeps (keep: the flags the device left behind the
+    scan; None: the complete result goes through boxes.nms_keep_mask, on the GPU as well)."""
+    if nms is None:
+        return res
+    if keep is None:
+        keep = nms_keep_mask(res["boxes"], res["scores"], nms[0], nms[1])
+    at = np.flatnonzero(keep)
+    for k in ("boxes", "scores", "level", "r", "c", "image"):
+        if k in res:
+            res[k] = res[k][at]
+    return res
 
 
 class Model:
@@ -155,15 +186,20 @@ class Model:
         return d["r"].astype(np.int64), d["c"].astype(np.int64), d["score"].copy(), alive
 
     # ---- whole-image detection (reference model.py:149-179)
-    def detect(self, image) -> Boxes:
+    def detect(self, image, iou_threshold=None, score_threshold=None) -> Boxes:
         """Detect objects in a 2-D image; returns Boxes with a 'scores' field, levels in pyramid
-        order and windows in row-major order within a level, like the reference."""
-        res = self.detect_raw(image, _full=False)
+        order and windows in row-major order within a level, like the reference.
+        iou_threshold: greedy non-maximum suppression of the result (boxes.non_max_suppression has the semantics;
+        score_threshold drops boxes below it first): the kept detections, still in that order.  It runs on the device
+        on the finished detections, enqueued behind the step's graph replay and in front of the call's one wait (the
+        plain step's graph is shared: a new threshold captures nothing); n_loc / n_weak are those of the scan.  None: the
+        plain call.  Scores are never NaN for a model the loader accepts."""
+        res = self.detect_raw(image, _full=False, _nms=_nms_args(iou_threshold, score_threshold))
         out = Boxes(res["boxes"])
         out.set_field("scores", res["scores"])
         return out
 
-    def detect_raw(self, image, _full=True):
+    def detect_raw(self, image, _full=True, _nms=None):
         """detect() with everything the parity tests compare: boxes, scores, (level, r, c),
         alive[level, stage]; updates n_loc / n_weak.  (_full=False: boxes and scores only -- what detect() returns.)"""
         _channels._validate_image(image, allow_tensor=True)
@@ -171,7 +207,7 @@ class Model:
         if spec is None:
             if not isinstance(image, np.ndarray):
                 image = image.cpu().numpy()                 # (a caller's own channel function takes host arrays)
-            return self._detect_raw_levelwise(image)
+            return _apply_nms(self._detect_raw_levelwise(image), _nms)
         m, n, Cc = self.shape
         assert Cc == spec.n_channels, f"Invalid number of channels. Expected {Cc} given {spec.n_channels}."
         H, W = (int(x) for x in image.shape)
@@ -185,8 +221,8 @@ class Model:
         eng.load_images(image)
         # one memset + octaves + channels (straight to this cascade's threshold ranks when it has rank tables) + cascade
         # + boxes and sort keys + the read-back: one hipGraph replay from the second call on
-        fin = eng.detect_run(dm)
-        return self._collect(eng, dm, eng._casc_state(dm), _full, fin)
+        fin = eng.detect_run(dm, _nms)
+        return self._collect(eng, dm, eng._casc_state(dm), _full, fin, _nms)
 
     def _detect_raw_levelwise(self, image):
         """detect_raw for a channel function without a kernel: the reference's own loop (model.py:171-177) -- one level at
@@ -214,18 +250,21 @@ class Model:
         dm = view if view is not None else self.device_cascade()
         return self._collect(eng, dm, eng.run_cascade(dm, ranks=view is not None))
 
-    def _collect(self, eng, dm, stt, full=True, fin=False):
+    def _collect(self, eng, dm, stt, full=True, fin=False, nms=None):
         """Results of the scan `stt` of image 0 of `eng`: the dict detect_raw returns; updates n_loc / n_weak.
-        fin: what eng.detect_run returned for this scan (False: fetch it here)."""
+        fin: what eng.detect_run returned for this scan (False: fetch it here).
+        nms: (iou_threshold, score_threshold or None): only the detections non-maximum suppression keeps -- by the flags
+        the device left with `fin`; the routes without them suppress their complete result (boxes.nms_keep_mask)."""
         m, n, Cc = self.shape
         T = dm.n_stages                                   # (the cascade that was scanned: detect_stream collects late)
         if fin is False:
-            fin = eng.fetch_final(dm, stt)                # ONE host synchronisation: sort keys, boxes, scores, statistics
+            fin = eng.fetch_final(dm, stt, nms=nms)       # ONE host synchronisation: sort keys, boxes, scores, statistics
         if fin is not None:
             # get_boxes and the (level, r, c) keys were formed on the device (wb_det_finish_sorted_launch) and -- up to 4096
             # detections -- put in the reference's order there: the host copies slices out of the read-back buffer.
             # Otherwise it sorts the keys -- unique, so any sort kind gives the reference order -- and gathers
-            keys, boxes_d, scores_d, alive, ordered = fin
+            keys, boxes_d, scores_d, alive, ordered = fin[:5]
+            keep = fin[5] if nms is not None and len(fin) > 5 else None
             alive = alive[0].reshape(eng.plan.n_levels, T)
             if "n_loc" not in stt:
                 stt["n_loc"] = eng.plan.n_loc(m, n)
@@ -238,11 +277,12 @@ class Model:
                 ks = np.sort(keys)
                 at = (ks & np.uint64((1 << 26) - 1)).astype(np.intp)
                 res = dict(boxes=boxes_d[at], scores=scores_d[at], alive=alive, scales=list(eng.plan.scales))
+                keep = keep[at] if keep is not None else None
             if full:
                 res.update(level=(ks >> np.uint64(54)).astype(np.int32),
                            r=((ks >> np.uint64(40)) & np.uint64(0x3fff)).astype(np.int64),
                            c=((ks >> np.uint64(26)) & np.uint64(0x3fff)).astype(np.int64))
-            return res
+            return _apply_nms(res, nms, keep)
         recs, alive = eng.fetch(dm, stt)                  # ONE host synchronisation: packed records + statistics
         alive = alive[0].reshape(eng.plan.n_levels, T)
         n_det = recs.shape[0]
@@ -261,15 +301,15 @@ class Model:
             np.multiply(r.astype(np.float32), inv, out=boxes[:, 1])
             np.multiply((c + n).astype(np.float32), inv, out=boxes[:, 2])
             np.multiply((r + m).astype(np.float32), inv, out=boxes[:, 3])
-            return dict(boxes=boxes, scores=score, level=level.astype(np.int32), r=r, c=c, alive=alive,
-                        scales=list(eng.plan.scales))
+            return _apply_nms(dict(boxes=boxes, scores=score, level=level.astype(np.int32), r=r, c=c, alive=alive,
+                                   scales=list(eng.plan.scales)), nms)
         det = eng.sorted_detections()
         boxes, scores = eng.boxes(det, dm)
         d = det.cpu().numpy().view(nat.DET_DTYPE).reshape(-1)
-        return dict(boxes=boxes.cpu().numpy(), scores=scores.cpu().numpy(), level=d["level"].copy(),
-                    r=d["r"].astype(np.int64), c=d["c"].astype(np.int64), alive=alive, scales=list(eng.plan.scales))
+        return _apply_nms(dict(boxes=boxes.cpu().numpy(), scores=scores.cpu().numpy(), level=d["level"].copy(),
+                               r=d["r"].astype(np.int64), c=d["c"].astype(np.int64), alive=alive, scales=list(eng.plan.scales)), nms)
 
-    def detect_stream(self, images, lanes=3, batch=1):
+    def detect_stream(self, images, lanes=3, batch=1, iou_threshold=None, score_threshold=None):
         """detect() over an iterable of 2-D images, as a generator of Boxes in the iterable's order -- the loop the
         reference's detection script runs (scripts/waldboost-detect.py:64-67), pipelined: `lanes` engines, each on its
         own stream, hold consecutive images, so image i + 1 is uploaded and image i - 1's detections are read back and
@@ -279,14 +319,18 @@ class Model:
         one launch (a shape change or the end of the iterable sends a partly filled batch); ordering and boxes of a
         batch are computed on the device.  Up to lanes * batch - 1 images are taken from the iterable ahead of the one
         whose Boxes are being yielded.
+        iou_threshold, score_threshold: as for detect -- every image's result after non-maximum suppression, which is
+        enqueued on the lane's stream right behind the image's (or the batch's) scan and ordering, in front of the
+        lane's one wait.
         (Measured and left out: the blocking upload on a helper thread -- 0.13 to 0.16 ms per 1080p image against 0.14 to
         0.15 without: what the copy frees, the two threads lose again handing the interpreter lock back and forth.)"""
         import torch
         lanes, K = max(int(lanes), 1), max(int(batch), 1)
+        nms = _nms_args(iou_threshold, score_threshold)
         shrink, n_per_oct, smooth, spec = _channels.read_opts(self.channel_opts, allow_callable=True)
         if spec is None:                      # (a caller's own channel function runs on the host between the GPU steps)
             for image in images:
-                yield self.detect(image)
+                yield self.detect(image, iou_threshold, score_threshold)
             return
         m, n, Cc = self.shape
         assert Cc == spec.n_channels, f"Invalid number of channels. Expected {Cc} given {spec.n_channels}."
@@ -297,24 +341,24 @@ class Model:
         def finish(item):
             eng, stream, dm, token, count = item
             if K == 1:
-                fin = eng.detect_collect(dm, token, stream)
+                fin = eng.detect_collect(dm, token, stream, nms=nms)
                 if fin is None:                               # (more detections than the one read-back holds: further copies)
                     with torch.cuda.stream(stream):
-                        res = self._collect(eng, dm, eng._casc_state(dm), False, None)
+                        res = self._collect(eng, dm, eng._casc_state(dm), False, None, nms)
                 else:
-                    res = self._collect(eng, dm, eng._casc_state(dm), False, fin)
+                    res = self._collect(eng, dm, eng._casc_state(dm), False, fin, nms)
                 out = Boxes(res["boxes"])
                 out.set_field("scores", res["scores"])
                 return [out]
             with torch.cuda.stream(stream):
-                return self._collect_batch(eng, dm, token[0], count, enqueued=token[1])
+                return self._collect_batch(eng, dm, token[0], count, enqueued=token[1], nms=nms)
 
         def send(f):
             _, eng, stream, dm, count = f
             with torch.cuda.stream(stream):
                 stt = eng.batch_enqueue(dm)
                 # the batch's results split by image, ordered and on their way to the host right behind the scan
-                ordered = _ORDER_BATCH and eng.order_batch_enqueue(dm, stt)
+                ordered = _ORDER_BATCH and eng.order_batch_enqueue(dm, stt, nms)
                 pending.append((eng, stream, dm, (stt, ordered), count))
 
         try:
@@ -346,14 +390,14 @@ class Model:
                     if eng.plan.n_levels == 0:
                         while pending:
                             yield from finish(pending.pop(0))
-                        yield self.detect(image)
+                        yield self.detect(image, iou_threshold, score_threshold)
                         continue
                     fill = [key, eng, stream, dm, 0]
                 _, eng, stream, _, count = fill
                 with torch.cuda.stream(stream):
                     if K == 1:
                         eng.load_images(image)
-                        pending.append((eng, stream, dm, eng.detect_enqueue(dm), 1))
+                        pending.append((eng, stream, dm, eng.detect_enqueue(dm, nms), 1))
                         fill = None
                     else:
                         eng.load_slot(count, image)
@@ -378,7 +422,7 @@ class Model:
             if fill is not None:
                 fill[2].synchronize()
 
-    def _collect_batch(self, eng, dm, stt, count, enqueued=False):
+    def _collect_batch(self, eng, dm, stt, count, enqueued=False, nms=None):
         """Boxes of images [0, count) of the batch `eng` has just scanned (detect_stream; the slots behind `count` hold
         earlier images, whose results are dropped).  Split by image, ordered and finished on the device
         (wb_det_order_batch_launch) with one read-back; an image with more than 4096 detections sends the batch the
@@ -388,13 +432,17 @@ class Model:
         # split by image, ordered and finished on the device (wb_det_order_batch_launch: up to 4096 detections per
         # image): per image a copy of its slices of the one read-back
         # (enqueued: detect_stream has put the launch and the copies behind the scan already -- only the wait is left)
-        res = eng.fetch_ordered_batch(dm, stt, enqueued) if _ORDER_BATCH else None   # ONE host synchronisation (overflow: grows and scans again)
+        res = eng.fetch_ordered_batch(dm, stt, enqueued, nms) if _ORDER_BATCH else None   # ONE host synchronisation (overflow: grows and scans again)
         if res is not None:
             per_image, alive = res
             self.n_loc += count * eng.plan.n_loc(m, n)
             self.n_weak += int(alive[:count].sum())
             out = []
-            for keys, boxes, scores in per_image[:count]:
+            for item in per_image[:count]:
+                boxes, scores = item[1], item[2]
+                if nms is not None:                            # (the device's keep flags; None: suppressed now)
+                    kept = _apply_nms(dict(boxes=boxes, scores=scores), nms, item[3])
+                    boxes, scores = kept["boxes"], kept["scores"]
                 bx = Boxes(boxes.copy())
                 bx.set_field("scores", scores.copy())
                 out.append(bx)
@@ -424,14 +472,16 @@ class Model:
         for b in range(count):
             bx = Boxes(boxes[cuts[b]:cuts[b + 1]])
             bx.set_field("scores", scores[cuts[b]:cuts[b + 1]])
-            out.append(bx)
+            out.append(bx if nms is None else non_max_suppression(bx, nms[0], nms[1]))
         return out
 
-    def detect_batch(self, images):
+    def detect_batch(self, images, iou_threshold=None, score_threshold=None):
         """detect() on a batch: `images` is [B,H,W] (ndarray or device tensor) of one shape and dtype;
         the whole batch goes through each kernel in one launch.  Returns a list of B Boxes (same
-        content and order as B calls of detect) and updates n_loc / n_weak."""
-        res = self.detect_batch_raw(images)
+        content and order as B calls of detect) and updates n_loc / n_weak.
+        iou_threshold, score_threshold: as for detect, per image (one wb_nms_finish_launch for the whole batch behind the
+        ordering launch, in front of the one wait)."""
+        res = self.detect_batch_raw(images, _nms=_nms_args(iou_threshold, score_threshold))
         out = []
         for b in range(res["batch"]):
             sel = res["image"] == b
@@ -440,7 +490,7 @@ class Model:
             out.append(bx)
         return out
 
-    def detect_batch_raw(self, images):
+    def detect_batch_raw(self, images, _nms=None):
         """All detections of a batch as flat arrays (image, level, r, c, boxes, scores, alive[B,L,T])."""
         if getattr(images, "ndim", None) != 3 and (not hasattr(images, "dim") or images.dim() != 3):
             raise ValueError("images must have 3 dimensions [B,H,W]")
@@ -461,9 +511,17 @@ class Model:
         stt = eng.run(dm)
         # split by image, ordered and finished on the device, one read-back (up to 4096 detections per image and 256
         # images: the read-back block is fixed-size); otherwise a device sort of all records and wb_boxes_launch
-        res = eng.fetch_ordered_batch(dm, stt) if (_ORDER_BATCH and B <= 256) else None
+        res = eng.fetch_ordered_batch(dm, stt, nms=_nms) if (_ORDER_BATCH and B <= 256) else None
         if res is not None:
             per_image, alive = res
+            if _nms is not None:
+                done = []
+                for keys, boxes, scores, keep in per_image:
+                    if keep is None:                           # (the device left no flags for this image: suppressed now)
+                        keep = nms_keep_mask(boxes, scores, _nms[0], _nms[1])
+                    at = np.flatnonzero(keep)
+                    done.append((keys[at], boxes[at], scores[at]))
+                per_image = done
             alive = alive.reshape(B, L, T)
             self.n_loc += B * eng.plan.n_loc(m, n)
             self.n_weak += int(alive.sum())
@@ -480,9 +538,14 @@ class Model:
         self.n_loc += B * eng.plan.n_loc(m, n)
         self.n_weak += int(alive.sum())
         d = det.cpu().numpy().view(nat.DET_DTYPE).reshape(-1)
-        return dict(batch=B, image=d["image"].copy(), level=d["level"].copy(), r=d["r"].astype(np.int64),
-                    c=d["c"].astype(np.int64), boxes=boxes.cpu().numpy(), scores=scores.cpu().numpy(), alive=alive,
-                    scales=list(eng.plan.scales))
+        res = dict(batch=B, image=d["image"].copy(), level=d["level"].copy(), r=d["r"].astype(np.int64),
+                   c=d["c"].astype(np.int64), boxes=boxes.cpu().numpy(), scores=scores.cpu().numpy(), alive=alive,
+                   scales=list(eng.plan.scales))
+        if _nms is not None:                                   # (image by image: the records are ordered by image)
+            cuts = np.searchsorted(res["image"], np.arange(B + 1))
+            keep = [nms_keep_mask(res["boxes"][a:b], res["scores"][a:b], _nms[0], _nms[1]) for a, b in zip(cuts[:-1], cuts[1:])]
+            res = _apply_nms(res, _nms, np.concatenate(keep))
+        return res
 
     def predict(self, X):
         """The cascade on samples X[N, m, n, C] -> (H, mask): H[i] is the response accumulated in stage
