@@ -416,14 +416,23 @@ template <typename RT, int RW> struct RPitch { static constexpr int value = size
 #endif
 __host__ __device__ constexpr int wb_strip_rows(int rh, int nw) { return WB_CHAN_RB * ((rh + nw * WB_CHAN_RB - 1) / (nw * WB_CHAN_RB)); }
 
-template <typename T, typename G, bool REFLECT = false, typename RT = float>
+template <typename T, typename G, bool REFLECT = false, typename RT = float, bool RADD = false>
 __device__ __forceinline__ void resample_tile(const ChanArgs &a, const WbLevel &L, const T *src, const double mn,
                                               const double mx, const int ry0, const int rx0, const int rh, RT *R,
                                               unsigned char *uni, float4 *rowtab, const int tid) {
     static_assert(sizeof(RT) == 4 || sizeof(T) == 1, "byte R holds uint8 pixels");
     constexpr int RP = RPitch<RT, G::RW>::value;             // R's row pitch in elements
+    // (RADD -- byte R at shrink 2, round 7: v is an integer of [0, 255] on every path -- the fast path's floor lies in the octave's
+    // range, the redo is clipped and truncated, the identity path copies a byte -- so v + 2^23 is exact and the low byte
+    // of its bits IS that integer: one add of the fast issue class instead of a conversion of the slow one, the same byte
+    // store.  Opaque to the SLP vectoriser like the arithmetic around it.)
     auto rput = [&](int idx, float v) {
-        if constexpr (sizeof(RT) == 1) R[idx] = (RT)(int)v; else R[idx] = v;
+        if constexpr (sizeof(RT) == 1 && RADD)
+            R[idx] = (RT)__float_as_uint(scalar_only(v + 8388608.0f));
+        else if constexpr (sizeof(RT) == 1)
+            R[idx] = (RT)(int)v;
+        else
+            R[idx] = v;
     };
     // rh <= RH: the tile rows that are needed (a tile on the bottom edge of its level uses fewer): wave-uniform, the
     // strips below are cut from it
@@ -847,17 +856,23 @@ __global__ __launch_bounds__(NT, sizeof(T) == 8 ? 1
     const int vrows = L.u - u0 < TU ? L.u - u0 : TU;
     const int su_need = vrows + 2 * HS, rh_need = S * su_need + 2;
     WB_CSTAMP(0);
-    resample_tile<T, G, false, RT>(a, L, src, mn, mx, ry0, rx0, rh_need, R, uni, rowtab, tid);
+    resample_tile<T, G, false, RT, RBYTES && S == 2>(a, L, src, mn, mx, ry0, rx0, rh_need, R, uni, rowtab, tid);
     __syncthreads();
     WB_CSTAMP(4);
     if (a.dbg & 1) return;
 
     // ---- step 2: gradients -> 4 oriented channels -> shrink, one shrunk pixel per call
     //      Rp: the pixel's (S + 2) x (S + 2) patch of R, Shp: where its shrunk value goes
-    auto shrunk_pixel = [&](const int ro, const int so) {     // (offsets, not pointers: R's alignment stays visible -- 8-byte reads)
+    //      grads: where the gradients come from -- OwnPatch{}: the pixel reads its patch (at ro) and forms them itself; else a
+    //      callable that hands them over (the row runs below, which carry half of every patch from the pixel above);
+    //      everything behind the gradients is the same code for both
+    struct OwnPatch {};
+    auto shrunk_pixel = [&](const int ro, const int so, auto grads) {     // (offsets, not pointers: R's alignment stays visible -- 8-byte reads)
         float ch[S][S][4], gxs[S][S], gys[S][S];
         constexpr bool TWO_PASS = FAST && S > 1;          // ordinary values first, residues only where they can show
-        if constexpr (RBYTES && S == 2) {
+        if constexpr (!std::is_same<decltype(grads), OwnPatch>::value) {
+            grads(gxs, gys);
+        } else if constexpr (RBYTES && S == 2) {
             // The 4 x 4 patch starts at the even column 2j of a dword-padded row: a patch row is two aligned 16-bit reads
             // (volatile: never merged into one dword read at a 2-byte boundary, which LDS serves slowly) and four byte
             // conversions.  The gradients are then formed differences first -- the centre row / column of a [-1,0,1] pass
@@ -991,30 +1006,98 @@ __global__ __launch_bounds__(NT, sizeof(T) == 8 ? 1
     };
     // Tiles whose shrunk width is a wave or a little more (the 16 x 64 tiles: 66 columns): a wave owns whole rows, lane =
     // column, so a pixel's LDS addresses are the previous round's plus a constant (no division by the width, no 64-bit
-    // multiply-add per pixel: round 4); the few columns beyond the 64th go to the last wave, which owns the fewest rows.
+    // multiply-add per pixel: round 4); the few columns beyond the 64th go to the last wave, which owns the fewest rows
+    // (one stand-alone pixel each).
     constexpr bool ROWMAP = SV >= 64 && SV - 64 <= 8 && NT % 64 == 0;
     if constexpr (ROWMAP) {
         constexpr int NWV = NT / 64, XC = SV - 64;
         const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-        int ro = S * (wave * RP + lane), so = wave * SV + lane;
+        if constexpr (RBYTES && S == 2) {
+            // Round 7: a wave owns CONTIGUOUS rows -- su_need rows over the waves as evenly as they go, the longer runs
+            // first (18 rows: 5, 5, 4, 4; the last wave, with the extra columns below, still owns the fewest) --, because
+            // the patch of the pixel below is this pixel's patch moved down two rows: of its four patch rows two are
+            // already in registers.  What is carried is not the converted bytes but what the gradients take from them,
+            // per patch row r: the column differences ex[r][x] = pt[r][x] - pt[r][x + 2] (gx = their vertical [1,2,1]
+            // pass, as in the stand-alone pixel) and the horizontal [1,2,1] sums hr[r][x] = pt[r][x] + 2 pt[r][x + 1] +
+            // pt[r][x + 2], of which gy is the row difference hr[y][x] - hr[y + 2][x]: the [1,2,1] pass first and the
+            // [-1,0,1] pass second, where the stand-alone pixel has them the other way round.  On pixels 0..255 every
+            // partial sum of either order is an integer of magnitude <= 1020, exact in fp32, so both give the same bits
+            // (a zero is +0 both ways: x - x and an exact fma sum of 0 are +0 under round-to-nearest).
+            // A row after a wave's first then reads two patch rows instead of four (4 LDS halfwords, 8 conversions) and
+            // needs 24 instead of 32 plain operations.  Unrolled completely, with a wave-uniform exit: nothing is carried
+            // around a back edge (round 4), the carried values are renamed, not moved.  A bottom-edge tile (su_need from
+            // 3) may leave a wave without a row.
+            constexpr int MAXR = (G::SU + NWV - 1) / NWV;
+            const int q = su_need / NWV, rem = su_need % NWV;
+            const int n_w = q + (wave < rem ? 1 : 0), i_w = wave * q + (wave < rem ? wave : rem);
+            const int ro = S * (i_w * RP + lane), so = i_w * SV + lane;
+            // (the conversions opaque: left visible, the compiler does the differences and sums on the bytes as integers and
+            // converts each of them -- six conversions per patch row instead of four)
+            auto patch_row = [&](const uint32_t lo, const uint32_t hi, float (&e)[S], float (&h)[S]) {
+                const float p0 = scalar_only((float)(lo & 0xffu)), p1 = scalar_only((float)(lo >> 8));
+                const float p2 = scalar_only((float)(hi & 0xffu)), p3 = scalar_only((float)(hi >> 8));
+                e[0] = scalar_only(p0 - p2);
+                e[1] = scalar_only(p1 - p3);
+                h[0] = scalar_only(Src<T>::hpass(p0, p1, p2));
+                h[1] = scalar_only(Src<T>::hpass(p1, p2, p3));
+            };
+            float ex[P][S], hr[P][S];
+#pragma unroll
+            for (int r = 0; r < MAXR; ++r) {
+                if (r >= n_w) break;                                                  // wave-uniform
+                const int o = ro + r * S * RP;
+                // the patch rows that are new to this pixel (all four for a wave's first): every read before the arithmetic
+                const int y0 = r == 0 ? 0 : S;
+                uint32_t lo[P], hi[P];
+#pragma unroll
+                for (int y = 0; y < P; ++y) {
+                    if (y < y0) continue;
+                    lo[y] = lds_u16_vol(Rraw, o + y * RP);
+                    hi[y] = lds_u16_vol(Rraw, o + y * RP + 2);
+                }
+#pragma unroll
+                for (int y = 0; y < P; ++y) {
+                    if (y >= y0) {
+                        patch_row(lo[y], hi[y], ex[y], hr[y]);
+                    } else {
+#pragma unroll
+                        for (int x = 0; x < S; ++x) {
+                            ex[y][x] = ex[y + S][x];
+                            hr[y][x] = hr[y + S][x];
+                        }
+                    }
+                }
+                shrunk_pixel(o, so + r * SV, [&](float (&gxs)[S][S], float (&gys)[S][S]) {
+#pragma unroll
+                    for (int y = 0; y < S; ++y)
+#pragma unroll
+                        for (int x = 0; x < S; ++x) {
+                            gxs[y][x] = scalar_only(Src<T>::hpass(ex[y][x], ex[y + 1][x], ex[y + 2][x]));
+                            gys[y][x] = scalar_only(hr[y][x] - hr[y + 2][x]);
+                        }
+                });
+            }
+        } else {
+            int ro = S * (wave * RP + lane), so = wave * SV + lane;
 #pragma nounroll
-        for (int i = wave; i < su_need; i += NWV) {                               // wave-uniform trip count
-            shrunk_pixel(ro, so);
-            ro += NWV * S * RP;
-            so += NWV * SV;
+            for (int i = wave; i < su_need; i += NWV) {                           // wave-uniform trip count
+                shrunk_pixel(ro, so, OwnPatch{});
+                ro += NWV * S * RP;
+                so += NWV * SV;
+            }
         }
         if constexpr (XC > 0) {
             if (wave == NWV - 1) {
                 for (int p = lane; p < su_need * XC; p += 64) {
                     const int i = p / XC, j = 64 + p - i * XC;
-                    shrunk_pixel(S * (i * RP + j), i * SV + j);
+                    shrunk_pixel(S * (i * RP + j), i * SV + j, OwnPatch{});
                 }
             }
         }
     } else {
         for (int p = tid; p < su_need * SV; p += NT) {
             const int i = p / SV, j = p - i * SV;
-            shrunk_pixel(S * (i * RP + j), p);
+            shrunk_pixel(S * (i * RP + j), p, OwnPatch{});
         }
     }
     // rank tables of the model (12 KiB, L2-resident): requested before the barrier, parked in R -- dead once every
