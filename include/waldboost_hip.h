@@ -41,6 +41,9 @@
  *   reference waldboost/testing.py:46 (bbx.non_max_suppression on a detector's result) and
  *        scripts/waldboost-detect.py:36 (detect(..., iou_threshold=0.2, score_threshold=0, separate=False))
  *        -> wb_nms_launch, wb_nms_ordered_launch; wb_nms_finish_launch (on the buffer wb_det_finish_sorted_launch / wb_det_order_batch_launch left)
+ *   reference waldboost/fpga/training.py:15-57 (H, _fit_threshold, _find_split: the split search of fpga.DTree.fit) and
+ *        :133-138 (the samples of a split node move to its children)
+ *        -> wb_fit_level_launch, wb_fit_route_launch
  */
 #ifndef WALDBOOST_HIP_H
 #define WALDBOOST_HIP_H
@@ -496,6 +499,44 @@ int wb_nms_finish_scratch_bytes(uint32_t out_capacity, int n_images, size_t *byt
 int wb_nms_finish_launch(void *stream, const void *fin, uint32_t out_capacity, int n_images, double iou_threshold,
                          int use_score_threshold, float score_threshold, void *scratch, size_t scratch_bytes,
                          void *result);
+
+/* Split search of the FPGA flavour's tree learner (reference fpga/training.py:15-57), one tree level per call.
+ * New symbols of ABI 8 (the version number did not change: nothing that existed did).
+ *   xt       dev uint8 [n_features][n_samples]: the samples, FEATURE-major
+ *   q        dev uint64 [n_samples], 8-byte aligned: the split weights as integers, rint(w' * 2^62), w' the weights with
+ *            each class divided by twice its sum (fpga/training.py:105-107) -- every sum is an integer add, so results do
+ *            not depend on the order of samples or on the run; a sum converts back as double(sum) * 2^-62
+ *   cls      dev uint8 [n_samples]: 0 / 1
+ *   node     dev int32 [n_samples]: the tree node (breadth-first id) each sample sits in
+ *   level_base, n_level, slot: the level's nodes have ids level_base .. level_base + n_level - 1 (n_level <= 8); slot is a
+ *            HOST array int8 [n_level]: the open slot 0 .. n_open - 1 of each, -1 for a leaf.  Samples of other nodes and
+ *            of leaves take no part.  An open node must hold at least one sample.
+ *   allowed  dev int32 [n_allowed]: the ordered feature list A (every entry in 0 .. n_features - 1)
+ *   scratch  dev, 16-byte aligned, wb_fit_scratch_bytes(n_allowed, n_open) bytes: one (float64 metric, int32 t) record per
+ *            (open node, entry of A) and two float64 totals per open node
+ *   splits   dev WbFitSplit [n_open], 8-byte aligned: per open slot the first entry of A with the largest metric and its
+ *            smallest best threshold t (candidates xmin .. xmax + 1 over the node's samples: 256 is a legal value), the
+ *            metric, and the node's class totals T0, T1.  A NaN metric is the largest (np.argmax): a node without weight
+ *            in one class answers (A[0], its xmin).
+ * Two launches (histograms and per-feature argmax: one workgroup per entry of A, (4 + 1) KiB of LDS per open node; then
+ * the argmax over A), no host synchronisation.
+ * wb_fit_route_launch applies the splits (fpga/training.py:133-138): a sample of open slot s moves to node
+ * child_base + 2 * s when x[feature] <= t, to child_base + 2 * s + 1 otherwise (breadth-first numbering: the children of
+ * a level's open nodes follow each other in slot order).  node is updated in place. */
+#define WB_FIT_MAX_OPEN 8
+typedef struct {
+    int32_t feature;    /* flat index into the (m, n, C) sample */
+    int32_t threshold;  /* t: the node routes with x <= t (the metric rated x < t -- the reference's own difference) */
+    double metric, t0, t1;
+} WbFitSplit;           /* 32 bytes */
+int wb_fit_scratch_bytes(int n_allowed, int n_open, size_t *bytes);
+int wb_fit_level_launch(void *stream, const uint8_t *xt, int64_t n_samples, int64_t n_features, const uint64_t *q,
+                        const uint8_t *cls, const int32_t *node, int level_base, int n_level, const int8_t *slot,
+                        int n_open, const int32_t *allowed, int n_allowed, void *scratch, size_t scratch_bytes,
+                        WbFitSplit *splits);
+int wb_fit_route_launch(void *stream, const uint8_t *xt, int64_t n_samples, int64_t n_features, int32_t *node,
+                        int level_base, int n_level, const int8_t *slot, int n_open, const WbFitSplit *splits,
+                        int child_base);
 
 /* Device self-test: the uint8 fast path of the orientation projection (fp32 arithmetic that is
  * proven equal to the reference's fp64 formula for integer gradients) is compared with the fp64

@@ -33,6 +33,9 @@ PATCH_DTYPE = np.dtype([("r_lo", "<i4"), ("c_lo", "<i4"), ("rows", "<u2"), ("byt
 DET_DTYPE = np.dtype([("image", "<i4"), ("level", "<i4"), ("r", "<u2"), ("c", "<u2"), ("score", "<f4")], align=True)
 assert LEVEL_DTYPE.itemsize == 64 and TILE_DTYPE.itemsize == 8 and DET_DTYPE.itemsize == 16 and TAP_DTYPE.itemsize == 24
 assert PATCH_DTYPE.itemsize == 16
+FIT_SPLIT_DTYPE = np.dtype([("feature", "<i4"), ("threshold", "<i4"), ("metric", "<f8"), ("t0", "<f8"), ("t1", "<f8")], align=True)   # WbFitSplit
+assert FIT_SPLIT_DTYPE.itemsize == 32
+WB_FIT_MAX_OPEN = 8
 
 
 class WbModelInfo(C.Structure):
@@ -95,6 +98,10 @@ SYMBOLS = {
     "wb_nms_ordered_launch": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_double, C.c_int, C.c_float, _P, C.c_size_t, _P, _P]),
     "wb_nms_finish_scratch_bytes": (C.c_int, [C.c_uint32, C.c_int, C.POINTER(C.c_size_t)]),
     "wb_nms_finish_launch": (C.c_int, [_P, _P, C.c_uint32, C.c_int, C.c_double, C.c_int, C.c_float, _P, C.c_size_t, _P]),
+    "wb_fit_scratch_bytes": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "wb_fit_level_launch": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, _P, C.c_int, C.c_int, _P, C.c_int, _P, C.c_int, _P,
+                                      C.c_size_t, _P]),
+    "wb_fit_route_launch": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, C.c_int, C.c_int, _P, C.c_int, _P, C.c_int]),
 }
 
 _lib = None

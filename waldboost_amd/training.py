@@ -1,14 +1,36 @@
-"""``DTree`` -- the weak classifier of the cascade (reference training.py:23-96).
+"""``DTree`` -- the weak classifier of the cascade (reference training.py:23-96) -- and the stage
+learner around it (reference training.py:14-20, 99-253).
 
 Same constructor, attributes, proto I/O and ``predict_on_image``/``apply``/``predict``
 signatures as the reference so that ``from waldboost_amd.training import DTree`` is a drop-in;
 the evaluation runs in a HIP kernel (csrc/wb_cascade.hip: tree_eval_kernel).  ``DTree.fit``
-(sklearn training, reference training.py:33-50) is out of scope of this build.
+(sklearn training, reference training.py:33-50) is out of scope of this build: the weak learner
+that trains here is ``waldboost_amd.fpga.DTree`` (csrc/wb_fit.hip).
+
+``Learner``, ``fit_rejection_threshold``, ``BasicRejectionSchedule``, ``weights``, ``loss`` and
+``as_features`` are the reference's host arithmetic on a pool's scores; ``Learner.fit_stage`` calls
+``wh.fit`` and ``weak.predict``, which run on the GPU.
 """
+import logging
+import pickle
+
 import numpy as np
 
 from . import _native as nat
 from .compare import channel_tensor
+
+logger = logging.getLogger(__name__)
+
+
+def weights(H):
+    """Sample weights of the scores H (reference training.py:14-15)."""
+    return np.exp(H) / H.size / 2
+
+
+def as_features(X):
+    """(N, m, n, C) samples as (N, m*n*C) feature rows (reference training.py:18-20)."""
+    n, *shape = X.shape
+    return X.reshape((n, int(np.prod(shape))))
 
 
 _ARRAYS = ("threshold", "prediction", "feature", "left", "right")
@@ -78,8 +100,8 @@ class DTree:
 
     @staticmethod
     def fit(*args, **kwargs):
-        raise NotImplementedError("DTree.fit (training) is outside the MI355X detection hot path; "
-                                  "train with the reference and load the .pb here")
+        raise NotImplementedError("training.DTree.fit (the sklearn learner) has no kernel in this build; "
+                                  "waldboost_amd.fpga.DTree.fit trains on the GPU")
 
     # ---- wire format (reference training.py:51-72, model.proto DTree)
     @staticmethod
@@ -160,3 +182,133 @@ class DTree:
         def d(n):
             return 0 if self.left[n] < 0 else 1 + max(d(int(self.left[n])), d(int(self.right[n])))
         return d(0)
+
+
+def loss(H0, H1):
+    """Exponential loss of the two score sets (reference training.py:99-102)."""
+    W0 = weights(H0)
+    W1 = weights(-H1)
+    return W0.mean() + W1.mean()
+
+
+class Learner:
+    """Training algorithm (reference training.py:105-188): fits one weak classifier and one rejection threshold per
+    stage and keeps the per-stage pass rates and losses.  The default ``wh`` is ``training.DTree``, whose ``fit`` is not
+    part of this build; ``fpga.train`` passes ``fpga.DTree``."""
+
+    def __init__(self, alpha=0.1, wh=DTree, **wh_args):
+        self.alpha = alpha
+        self.wh = wh
+        self.wh_args = wh_args
+        self.p0 = []
+        self.p1 = []
+        self.losses = []
+
+    @staticmethod
+    def from_dict(d):
+        L = Learner(alpha=d["alpha"], wh=d["wh"], **d["wh_args"])
+        L.p0 = d["p0"]
+        L.p1 = d["p1"]
+        L.losses = d["losses"]
+        if len(L.p0) != len(L.losses) or len(L.p1) != len(L.losses):
+            raise ValueError("Wrong values for p0, p1 or loss")
+        return L
+
+    def save(self, filename):
+        with open(filename, "wb") as f:
+            pickle.dump(self.__dict__, f)
+
+    @staticmethod
+    def load(filename):
+        with open(filename, "rb") as f:
+            return Learner.from_dict(pickle.load(f))
+
+    @property
+    def false_positive_rate(self):
+        return np.prod(self.p0)
+
+    @property
+    def true_positive_rate(self):
+        return np.prod(self.p1)
+
+    @property
+    def loss(self):
+        return self.losses[-1] if self.losses else None
+
+    def __len__(self):
+        return len(self.losses)
+
+    def __bool__(self):
+        return True
+
+    def get_stats(self):
+        return {
+            "false_positive_rate": np.cumprod(self.p0),
+            "true_positive_rate": np.cumprod(self.p1),
+            "loss": np.array(self.losses),
+        }
+
+    def fit_stage(self, model, X0, H0, X1, H1, theta=None, **wh_args):
+        """Append a new stage to the model: returns (loss, false positive rate, true positive rate)."""
+        W0 = weights(H0)
+        W1 = weights(-H1)
+        weak = self.wh.fit(X0, W0, X1, W1, **{**self.wh_args, **wh_args})
+        H0 = H0 + weak.predict(X0)
+        H1 = H1 + weak.predict(X1)
+        if not theta:       # (None -- and 0.0, as in the reference -- means: estimate it)
+            theta = fit_rejection_threshold(H0, self.false_positive_rate, H1, self.true_positive_rate, self.alpha)
+        p0 = (H0 >= theta).sum() / H0.size
+        p1 = (H1 >= theta).sum() / H1.size
+        self.p0.append(p0)
+        self.p1.append(p1)
+        self.losses.append(loss(H0, H1))
+        model.append(weak, theta)
+        return self.loss, self.false_positive_rate, self.true_positive_rate
+
+
+def fit_rejection_threshold(H0, P0, H1, P1, alpha):
+    """Rejection threshold by the SPRT (reference training.py:191-220): the largest candidate t (a response that
+    occurs, the smallest excepted) whose likelihood ratio R(t) exceeds 1/alpha.  The reference's loop over candidates
+    is two ``searchsorted`` calls here: the counts `(H < t).sum()` are integers, so R is the same float for float."""
+    max0 = np.max(H0)
+    min1 = np.min(H1)
+    if max0 < min1:
+        logger.log(15, f"H0 and H1 are non-overlapping H0 < {max0}, H1 > {min1}")
+        return min1
+    ts = np.unique(np.concatenate([H0.flatten(), H1.flatten()]))
+    if ts.size < 3:
+        logger.log(15, f"Not enough unique responses to estimate theta (forcing to {-np.inf})")
+        return -np.inf
+    ts = ts[1:]
+    logger.log(15, f"Testing {ts.size} thresholds on interval <{min(ts):.2f},{max(ts):.2f}>")
+    p0 = np.searchsorted(np.sort(H0.flatten()), ts, side="left") / H0.size
+    p1 = np.searchsorted(np.sort(H1.flatten()), ts, side="left") / H1.size
+    R = ((P0 * p0 + (1 - P0) + 1e-6) / (P1 * p1 + (1 - P1) + 1e-6)).astype(ts.dtype)   # (the reference fills an empty_like(ts))
+    A = 1 / alpha
+    logger.log(15, f"R: <{min(R):.2f},{max(R):.2f}>; need R > {A}")
+    idx = np.nonzero(R > A)[0]
+    if idx.size == 0:
+        logger.log(15, "No suitable theta found")
+        theta = -np.inf
+    else:
+        theta = ts[np.max(idx)]
+    logger.log(15, f"theta = {theta:.4f}")
+    return theta
+
+
+class BasicRejectionSchedule:
+    """Which stages learn a rejection threshold (reference training.py:223-253): called with (stage, p0) it returns
+    -inf outside ``rejection_interval`` = (first, last) stage or once the false positive rate p0 has fallen below
+    ``target_p0``, and None (estimate theta from the data) otherwise."""
+
+    def __init__(self, rejection_interval=(0, None), target_p0=1e-5):
+        if rejection_interval is None:
+            rejection_interval = (None, None)
+        self.s0 = rejection_interval[0] or 0
+        self.s1 = rejection_interval[1] or np.inf
+        self.target_p0 = target_p0
+
+    def __call__(self, stage, p0):
+        if stage < self.s0 or stage > self.s1 or p0 < self.target_p0:
+            return -np.inf
+        return None
