@@ -174,6 +174,41 @@ def test_stream_in_batches_grows_an_overflowing_detection_buffer():
         assert same_boxes(g, r), f"image {i}"
 
 
+def dense_image(H, W, period, sigma, seed):
+    """A noise patch repeated with an even period: what a window sees at the first pyramid levels repeats with it, so a
+    patch that fires at all fires all over the image -- many detections in every tile of those levels.  (The scattered
+    detections of synth_image never put more than 16 into one shard of the detection buffer at this size: the oracle's
+    detections of 600 seeds were counted tile by tile.)"""
+    patch = np.clip(127 + np.random.default_rng(seed).normal(0, sigma, (period, period)), 0, 255).astype(np.uint8)
+    return np.ascontiguousarray(np.tile(patch, (H // period + 1, W // period + 1))[:H, :W])
+
+
+def test_stream_grows_an_overflowing_buffer_whose_detections_exceed_one_read_back(monkeypatch):
+    """Both at once, in one call: a shard of the lane's detection buffer overflows (the scan is repeated with a larger
+    buffer) AND the repeated scan finds more detections than the read-back block holds (further copies; a batch goes
+    the older way) -- the regrow path is shared by the routes that meet here."""
+    from waldboost_amd import _native as nat, engine as E
+    monkeypatch.setattr(E.PyramidEngine, "_FETCH_ROWS", 64)
+    monkeypatch.setattr(E.PyramidEngine, "_ORDER_ROWS", 64)
+    M = load()
+    ims = [dense_image(200, 264, *a) for a in ((16, 17, 4), (16, 17, 7), (16, 20, 1), (24, 20, 11), (24, 25, 11), (24, 25, 0))]
+    ref = [oracle_detect(M, im) for im in ims]
+    assert min(r["scores"].size for r in ref) > 64
+    for batch in (1, 2):
+        list(M.detect_stream(ims, lanes=3, batch=batch))    # lanes built, graphs captured
+        engines = [eng for group in M._lanes.values() for eng, _ in group if eng.batch == batch]
+        assert len(engines) == 3
+        for eng in engines:
+            eng.det_capacity = 16 * nat.WB_DET_SHARDS       # every call of a lane now overflows a shard until it has grown
+            eng._alloc_det()
+        got = list(M.detect_stream(ims, lanes=3, batch=batch))
+        assert all(eng.detb.cap > 16 for eng in engines), "no shard overflowed: the images are not dense enough"
+        assert len(got) == len(ref)
+        for i, (g, r) in enumerate(zip(got, ref)):
+            assert np.array_equal(g.get().view(np.uint32), r["boxes"].view(np.uint32)), f"batch {batch}, image {i}"
+            assert np.array_equal(g.get_field("scores").view(np.uint32), r["scores"].view(np.uint32)), f"batch {batch}, image {i}"
+
+
 def test_detect_on_images_through_the_stream():
     """testing.detect_on_images (reference testing.py:127-132) with lanes / batch: the same tuples as its plain loop."""
     from waldboost_amd.testing import detect_on_images

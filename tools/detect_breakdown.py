@@ -7,6 +7,7 @@ sys.path.insert(0, ROOT)
 import torch
 import waldboost_amd as wb
 from waldboost_amd import engine as E, _native as nat, channels as CH
+from waldboost_amd.readback import key_positions
 from waldboost_amd.synth import synth_image
 M = wb.load(os.path.join(ROOT, "tests/golden/models/cfg2_d2_T128.pb"))
 imgs = [synth_image(1080, 1920, s) for s in range(4)]
@@ -30,13 +31,12 @@ for i in range(N):
     t = lap("validate, opts, cached cascade, cached engine", t)
     eng.load_images(img); t = lap("load_images (H2D from pageable memory: blocks)", t)
     fin = eng.detect_run(dm); t = lap("detect_run: graph replay (memset .. copies), wait for the GPU", t)
-    keys, boxes_d, scores_d, alive, ordered = fin
+    keys, ordered = fin.keys, fin.ordered
     if ordered:
-        b, s_ = boxes_d[:keys.size].copy(), scores_d[:keys.size].copy()
+        b, s_ = fin.boxes[:keys.size].copy(), fin.scores[:keys.size].copy()
     else:
-        ks = np.sort(keys)
-        at = (ks & np.uint64((1 << 26) - 1)).astype(np.intp)
-        b, s_ = boxes_d[at], scores_d[at]
+        at = key_positions(np.sort(keys))
+        b, s_ = fin.boxes[at], fin.scores[at]
     out = wb.Boxes(b); out.set_field("scores", s_)
     t = lap("host: boxes and scores out of the read-back buffer (ordered on the device), Boxes" if ordered else "host: sort keys, gather boxes and scores, Boxes", t)
 print("host timeline of one call (no added synchronisation):")

@@ -19,6 +19,7 @@ import numpy as np
 from . import _native as nat
 from .chanfunc import SPECS
 from .plan import PyramidPlan, N_CHANNELS
+from .readback import FinishBlock, Finished, ImageResult, Packed, key_fits
 
 _TORCH_DT = {}
 _log = logging.getLogger("waldboost_amd")
@@ -333,15 +334,6 @@ class DetBuffer:
     def max_count(self):
         return int(self.counts.max().item())
 
-    def valid_records(self, counts):
-        """The valid records of all shards (shard order) as one int32 [n, 4] tensor, given the host copy of
-        the shard counters: plain slices, no mask."""
-        import torch
-        parts = [self.recs[s * self.cap: s * self.cap + int(c)] for s, c in enumerate(counts) if c]
-        if not parts:
-            return self.recs[:0]
-        return parts[0] if len(parts) == 1 else torch.cat(parts)
-
     def compact(self):
         """All valid records as one int32 [n, 4] tensor (shard order)."""
         import torch
@@ -446,10 +438,11 @@ class PyramidEngine:
         self._level_tiles = None
         self.epoch = 0
         self.det_capacity = int(det_capacity)
-        self._h_packed = self._h_alive = self._fetch_ev = None
+        self._h_packed = self._h_alive = None
+        self._fetch_ev = torch.cuda.Event()                        # what fetch, fetch_final and detect_multi_run wait on
         self._h2d_ev, self._upload_async = None, False
         self._mm_host = None
-        self._inv_scales_d = self._final_dims = None
+        self._inv_scales_d = self._key_dims = None
         self._order = None            # buffers of fetch_ordered_batch (scratch, out, page-locked copy), on first use
         self._alloc_det()
         if exact_single:
@@ -845,20 +838,14 @@ class PyramidEngine:
             need = self.detb.max_count()
             if need <= self.detb.cap:
                 return int(self.detb.counts.sum().item())
-            self.det_capacity = (int(need * 1.5) + 16) * nat.WB_DET_SHARDS
-            self._alloc_det()
-            self.run_cascade(dm, ranks=self._casc_state(dm).get("ranks", False))
+            self._grow_and_rescan(dm, self._casc_state(dm), need)
 
-    def shard_counts(self, dm):
-        """Host copy of the shard counters after the last scan; re-runs the cascade with a larger buffer if a
-        shard overflowed."""
-        while True:
-            counts = self.detb.counts.cpu().numpy().astype(np.int64)
-            if counts.max(initial=0) <= self.detb.cap:
-                return counts
-            self.det_capacity = (int(counts.max() * 1.5) + 16) * nat.WB_DET_SHARDS
-            self._alloc_det()
-            self.run_cascade(dm, ranks=self._casc_state(dm).get("ranks", False))
+    def _grow_and_rescan(self, dm, stt, worst):
+        """A shard of the detection buffer overflowed in the scan `stt` (its fullest holds `worst` records): a larger
+        buffer, and the same scan again on the resident channels.  Returns the scan state."""
+        self.det_capacity = (int(worst * 1.5) + 16) * nat.WB_DET_SHARDS
+        self._alloc_det()
+        return self.run_cascade(dm, ranks=stt.get("ranks", False))
 
     def pack(self, out=None):
         """Pack the valid records of all shards behind a 4-word header (wb_det_pack_launch) into self.packed --
@@ -866,69 +853,68 @@ class PyramidEngine:
         tensor (16-byte aligned, e.g. a rank's slot of a collective's send buffer) to pack into instead -- the header
         then says how many of the valid records fitted its `rows`."""
         import torch
-        if out is not None:
-            nat.check(self.lib.wb_det_pack_launch(nat.stream_ptr(), nat.ptr(self.detb.recs), nat.ptr(self.detb.counts),
-                                                  self.detb.cap, nat.ptr(out), out.shape[0] - 1), "wb_det_pack_launch")
-            return out
-        if self.packed is None:
-            self.packed = torch.empty((1 + self.detb.NS * self.detb.cap, 4), dtype=torch.int32, device=self.dev)
+        if out is None:
+            if self.packed is None:
+                self.packed = torch.empty((1 + self.detb.NS * self.detb.cap, 4), dtype=torch.int32, device=self.dev)
+            out = self.packed
         nat.check(self.lib.wb_det_pack_launch(nat.stream_ptr(), nat.ptr(self.detb.recs), nat.ptr(self.detb.counts),
-                                              self.detb.cap, nat.ptr(self.packed), self.packed.shape[0] - 1),
-                  "wb_det_pack_launch")
-        return self.packed
+                                              self.detb.cap, nat.ptr(out), out.shape[0] - 1), "wb_det_pack_launch")
+        return out
 
     def fetch(self, dm, stt, limit=None):
         """Everything the host needs from the last scan in ONE synchronisation: the shard contents packed on
         the device (wb_det_pack_launch), then asynchronous copies of the header + first records and of
         alive[B, L, T] into page-locked memory, one event wait.  Grows the buffer and scans again if a shard
         overflowed; a second copy only when there are more than _FETCH_ROWS detections.
-        Returns (records int32 [n, 4] in shard order, alive int64 [B, L, T]).
-        limit: with more than `limit` detections the records stay on the device (self.packed[1:1 + n]; the caller orders
-        them there) and their count is returned in place of the array."""
+        Returns Packed(total, records int32 [total, 4] in shard order, alive int64 [B, L, T]).
+        limit: with more than `limit` detections the records stay on the device (self.packed[1:1 + total]; the caller
+        orders them there) and `records` is None."""
         import torch
-        T = dm.n_stages
         while True:
             if self._h_packed is None:
                 self._h_packed = torch.empty((1 + self._FETCH_ROWS, 4), dtype=torch.int32).pin_memory()
-                self._fetch_ev = torch.cuda.Event()
-            if self._h_alive is None or self._h_alive.shape != stt["alive"].shape:
-                self._h_alive = torch.empty(stt["alive"].shape, dtype=torch.int32).pin_memory()
             self.pack()
             rows = min(self._h_packed.shape[0], self.packed.shape[0])
             self._h_packed[:rows].copy_(self.packed[:rows], non_blocking=True)
-            self._h_alive.copy_(stt["alive"], non_blocking=True)
+            self._alive_enqueue(stt)
             self._fetch_ev.record()
             self._fetch_ev.synchronize()
             total, worst = int(self._h_packed[0, 0]), int(self._h_packed[0, 1])
             if worst <= self.detb.cap:
                 break
-            self.det_capacity = (int(worst * 1.5) + 16) * nat.WB_DET_SHARDS
-            self._alloc_det()
-            stt = self.run_cascade(dm, ranks=stt.get("ranks", False))
-        alive = self._h_alive.numpy()[:, :, :T].astype(np.int64)
+            stt = self._grow_and_rescan(dm, stt, worst)
+        alive = self._h_alive.numpy()[:, :, :dm.n_stages].astype(np.int64)
         if limit is not None and total > limit:
-            return total, alive
+            return Packed(total, None, alive)
         recs = self._h_packed[1:1 + min(total, rows - 1)].numpy().copy()
         if total > rows - 1:
             recs = np.concatenate([recs, self.packed[rows:1 + total].cpu().numpy()])
-        return recs, alive
+        return Packed(total, recs, alive)
 
-    def _final_ready(self):
-        """Whether Model.detect's one-copy read-back form applies to this engine (one image, a pyramid within the sort
-        key's 10 / 14 / 14-bit fields); allocates its buffers on first use."""
+    def _alive_enqueue(self, stt):
+        """The copy of alive[B, L, T] of the scan `stt` into page-locked memory (self._h_alive), no synchronisation."""
         import torch
-        p = self.plan
-        if self._final_dims is None:
-            ok = self.batch == 1 and 0 < p.n_levels <= 1024
+        if self._h_alive is None or self._h_alive.shape != stt["alive"].shape:
+            self._h_alive = torch.empty(stt["alive"].shape, dtype=torch.int32).pin_memory()
+        self._h_alive.copy_(stt["alive"], non_blocking=True)
+
+    def _key_extent(self):
+        """(whether this pyramid fits the sort key's bit fields, its largest u, its largest v) -- what the finish launches
+        are told; when it fits, they also take the levels' inverse scales, uploaded here on first use."""
+        import torch
+        if self._key_dims is None:
+            p = self.plan
             mu = max((int(lv["u"]) for lv in p.levels), default=0)
             mv = max((int(lv["v"]) for lv in p.levels), default=0)
-            self._final_dims = (ok and mu <= 16384 and mv <= 16384, mu, mv)
-        if not self._final_dims[0]:
-            return False
-        if self._inv_scales_d is None:
-            self._inv_scales_d = torch.from_numpy(self.inv_scales()).to(self.dev)
-            self._fetch_ev = self._fetch_ev or torch.cuda.Event()
-        return True
+            self._key_dims = (key_fits(p.n_levels, mu, mv), mu, mv)
+            if self._key_dims[0]:
+                self._inv_scales_d = torch.from_numpy(self.inv_scales()).to(self.dev)
+        return self._key_dims
+
+    def _final_ready(self):
+        """Whether Model.detect's one-copy read-back form applies to this engine: one image, a pyramid within the sort
+        key's bit fields."""
+        return self.batch == 1 and self._key_extent()[0]
 
     def _final_enqueue(self, dm, stt):
         """wb_det_finish_sorted_launch + the ONE read-back copy into page-locked memory (no synchronisation).  The buffers
@@ -937,34 +923,32 @@ class PyramidEngine:
         import torch
         n_alive = stt["alive"].numel()
         if "final" not in stt or stt["final_alive_words"] != n_alive:
-            # header | keys | boxes | scores | alive[B, L, T] (the kernel copies the statistics behind the scores: one
-            # read-back copy instead of two)
-            P = self._FETCH_ROWS
-            nbytes = 16 + P * 28 + 4 * n_alive
+            # the finish block | alive[B, L, T] (the kernel copies the statistics behind it: one read-back copy, not two)
+            blk = FinishBlock(self._FETCH_ROWS)
+            nbytes = blk.nbytes + 4 * n_alive
             stt["final"] = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
             stt["h_final"] = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
             stt["final_alive_words"] = n_alive
             h = stt["h_final"].numpy()
-            stt["h_final_views"] = (h[:16].view(np.int32), h[16:16 + 8 * P].view(np.uint64),
-                                    h[16 + 8 * P:16 + 24 * P].view(np.float32).reshape(P, 4), h[16 + 24 * P:16 + 28 * P].view(np.float32))
-            stt["h_alive"] = h[16 + 28 * P:].view(np.int32).reshape(tuple(stt["alive"].shape))
-        # (ordered on the device: one workgroup sorts the keys in LDS and writes keys, boxes and scores in the reference's
-        # order whenever they number at most 4096 -- header[3] says whether it did)
+            stt["h_final_views"] = blk.views(h)
+            stt["h_alive"] = h[blk.nbytes:].view(np.int32).reshape(tuple(stt["alive"].shape))
+        # (one workgroup sorts up to 4096 keys in LDS and writes the sections in the reference's order: header[3])
         nat.check(self.lib.wb_det_finish_sorted_launch(nat.stream_ptr(), nat.ptr(self.detb.recs), nat.ptr(self.detb.counts),
                                                        self.detb.cap, nat.ptr(self._inv_scales_d), self.plan.n_levels,
-                                                       self._final_dims[1], self._final_dims[2], dm.m, dm.n,
+                                                       self._key_dims[1], self._key_dims[2], dm.m, dm.n,
                                                        nat.ptr(stt["final"]), self._FETCH_ROWS, nat.ptr(stt["alive"]), n_alive),
                   "wb_det_finish_sorted_launch")
         stt["h_final"].copy_(stt["final"], non_blocking=True)
 
-    def _nms_buffers(self, holder, rows, n_images):
-        """Result block, its page-locked copy and the scratch of wb_nms_finish_launch for `n_images` finish blocks of
-        `rows` rows, kept in `holder` (a scan state, the batch's order buffers); None when the rows do not fit the
-        launch (then the caller suppresses the complete result with boxes.nms_keep_mask)."""
-        import ctypes as C
+    def _nms_enqueue(self, holder, fin_ptr, rows, n_images, nms):
+        """wb_nms_finish_launch on the `n_images` finish blocks of `rows` rows at `fin_ptr` + the copy of its keep flags
+        into page-locked memory, in the current stream, behind the launch that wrote the blocks (no synchronisation).
+        Its result block, that block's page-locked copy and its scratch are kept in `holder` (a scan state, the batch's
+        order buffers).  Nothing when the rows do not fit the launch: the caller then suppresses the complete result with
+        boxes.nms_keep_mask.  nms: (iou_threshold, score_threshold or None)."""
         import torch
         if rows < 4 or rows % 4:
-            return None
+            return
         nb = holder.get("nms")
         if nb is None or nb["rows"] != rows or nb["images"] != n_images:
             need = C.c_size_t()
@@ -974,16 +958,6 @@ class PyramidEngine:
                                       res=torch.empty(n_images * (16 + rows), dtype=torch.uint8, device=self.dev),
                                       h_res=torch.empty(n_images * (16 + rows), dtype=torch.uint8).pin_memory())
             nb["h"] = nb["h_res"].numpy().reshape(n_images, 16 + rows)
-        return nb
-
-    def _nms_enqueue(self, holder, fin_ptr, rows, n_images, nms):
-        """wb_nms_finish_launch on the finish block(s) at `fin_ptr` + the copy of its keep flags into page-locked memory,
-        in the current stream, behind the launch that wrote the blocks (no synchronisation).
-        nms: (iou_threshold, score_threshold or None)."""
-        import ctypes as C
-        nb = self._nms_buffers(holder, rows, n_images)
-        if nb is None:
-            return
         iou_t, score_t = nms
         nat.check(self.lib.wb_nms_finish_launch(nat.stream_ptr(), C.c_void_p(fin_ptr), rows, n_images, float(iou_t),
                                                 0 if score_t is None else 1, 0.0 if score_t is None else float(score_t),
@@ -1005,78 +979,63 @@ class PyramidEngine:
         return row[16:16 + total].astype(bool)
 
     def fetch_final(self, dm, stt, enqueued=False, stream=None, nms=None):
-        """fetch() for Model.detect on ONE image: wb_det_finish_launch leaves sort keys, boxes and scores of all
-        valid records behind one header; they come back with ONE copy and ONE event wait together with alive[B, L, T].
-        Returns (keys uint64 [n] (level << 54 | r << 40 | c << 26 | position), boxes float32 [rows, 4], scores
-        float32 [rows], alive int64 [B, L, T], ordered) -- ordered: the device sorted them (keys ascending, boxes[i] /
-        scores[i] the i-th detection: at most 4096 of them); else keys unsorted, boxes / scores indexed by a key's
-        position.  The arrays are views of the page-locked read-back buffer: copy what is kept.  None when this form does not apply (a batch, a pyramid beyond the key's bit fields, more than _FETCH_ROWS
-        detections): use fetch() then.  Grows the detection buffer and scans again if a shard overflowed.
+        """fetch() for Model.detect on ONE image: wb_det_finish_sorted_launch leaves sort keys, boxes and scores of all
+        valid records in one finish block (readback.FinishBlock); it comes back with ONE copy and ONE event wait together
+        with alive[B, L, T].  Returns a readback.Finished, or None when this form does not apply (a batch, a pyramid beyond
+        the key's bit fields, more than _FETCH_ROWS detections): use fetch() then.  Grows the detection buffer and scans
+        again if a shard overflowed.
         enqueued: the launch and the copies are already in the stream (detect_run's graph replay).
         stream: that stream, when it is not the current one -- then only the wait happens here, and False is returned
         if more than a wait is needed (the caller comes back on that stream).
         nms: (iou_threshold, score_threshold or None) -- non-maximum suppression ran (enqueued) or runs (not enqueued)
-        on the finish buffer behind the launch that wrote it, a scan repeated after an overflow included; the result then
-        has a sixth member: the keep flags (bool [n], positions of the finish buffer), or None when the device did not
-        suppress (the caller then suppresses the complete result)."""
+        on the finish buffer behind the launch that wrote it, a scan repeated after an overflow included; the result's
+        `keep` then holds its flags."""
         if not self._final_ready():
             return None
-        P, T = self._FETCH_ROWS, dm.n_stages
         while True:
             if not enqueued:
                 self._final_enqueue(dm, stt)
                 if nms is not None:
                     self._nms_enqueue(stt, stt["final"].data_ptr(), self._FETCH_ROWS, 1, nms)
             enqueued = False
-            if stream is None:
-                self._fetch_ev.record()
-            else:
-                self._fetch_ev.record(stream)
+            self._fetch_ev.record(stream)                     # (None: the current stream)
             self._fetch_ev.synchronize()
-            hdr, keys, boxes, scores = stt["h_final_views"]
-            total, worst = int(hdr[0]), int(hdr[1])
+            worst = int(stt["h_final_views"][0][1])
             if worst <= self.detb.cap:
                 break
             if stream is not None:
                 return False
-            self.det_capacity = (int(worst * 1.5) + 16) * nat.WB_DET_SHARDS
-            self._alloc_det()
-            stt = self.run_cascade(dm, ranks=stt.get("ranks", False))
-        if total > P:
+            stt = self._grow_and_rescan(dm, stt, worst)
+        return self._finished(stt, dm.n_stages, nms is not None)
+
+    def _finished(self, stt, T, nms=False):
+        """The Finished of the read-back in the scan state `stt` (T stages; nms: with the keep flags _nms_enqueue left),
+        None when there are more detections than the block holds."""
+        hdr, keys, boxes, scores = stt["h_final_views"]
+        total = int(hdr[0])
+        if total > self._FETCH_ROWS:
             return None
-        alive = stt["h_alive"][:, :, :T].astype(np.int64)
-        if nms is not None:
-            return keys[:total], boxes, scores, alive, bool(hdr[3]), self._nms_keep(stt, 0, P, total)
-        return keys[:total], boxes, scores, alive, bool(hdr[3])
+        return Finished(keys[:total], boxes, scores, stt["h_alive"][:, :, :T].astype(np.int64), bool(hdr[3]),
+                        self._nms_keep(stt, 0, self._FETCH_ROWS, total) if nms else None)
 
     _ORDER_ROWS = 4096               # per image: what wb_det_order_batch_launch orders (more: the caller's other path)
 
     def _order_buffers(self):
         """Buffers of the batch's ordered read-back (scratch, output, its page-locked copy), on first use; whether the
-        form applies to this pyramid (the sort key's 10 / 14 / 14-bit fields)."""
+        form applies to this pyramid (the sort key's bit fields)."""
         import torch
-        p = self.plan
         if self._order is None:
-            mu = max((int(lv["u"]) for lv in p.levels), default=0)
-            mv = max((int(lv["v"]) for lv in p.levels), default=0)
-            fits = 0 < p.n_levels <= 1024 and mu <= 16384 and mv <= 16384
-            od = self._order = dict(fits=fits, mu=mu, mv=mv)
-            if fits:
+            od = self._order = dict(fits=self._key_extent()[0])
+            if od["fits"]:
                 P, B = self._ORDER_ROWS, self.batch
-                blk = 16 + 28 * P
+                blk = FinishBlock(P)
                 od["scratch"] = torch.empty(B * (256 + 16 * P), dtype=torch.uint8, device=self.dev)
-                od["out"] = torch.empty(16 + B * blk, dtype=torch.uint8, device=self.dev)
-                od["h_out"] = torch.empty(16 + B * blk, dtype=torch.uint8).pin_memory()
+                od["out"] = torch.empty(16 + B * blk.nbytes, dtype=torch.uint8, device=self.dev)
+                od["h_out"] = torch.empty(16 + B * blk.nbytes, dtype=torch.uint8).pin_memory()
                 od["ev"] = torch.cuda.Event()
                 h = od["h_out"].numpy()
                 od["info"] = h[:16].view(np.int32)
-                od["views"] = []
-                for b in range(B):
-                    o = 16 + b * blk
-                    od["views"].append((h[o:o + 16].view(np.int32), h[o + 16:o + 16 + 8 * P].view(np.uint64),
-                                        h[o + 16 + 8 * P:o + 16 + 24 * P].view(np.float32).reshape(P, 4), h[o + 16 + 24 * P:o + blk].view(np.float32)))
-                if self._inv_scales_d is None:
-                    self._inv_scales_d = torch.from_numpy(self.inv_scales()).to(self.dev)
+                od["views"] = [blk.views(h, 16 + b * blk.nbytes) for b in range(B)]
         return self._order["fits"]
 
     def order_batch_enqueue(self, dm, stt, nms=None):
@@ -1084,19 +1043,16 @@ class PyramidEngine:
         into page-locked memory + an event, all in the current stream, no synchronisation: what fetch_ordered_batch
         waits for.  Enqueued right behind the step, the results are on the host by the time they are asked for.
         Returns False when the form does not apply to this pyramid."""
-        import torch
         if not self._order_buffers():
             return False
         od, p = self._order, self.plan
-        if self._h_alive is None or self._h_alive.shape != stt["alive"].shape:
-            self._h_alive = torch.empty(stt["alive"].shape, dtype=torch.int32).pin_memory()
         nat.check(self.lib.wb_det_order_batch_launch(nat.stream_ptr(), nat.ptr(self.detb.recs), nat.ptr(self.detb.counts),
                                                      self.detb.cap, self.batch, nat.ptr(self._inv_scales_d), p.n_levels,
-                                                     od["mu"], od["mv"], dm.m, dm.n, nat.ptr(od["scratch"]),
+                                                     self._key_dims[1], self._key_dims[2], dm.m, dm.n, nat.ptr(od["scratch"]),
                                                      od["scratch"].numel(), nat.ptr(od["out"]), self._ORDER_ROWS),
                   "wb_det_order_batch_launch")
         od["h_out"].copy_(od["out"], non_blocking=True)
-        self._h_alive.copy_(stt["alive"], non_blocking=True)
+        self._alive_enqueue(stt)
         if nms is not None:                                   # (every image's block suppressed in the same three launches)
             self._nms_enqueue(od, od["out"].data_ptr() + 16, self._ORDER_ROWS, self.batch, nms)
         od["ev"].record()
@@ -1108,12 +1064,10 @@ class PyramidEngine:
         and scores on the device; they come back with ONE copy and ONE event wait together with alive[B, L, T].
         enqueued: order_batch_enqueue has run behind the scan already (only the wait happens here).
         Grows the detection buffer and scans again if a shard overflowed.
-        Returns ([(keys uint64 [n_b], boxes float32 [n_b, 4], scores float32 [n_b]) per image], alive int64 [B, L, T])
-        -- views of the page-locked read-back buffer: copy what is kept -- or None when this form does not apply (a
+        Returns ([readback.ImageResult per image], alive int64 [B, L, T]), or None when this form does not apply (a
         pyramid beyond the sort key's bit fields, an image with more than _ORDER_ROWS detections): use fetch() then.
-        nms: as for order_batch_enqueue (with enqueued, what it was given there); every image's tuple then has a fourth
-        member, its keep flags (bool [n_b]) or None."""
-        T = dm.n_stages
+        nms: as for order_batch_enqueue (with enqueued, what it was given there); every image's `keep` then holds its
+        flags."""
         while True:
             if not enqueued and not self.order_batch_enqueue(dm, stt, nms):
                 return None
@@ -1123,19 +1077,15 @@ class PyramidEngine:
             worst = int(od["info"][1])
             if worst <= self.detb.cap:
                 break
-            self.det_capacity = (int(worst * 1.5) + 16) * nat.WB_DET_SHARDS
-            self._alloc_det()
-            stt = self.run_cascade(dm, ranks=stt.get("ranks", False))
+            stt = self._grow_and_rescan(dm, stt, worst)
         out = []
         for hdr, keys, boxes, scores in od["views"]:
             n_b = int(hdr[0])
             if int(hdr[1]) > self._ORDER_ROWS or int(hdr[3]) != 1:
                 return None
-            if nms is not None:
-                out.append((keys[:n_b], boxes[:n_b], scores[:n_b], self._nms_keep(od, len(out), self._ORDER_ROWS, n_b)))
-            else:
-                out.append((keys[:n_b], boxes[:n_b], scores[:n_b]))
-        return out, self._h_alive.numpy()[:, :, :T].astype(np.int64)
+            out.append(ImageResult(keys[:n_b], boxes[:n_b], scores[:n_b],
+                                   self._nms_keep(od, len(out), self._ORDER_ROWS, n_b) if nms is not None else None))
+        return out, self._h_alive.numpy()[:, :, :dm.n_stages].astype(np.int64)
 
     def live_check(self, dm):
         """A cascade whose specialised kernel has just been built, on the image(s) resident in this engine: the whole step
@@ -1170,7 +1120,7 @@ class PyramidEngine:
         """Model.detect's whole device sequence for the resident image -- one memset, octaves, channels, cascade,
         wb_det_finish_sorted_launch (which also carries alive[] behind the scores), the ONE read-back copy -- and its one synchronisation; from the second call with the
         same cascade on it is replayed as ONE hipGraph (one enqueue instead of seven, no gaps between the kernels).
-        Returns what fetch_final returns, or None (then: run(dm) has happened, use fetch()).
+        Returns what fetch_final returns: a readback.Finished, or None (then: use fetch()).
         nms: (iou_threshold, score_threshold or None) -- the same step, eager or replayed, then wb_nms_finish_launch and the
         copy of its keep flags enqueued behind it, in front of the one wait: the plain step's graph is shared, a new
         threshold captures nothing."""
@@ -1231,7 +1181,7 @@ class PyramidEngine:
         """waldboost.detect's whole device sequence for the resident image -- octaves, ONE channel pyramid (as ranks of
         dms[0]'s rank tables -- a rank group's union tables -- or as float32 channels), then per cascade of `dms` its
         scan, wb_det_finish_sorted_launch and the read-back copy -- with ONE wait at its end; from the second call with the
-        same cascades on it is one hipGraph replay.  Returns [what fetch_final returns, per cascade] -- None in the place of
+        same cascades on it is one hipGraph replay.  Returns [readback.Finished per cascade] -- None in the place of
         a cascade whose results did not fit (an overflowing detection buffer, more detections than one read-back holds): the
         pyramid stays resident and the caller scans that cascade alone again --, or None when the form does not apply at all
         (more cascades than an engine keeps states for, a pyramid beyond the sort key's fields, a sequence that kept missing
@@ -1275,23 +1225,18 @@ class PyramidEngine:
             self.rank_owner = dms[0].rank_key if ranks else None
         self._fetch_ev.record()
         self._fetch_ev.synchronize()
-        out, missed = [], False
+        out = []
         for d, stt in zip(dms, stts):
-            hdr, keys, boxes, scores = stt["h_final_views"]
-            total, worst = int(hdr[0]), int(hdr[1])
-            if worst > self.detb.cap or total > self._FETCH_ROWS:
-                # this cascade's results did not fit (a shard overflowed, or more detections than one read-back holds):
-                # None in its place -- the caller scans THAT cascade again on the pyramid this call left resident
-                # (Model.scan_engine: run_cascade + fetch, which grows the buffer); the others keep what they have
-                missed = True
-                out.append(None)
-            else:
-                out.append((keys[:total], boxes, scores, stt["h_alive"][:, :, :d.n_stages].astype(np.int64), bool(hdr[3])))
-        if missed:
+            # a cascade whose results did not fit (a shard overflowed, or more detections than one read-back holds): None
+            # in its place -- the caller scans THAT cascade again on the pyramid this call left resident
+            # (Model.scan_engine: run_cascade + fetch, which grows the buffer); the others keep what they have
+            out.append(None if int(stt["h_final_views"][0][1]) > self.detb.cap else self._finished(stt, d.n_stages))
+        if any(f is None for f in out):
             st["fails"] += 1                                  # (the whole sequence is tried again after 16, 32, 64 ... calls)
             st["skip"] = min(8 << st["fails"], 4096)
             # (the re-scans may reuse read-back buffers before the caller has collected the fitted results: hand out copies)
-            out = [None if f is None else (f[0].copy(), np.array(f[1][:f[0].size]), np.array(f[2][:f[0].size]), f[3], f[4]) for f in out]
+            out = [None if f is None else f._replace(keys=f.keys.copy(), boxes=np.array(f.boxes[:f.keys.size]),
+                                                     scores=np.array(f.scores[:f.keys.size])) for f in out]
         else:
             st["fails"] = 0
         return out
@@ -1300,16 +1245,15 @@ class PyramidEngine:
         """The wait and the read-back that end detect_run, for a token of detect_enqueue.
         stream: the stream detect_enqueue ran on, when that is not the current one."""
         import torch
-        if stream is None:
-            return None if token is None else self.fetch_final(dm, token, enqueued=True, nms=nms)
-        if token is not None:
-            fin = self.fetch_final(dm, token, enqueued=True, stream=stream, nms=nms)
-            if fin is not False:
-                return fin
-        with torch.cuda.stream(stream):                       # (the rare ways out: launches and copies of their own)
-            return None if token is None else self.fetch_final(dm, token, enqueued=False, nms=nms)
+        if token is None:
+            return None
+        fin = self.fetch_final(dm, token, enqueued=True, stream=stream, nms=nms)
+        if fin is False:
+            with torch.cuda.stream(stream):                   # (the rare ways out: launches and copies of their own)
+                fin = self.fetch_final(dm, token, enqueued=False, nms=nms)
+        return fin
 
-    def sorted_detections(self, n=None):
+    def sorted_detections(self):
         """Detections ordered by (image, level, r, c) as an int32 [n, 4] tensor of WbDet records."""
         return sort_records(self.detb.compact())
 
@@ -1319,8 +1263,7 @@ class PyramidEngine:
         boxes = torch.empty((n, 4), dtype=torch.float32, device=self.dev)
         scores = torch.empty(n, dtype=torch.float32, device=self.dev)
         if n:
-            inv = np.array([np.float32(1.0 / s) for s in self.plan.scales], np.float32)
-            inv_d = torch.from_numpy(inv).to(self.dev)
+            inv_d = torch.from_numpy(self.inv_scales()).to(self.dev)
             nat.check(self.lib.wb_boxes_launch(nat.stream_ptr(), nat.ptr(det_sorted), n, nat.ptr(inv_d), dm.m, dm.n,
                                                nat.ptr(boxes), nat.ptr(scores)), "wb_boxes_launch")
         return boxes, scores

@@ -16,6 +16,7 @@ from . import model_pb2
 from .boxes import Boxes, concatenate, nms_keep_mask, non_max_suppression
 from .channels import channel_pyramid
 from .compare import channel_tensor
+from .readback import host_boxes, key_positions, split_keys
 from .training import DTree, _REBINDS
 
 # above this many detections per call the compaction, ordering and boxes stay on the GPU
@@ -256,58 +257,41 @@ class Model:
         nms: (iou_threshold, score_threshold or None): only the detections non-maximum suppression keeps -- by the flags
         the device left with `fin`; the routes without them suppress their complete result (boxes.nms_keep_mask)."""
         m, n, Cc = self.shape
-        T = dm.n_stages                                   # (the cascade that was scanned: detect_stream collects late)
         if fin is False:
             fin = eng.fetch_final(dm, stt, nms=nms)       # ONE host synchronisation: sort keys, boxes, scores, statistics
+        got = fin if fin is not None else eng.fetch(dm, stt)      # (likewise: packed records + statistics)
+        # (dm: the cascade that was scanned -- detect_stream collects late)
+        res = dict(alive=got.alive[0].reshape(eng.plan.n_levels, dm.n_stages), scales=list(eng.plan.scales))
+        if "n_loc" not in stt:
+            stt["n_loc"] = eng.plan.n_loc(m, n)
+        self.n_loc += stt["n_loc"]
+        self.n_weak += int(res["alive"].sum())
+        keep = None
         if fin is not None:
             # get_boxes and the (level, r, c) keys were formed on the device (wb_det_finish_sorted_launch) and -- up to 4096
             # detections -- put in the reference's order there: the host copies slices out of the read-back buffer.
             # Otherwise it sorts the keys -- unique, so any sort kind gives the reference order -- and gathers
-            keys, boxes_d, scores_d, alive, ordered = fin[:5]
-            keep = fin[5] if nms is not None and len(fin) > 5 else None
-            alive = alive[0].reshape(eng.plan.n_levels, T)
-            if "n_loc" not in stt:
-                stt["n_loc"] = eng.plan.n_loc(m, n)
-            self.n_loc += stt["n_loc"]
-            self.n_weak += int(alive.sum())
-            if ordered:
-                ks = keys                                  # (the fields below are taken out as new arrays)
-                res = dict(boxes=boxes_d[:keys.size].copy(), scores=scores_d[:keys.size].copy(), alive=alive, scales=list(eng.plan.scales))
+            ks, keep = fin.keys, fin.keep
+            if fin.ordered:
+                res.update(boxes=fin.boxes[:ks.size].copy(), scores=fin.scores[:ks.size].copy())
             else:
-                ks = np.sort(keys)
-                at = (ks & np.uint64((1 << 26) - 1)).astype(np.intp)
-                res = dict(boxes=boxes_d[at], scores=scores_d[at], alive=alive, scales=list(eng.plan.scales))
+                ks = np.sort(ks)
+                at = key_positions(ks)
+                res.update(boxes=fin.boxes[at], scores=fin.scores[at])
                 keep = keep[at] if keep is not None else None
             if full:
-                res.update(level=(ks >> np.uint64(54)).astype(np.int32),
-                           r=((ks >> np.uint64(40)) & np.uint64(0x3fff)).astype(np.int64),
-                           c=((ks >> np.uint64(26)) & np.uint64(0x3fff)).astype(np.int64))
-            return _apply_nms(res, nms, keep)
-        recs, alive = eng.fetch(dm, stt)                  # ONE host synchronisation: packed records + statistics
-        alive = alive[0].reshape(eng.plan.n_levels, T)
-        n_det = recs.shape[0]
-        self.n_loc += eng.plan.n_loc(m, n)
-        self.n_weak += int(alive.sum())
-        if n_det <= _HOST_POST_MAX:
+                res["level"], res["r"], res["c"] = split_keys(ks)          # (new arrays, like boxes and scores)
+        elif got.total <= _HOST_POST_MAX:
             # few detections (the usual case): order and boxes on the host -- the same float32 arithmetic as
             # boxes_kernel, without three launches and four copies
-            d = recs.view(nat.DET_DTYPE).reshape(-1)
-            level, r, c = d["level"].astype(np.int64), d["r"].astype(np.int64), d["c"].astype(np.int64)
-            order = np.argsort((level << 32) | (r << 16) | c)        # (level, r, c): unique keys, any sort kind
-            level, r, c, score = level[order], r[order], c[order], d["score"][order]
-            inv = eng.inv_scales()[level] if n_det else np.zeros(0, "f")
-            boxes = np.empty((n_det, 4), np.float32)
-            np.multiply(c.astype(np.float32), inv, out=boxes[:, 0])
-            np.multiply(r.astype(np.float32), inv, out=boxes[:, 1])
-            np.multiply((c + n).astype(np.float32), inv, out=boxes[:, 2])
-            np.multiply((r + m).astype(np.float32), inv, out=boxes[:, 3])
-            return _apply_nms(dict(boxes=boxes, scores=score, level=level.astype(np.int32), r=r, c=c, alive=alive,
-                                   scales=list(eng.plan.scales)), nms)
-        det = eng.sorted_detections()
-        boxes, scores = eng.boxes(det, dm)
-        d = det.cpu().numpy().view(nat.DET_DTYPE).reshape(-1)
-        return _apply_nms(dict(boxes=boxes.cpu().numpy(), scores=scores.cpu().numpy(), level=d["level"].copy(),
-                               r=d["r"].astype(np.int64), c=d["c"].astype(np.int64), alive=alive, scales=list(eng.plan.scales)), nms)
+            _, res["level"], res["r"], res["c"], res["boxes"], res["scores"] = host_boxes(got.records, m, n, eng.inv_scales())
+        else:
+            det = eng.sorted_detections()
+            boxes, scores = eng.boxes(det, dm)
+            d = det.cpu().numpy().view(nat.DET_DTYPE).reshape(-1)
+            res.update(boxes=boxes.cpu().numpy(), scores=scores.cpu().numpy(), level=d["level"].copy(),
+                       r=d["r"].astype(np.int64), c=d["c"].astype(np.int64))
+        return _apply_nms(res, nms, keep)
 
     def detect_stream(self, images, lanes=3, batch=1, iou_threshold=None, score_threshold=None):
         """detect() over an iterable of 2-D images, as a generator of Boxes in the iterable's order -- the loop the
@@ -429,44 +413,33 @@ class Model:
         older way: few detections ordered on the host from the one read-back, otherwise ordered, and their boxes formed,
         on the device (wb_boxes_launch).  Updates n_loc / n_weak."""
         m, n, Cc = self.shape
-        # split by image, ordered and finished on the device (wb_det_order_batch_launch: up to 4096 detections per
-        # image): per image a copy of its slices of the one read-back
+        # ONE host synchronisation (overflow: grows and scans again); per image a copy of its slices of the one read-back
         # (enqueued: detect_stream has put the launch and the copies behind the scan already -- only the wait is left)
-        res = eng.fetch_ordered_batch(dm, stt, enqueued, nms) if _ORDER_BATCH else None   # ONE host synchronisation (overflow: grows and scans again)
+        res = eng.fetch_ordered_batch(dm, stt, enqueued, nms) if _ORDER_BATCH else None
         if res is not None:
             per_image, alive = res
             self.n_loc += count * eng.plan.n_loc(m, n)
             self.n_weak += int(alive[:count].sum())
             out = []
             for item in per_image[:count]:
-                boxes, scores = item[1], item[2]
+                boxes, scores = item.boxes, item.scores
                 if nms is not None:                            # (the device's keep flags; None: suppressed now)
-                    kept = _apply_nms(dict(boxes=boxes, scores=scores), nms, item[3])
+                    kept = _apply_nms(dict(boxes=boxes, scores=scores), nms, item.keep)
                     boxes, scores = kept["boxes"], kept["scores"]
                 bx = Boxes(boxes.copy())
                 bx.set_field("scores", scores.copy())
                 out.append(bx)
             return out
-        got, alive = eng.fetch(dm, stt, limit=_HOST_POST_BATCH)   # ONE host synchronisation (overflow: grows and scans again)
+        got = eng.fetch(dm, stt, limit=_HOST_POST_BATCH)          # ONE host synchronisation (overflow: grows and scans again)
         self.n_loc += count * eng.plan.n_loc(m, n)
-        self.n_weak += int(alive[:count].sum())
-        if isinstance(got, np.ndarray):
-            d = got.view(nat.DET_DTYPE).reshape(-1)
-            d = d[d["image"] < count]
-            image, level, r, c = (d[k].astype(np.int64) for k in ("image", "level", "r", "c"))
-            order = np.argsort((image << 48) | (level << 32) | (r << 16) | c)          # unique keys, any sort kind
-            image, level, r, c, scores = image[order], level[order], r[order], c[order], d["score"][order]
-            inv = eng.inv_scales()[level] if d.size else np.zeros(0, "f")
-            boxes = np.empty((d.size, 4), np.float32)
-            np.multiply(c.astype(np.float32), inv, out=boxes[:, 0])
-            np.multiply(r.astype(np.float32), inv, out=boxes[:, 1])
-            np.multiply((c + n).astype(np.float32), inv, out=boxes[:, 2])
-            np.multiply((r + m).astype(np.float32), inv, out=boxes[:, 3])
+        self.n_weak += int(got.alive[:count].sum())
+        if got.records is not None:
+            d = got.records.view(nat.DET_DTYPE).reshape(-1)
+            image, _, _, _, boxes, scores = host_boxes(d[d["image"] < count], m, n, eng.inv_scales(), with_image=True)
         else:
-            det = _engine.sort_records(eng.packed[1:1 + got])
-            boxes, scores = eng.boxes(det, dm)
+            det = _engine.sort_records(eng.packed[1:1 + got.total])
             image = det[:, 0].cpu().numpy()
-            boxes, scores = boxes.cpu().numpy(), scores.cpu().numpy()
+            boxes, scores = (t.cpu().numpy() for t in eng.boxes(det, dm))
         cuts = np.searchsorted(image, np.arange(count + 1))
         out = []
         for b in range(count):
@@ -514,23 +487,18 @@ class Model:
         res = eng.fetch_ordered_batch(dm, stt, nms=_nms) if (_ORDER_BATCH and B <= 256) else None
         if res is not None:
             per_image, alive = res
-            if _nms is not None:
-                done = []
-                for keys, boxes, scores, keep in per_image:
-                    if keep is None:                           # (the device left no flags for this image: suppressed now)
-                        keep = nms_keep_mask(boxes, scores, _nms[0], _nms[1])
-                    at = np.flatnonzero(keep)
-                    done.append((keys[at], boxes[at], scores[at]))
-                per_image = done
             alive = alive.reshape(B, L, T)
             self.n_loc += B * eng.plan.n_loc(m, n)
             self.n_weak += int(alive.sum())
-            keys = np.concatenate([k for k, _, _ in per_image]) if B else np.empty(0, np.uint64)
-            return dict(batch=B, image=np.repeat(np.arange(B, dtype=np.int32), [k.size for k, _, _ in per_image]),
-                        level=(keys >> np.uint64(54)).astype(np.int32), r=((keys >> np.uint64(40)) & np.uint64(0x3fff)).astype(np.int64),
-                        c=((keys >> np.uint64(26)) & np.uint64(0x3fff)).astype(np.int64),
-                        boxes=np.concatenate([b_ for _, b_, _ in per_image]), scores=np.concatenate([s_ for _, _, s_ in per_image]),
-                        alive=alive, scales=list(eng.plan.scales))
+            level, r, c = split_keys(np.concatenate([it.keys for it in per_image]))
+            res = dict(batch=B, image=np.repeat(np.arange(B, dtype=np.int32), [it.keys.size for it in per_image]),
+                       level=level, r=r, c=c, boxes=np.concatenate([it.boxes for it in per_image]),
+                       scores=np.concatenate([it.scores for it in per_image]), alive=alive, scales=list(eng.plan.scales))
+            if _nms is None:
+                return res
+            # (keep None: the device left no flags for this image, it is suppressed now)
+            keep = [it.keep if it.keep is not None else nms_keep_mask(it.boxes, it.scores, _nms[0], _nms[1]) for it in per_image]
+            return _apply_nms(res, _nms, np.concatenate(keep))
         eng.ensure_capacity(dm)
         det = eng.sorted_detections()
         boxes, scores = eng.boxes(det, dm)
