@@ -6,6 +6,7 @@ import os
 import numpy as np
 import pytest
 
+import fit_designs as fd
 import fit_reference as fr
 import waldboost_amd as wb
 from fit_fixture import assert_tree_equal, case, case_names, fixture
@@ -82,7 +83,7 @@ def test_every_node_of_a_random_tree_holds_against_the_yardstick(name):
     w = fr.split_weights(W, Y)
     msl = kw.get("min_samples_leaf", 10)
     assert np.array_equal(info["samples"][0], np.arange(W.size))
-    n_split = 0
+    n_split = n_tied = 0
     for i in range(tree.left.size):
         S, depth = info["samples"][i], int(info["depth"][i])
         pred = fr.node_prediction(W, Y, S, kw.get("clip", 3), kw.get("quantizer", 32))
@@ -108,16 +109,77 @@ def test_every_node_of_a_random_tree_holds_against_the_yardstick(name):
             assert abs(info["metric"][i] - mine) <= 1e-10
             if fr.table_gap(M) >= 1e-8:
                 assert (f, t) == (int(A[k]), t_best)
+                n_tied += int((M == m_best).sum() >= 2)           # ... where the yardstick's best was an exact tie
         goes_left = X[S, f] <= t
         assert np.array_equal(info["samples"][tree.left[i]], S[goes_left])
         assert np.array_equal(info["samples"][tree.right[i]], S[~goes_left])
         assert info["depth"][tree.left[i]] == info["depth"][tree.right[i]] == depth + 1
     assert n_split >= 1
+    print(f"{name}: {n_tied} of {n_split} split nodes had an exact tie at the best and were held to the first argmax")
+    if name == "banks_d2":                                  # 240 samples leave gaps in 0 .. 255: runs of thresholds tie
+        assert n_tied >= 1
     # the whole tree against the yardstick's, when every split of it is clear
     ref_tree, nodes = fr.fit(X0, W0, X1, W1, **kw)
     gaps = np.array([n["gap"] for n in nodes if n["left"] >= 0])
     if np.all(np.isnan(gaps) | (gaps >= 1e-8)):
         assert_tree_equal(tree, {a: getattr(ref_tree, a) for a in ("feature", "threshold", "left", "right", "prediction")}, name)
+
+
+# ------------------------------------------------------------------------------ a designed tree
+def _designed_tree_case():
+    """Depth 3 from the planted generator of tests/fit_designs.py: the root's column f* = 10 has a copy, feature 4, earlier
+    in allowed_features[0]; class 0 keeps to the low side of t* and 25 class-1 samples stray there, so the root's right
+    child is pure -- the NaN rule, (A[0], xmin) -- and is split again all the same.  Integer weights with a class total of
+    2^17: the split weights and every sum of them are exact on both sides, so ties are ties."""
+    rng = np.random.default_rng(21)
+    shape, n0, n1, f_star, f_dup, t_star = (3, 3, 2), 150, 170, 10, 4, 120
+    F = int(np.prod(shape))
+    cls = np.array([0] * n0 + [1] * n1, np.uint8)
+    X = fd._noise(rng, n0 + n1, F)
+    col = fd._planted_values(rng, cls, t_star, flip=0.0)
+    col[n0 + rng.permutation(n1)[:25]] = rng.integers(30, t_star - 29, 25)
+    X[:, f_star] = X[:, f_dup] = col
+    W = []
+    for n in (n0, n1):
+        k = rng.integers(256, 1024, n)
+        rest = 2 ** 17 - int(k.sum())                           # a class total of 2^17: w' = W / 2^18 is exact
+        k += rest // n
+        k[:rest % n] += 1
+        assert k.sum() == 2 ** 17 and k.min() > 0
+        W.append(k.astype(np.float64))
+    allowed = [np.array([13, 4, 2, 10, 7, 0, 16]), np.array([9, 1, 15, 3, 12]), np.array([17, 5, 11, 8, 6, 14])]
+    kw = dict(max_depth=3, min_samples_leaf=10, allowed_features=allowed)
+    return X[:n0].reshape((n0,) + shape), W[0], X[n0:].reshape((n1,) + shape), W[1], kw, (f_star, f_dup)
+
+
+def test_designed_tree_with_a_feature_tie_and_a_pure_child():
+    X0, W0, X1, W1, kw, (f_star, f_dup) = _designed_tree_case()
+    tree, info = fit_detail(X0, W0, X1, W1, **kw)
+    ref_tree, nodes = fr.fit(X0, W0, X1, W1, **kw)
+    assert_tree_equal(tree, {a: getattr(ref_tree, a) for a in ("feature", "threshold", "left", "right", "prediction")})
+    # the yardstick's tree is a fair judge: every rated split of it leads by a margin
+    gaps = np.array([n["gap"] for n in nodes if n["left"] >= 0])
+    assert np.all(np.isnan(gaps) | (gaps >= 1e-6)) and tree.depth() == 3
+    # the cross-feature tie occurred: the copy's row of the root's table equals f*'s bit for bit, the best is in both and
+    # in several thresholds of each, and the earlier entry of A and its first best threshold were taken
+    root = nodes[0]
+    A, M = root["A"].tolist(), root["table"]
+    ka, kb = A.index(f_dup), A.index(f_star)
+    tied = M == root["metric"]
+    assert ka < kb and np.array_equal(M[ka].view(np.uint64), M[kb].view(np.uint64))
+    assert tied[ka].sum() >= 2 and np.flatnonzero(tied.any(axis=1)).tolist() == [ka, kb]
+    assert info["flat_feature"][0] == f_dup and tree.threshold[0] == np.flatnonzero(tied[ka])[0]
+    # the pure child occurred: one class, at least min_samples_leaf samples, a NaN metric, (A[0], xmin), and children
+    pure = int(tree.right[0])
+    S = info["samples"][pure]
+    assert S.size >= kw["min_samples_leaf"] and S.min() >= X0.shape[0] and info["depth"][pure] == 1
+    assert np.isnan(info["metric"][pure]) and np.isnan(nodes[pure]["metric"]) and info["t0"][pure] == 0 and info["t1"][pure] > 0
+    first = int(kw["allowed_features"][1][0])
+    xs = np.concatenate([X0, X1]).reshape(-1, X0[0].size)[S, first]
+    assert (int(info["flat_feature"][pure]), int(tree.threshold[pure])) == (first, int(xs.min()))
+    assert tree.left[pure] > 0 and tree.right[pure] > 0
+    assert np.array_equal(info["samples"][tree.left[pure]], S[xs == xs.min()])
+    assert np.isfinite(info["metric"][tree.left[0]])                        # ... beside a rated node in the same launch
 
 
 # ------------------------------------------------------------------------------ order independence
