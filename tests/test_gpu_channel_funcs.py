@@ -295,6 +295,33 @@ def test_channel_function_arguments_that_change_the_arithmetic_dtype():
         wb.channels.grad_hist(img, bias=np.complex64(1.0))
 
 
+# ------------------------------------------------------------------------------ every cell of the kernels' dispatch table
+CELL_FUNCS = {"grad_hist": wb.channels.grad_hist, "grad_mag": wb.channels.grad_mag, **FUNCS}
+CELL_INPUTS = [("grad_hist", np.uint8), ("grad_hist", np.float32), ("grad_hist", np.int16), ("grad_hist_4_u1", np.uint8),
+               ("grad_mag_u1", np.uint8), ("grad_mag", np.uint8), ("grad_mag", np.float32)]
+
+
+@pytest.mark.parametrize("smooth", [0, 1])
+@pytest.mark.parametrize("shrink", [1, 2, 4])
+@pytest.mark.parametrize("fn,dtype", CELL_INPUTS, ids=lambda v: v if isinstance(v, str) else np.dtype(v).name)
+def test_every_cell_of_the_channel_dispatch_vs_oracle(fn, dtype, shrink, smooth):
+    """Channel function x image dtype (int16: the float64-held path) x shrink x smooth: each cell is a kernel instantiation
+    of its own, chosen by the one dispatcher from the one tile table.  75 x 150 is the smallest image whose level 0 has at
+    least two tiles on both axes and a partial bottom and right tile at every shrink (5 x 3 tiles of 16 x 64, 3 x 2, 3 x 2
+    of 8 x 30 or 8 x 32); the pyramid also holds an identity level and staged down-scaled ones.  Bit for bit."""
+    if dtype == np.int16:
+        img = synth_image(75, 150, 7, np.uint8).astype(np.int16) * 97 - 9000
+    else:
+        img = synth_image(75, 150, 7, dtype)
+    opts = dict(shrink=shrink, n_per_oct=2, smooth=smooth)
+    ref = list(orc.channel_pyramid(img, dict(opts, channels=fn)))
+    got = list(wb.channels.channel_pyramid(img, dict(opts, channels=CELL_FUNCS[fn])))
+    assert len(got) == len(ref) == 8
+    for l, ((c, s), (rc, rs)) in enumerate(zip(got, ref)):
+        assert s == rs and c.dtype == rc.dtype and c.shape == rc.shape, l
+        assert np.array_equal(np.ascontiguousarray(c).view(np.uint8), np.ascontiguousarray(rc).view(np.uint8)), l
+
+
 # ------------------------------------------------------------------------------ a channel function without a kernel
 def _two_channels(im):
     """A caller's own channel function (reference channels.py:119,136 calls whatever channel_opts["channels"] holds)."""

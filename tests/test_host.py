@@ -101,17 +101,42 @@ def test_channels_tile_query_and_argument_errors_without_gpu():
     import ctypes as C
     lib = nat.load()
     tu, tv = C.c_int(), C.c_int()
-    assert lib.wb_channels_tile(nat.WB_CHN_GRAD_HIST, 2, C.byref(tu), C.byref(tv)) == 0 and (tu.value, tv.value) == (16, 64)
-    assert lib.wb_channels_tile(nat.WB_CHN_GRAD_HIST_4_U1, 2, C.byref(tu), C.byref(tv)) == 0 and (tu.value, tv.value) == (16, 64)
-    assert lib.wb_channels_tile(nat.WB_CHN_GRAD_HIST, 1, C.byref(tu), C.byref(tv)) == 0 and (tu.value, tv.value) == (16, 64)
-    assert lib.wb_channels_tile(nat.WB_CHN_GRAD_HIST, 4, C.byref(tu), C.byref(tv)) == 0 and (tu.value, tv.value) == (8, 30)
-    assert lib.wb_channels_tile(nat.WB_CHN_GRAD_HIST_4_U1, 4, C.byref(tu), C.byref(tv)) == 0 and (tu.value, tv.value) == (8, 32)
-    assert lib.wb_channels_tile(nat.WB_CHN_GRAD_HIST, 3, C.byref(tu), C.byref(tv)) == nat.WB_ERR_UNSUPPORTED
-    assert b"shrink=3" in lib.wb_last_error()
+    funcs = (nat.WB_CHN_GRAD_HIST, nat.WB_CHN_GRAD_HIST_4_U1, nat.WB_CHN_GRAD_MAG_U1, nat.WB_CHN_GRAD_MAG)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    for fid in funcs:
+        for shrink in (1, 2, 4):
+            want = (16, 64) if shrink != 4 else (8, 30) if fid == nat.WB_CHN_GRAD_HIST else (8, 32)
+            assert lib.wb_channels_tile(fid, shrink, C.byref(tu), C.byref(tv)) == 0 and (tu.value, tv.value) == want, (fid, shrink)
+            if fid == nat.WB_CHN_GRAD_MAG:
+                continue                                # (takes no patch table)
+            # the patch table is computed with the same shapes: a plan tiled with them is accepted for either smooth, and
+            # a small uint8 plan at shrink 2 stages some of its tiles
+            p = PyramidPlan(75, 150, shrink, 2, 1, chan_func=fid)
+            table, _ = p.level_table()
+            tiles = np.ascontiguousarray(p.chan_tiles())
+            assert tiles.size == sum(-(-lv["u"] // want[0]) * -(-lv["v"] // want[1]) for lv in p.levels)
+            for smooth in (0, 1):
+                out = np.zeros(tiles.size, nat.PATCH_DTYPE)
+                assert lib.wb_channels_tile_patches(fid, shrink, smooth, vp(table), p.n_levels, vp(tiles), tiles.size, vp(out)) == 0
+                assert shrink != 2 or (out["rows"] > 0).any()
+        assert lib.wb_channels_tile(fid, 3, C.byref(tu), C.byref(tv)) == nat.WB_ERR_UNSUPPORTED
+        assert b"shrink=3" in lib.wb_last_error()
     # null pointers are rejected before any HIP call
     assert lib.wb_octaves_launch(None, None, 0, 1, 16, 16, 256, None, 0, None, 1, None) == nat.WB_ERR_INVALID
     with pytest.raises(ValueError):
         nat.check(lib.wb_model_info(None, None), "wb_model_info")
+
+
+def test_channels_launch_checks_rank_and_rank_model_before_it_reads_the_model():
+    """rank without rank_model (16-bit ranks): WB_ERR_INVALID, not a read through the null model.  Every requirement of
+    wb_channels_launch_x precedes its first HIP call, so the dummy pointers are never followed."""
+    lib = nat.load()
+    buf = np.zeros(64, np.uint64)
+    p = C.c_void_p(buf.ctypes.data)       # img, levels, tiles, minmax, taps and rank; rank_model stays NULL
+    rc = lib.wb_channels_launch_x(None, p, 0, None, 0, nat.WB_DTYPE_U8, 1, p, 1, p, 1, p, 1, p, nat.WB_CHN_GRAD_HIST, 2, 1,
+                                  None, None, 0, None, p, 0, None, nat.WB_DTYPE_RANK16)
+    assert rc == nat.WB_ERR_INVALID
+    assert b"rank and rank_model" in lib.wb_last_error()
 
 
 def test_compute_entry_points_fail_loudly_without_a_gpu():
