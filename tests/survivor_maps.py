@@ -32,7 +32,7 @@ PHASE_A = 8               # S0 in wb_cascade_tile.h: dense stages before the wor
 WAVES = 8                 # wb_api.hip, wb_model_create: `int rpw = 4, waves = 8;` (tile_rows = rpw * waves); wb_model_info does
 #                           not report it: the GPU module checks it, and queue_cap with it, through lds_bytes() below
 GENERIC_WAVES = 4         # ... and `M->waves = 4` for the node-walk kernel (tile_rows 4)
-SPAR = (32, 8, 16, 2)     # wb_cascade.hip, wb_cascade_launch_z: `Spar s = {{32, 8, 16, 2}};`
+SPAR = (32, 8, 16, 2)     # wb_cascade.hip, CascEnv: `int spar[4] = {32, 8, 16, 2};`
 SPAR_WG = 32              # same function: `... atoi(getenv("WB_CASC_SPAR_WG")) : 32`
 NEVER = 255               # a death stage no cascade here reaches (T <= 200), and a valid uint8 pixel
 REJECT = -1000.0

@@ -3,7 +3,9 @@
 done on the device: every record is ranked by the number of smaller keys.  Checked against NumPy for record counts
 around the sizes the kernel's loops change shape at (a workgroup's 32 records, a pass's 64 keys, the 4096-key limit
 behind which the kernel leaves the ordering to the host), and wb_det_order_batch_launch -- the same per image of a
-batch -- on records mixed over the shards as a batched scan leaves them."""
+batch -- on records mixed over the shards as a batched scan leaves them.  wb_det_pack_launch and wb_det_finish_launch,
+which share the kernels' shard prefix, on designed shards: empty ones, the last one alone, overflowed counters, a capacity
+below the valid total."""
 import ctypes as C
 
 import numpy as np
@@ -190,3 +192,81 @@ def test_order_batch_splits_by_image_and_orders_every_image(per_image):
         c, r = e["c"].astype(np.int64), e["r"].astype(np.int64)
         want = np.stack([c.astype(np.float32) * sc, r.astype(np.float32) * sc, (c + n).astype(np.float32) * sc, (r + m).astype(np.float32) * sc], 1)
         assert np.array_equal(boxes[:k].view(np.uint32), want.view(np.uint32))
+
+
+# ---- designed shards for the two entry points that only read the shard prefix and copy: a few hundred records
+DESIGNED = ["all-empty", "only-shard-63", "empty-and-overflowing-alternate", "capacity-below-total"]
+
+
+def _designed(case):
+    """(records by shard -- a shard's counter is its length, which may exceed cap --, cap, output capacity)."""
+    rng = np.random.default_rng(DESIGNED.index(case))
+    if case == "all-empty":
+        return [_records(rng, 0) for _ in range(SHARDS)], 16, 64
+    if case == "only-shard-63":
+        return [_records(rng, 200 if s == 63 else 0) for s in range(SHARDS)], 256, 256
+    if case == "empty-and-overflowing-alternate":
+        d = _records(rng, sum(10 + s % 4 for s in range(1, SHARDS, 2)))
+        cuts = np.cumsum([10 + s % 4 if s % 2 else 0 for s in range(SHARDS)])
+        return np.split(d, cuts[:-1]), 9, 512                # (every odd shard's counter is 1 .. 4 above cap)
+    d = _records(rng, 300)
+    shard = rng.integers(0, SHARDS, 300)
+    by = [d[shard == s] for s in range(SHARDS)]
+    return by, max(len(b) for b in by), 100
+
+
+def _expected(by, cap, out_cap):
+    valid = np.concatenate([b[:cap] for b in by])
+    return valid, [valid.size, max(len(b) for b in by), min(valid.size, out_cap), cap]
+
+
+@pytest.mark.parametrize("case", DESIGNED)
+def test_det_pack_on_designed_shards(case):
+    """wb_det_pack_launch: the header, the valid records of the shards back to back in shard order, cut at the capacity,
+    and not a byte written behind them."""
+    import torch
+    from waldboost_amd import _native as nat
+    lib = nat.load()
+    by, cap, out_cap = _designed(case)
+    valid, header = _expected(by, cap, out_cap)
+    det = np.zeros((SHARDS * cap, 4), np.int32)
+    for s, r in enumerate(by):
+        det[s * cap:s * cap + min(len(r), cap)] = r[:cap].view(np.int32).reshape(-1, 4)
+    det_d = torch.from_numpy(det).to("cuda:0")
+    cnt_d = torch.from_numpy(np.array([len(r) for r in by], np.int32)).to("cuda:0")
+    out = torch.full((16 + 16 * out_cap + 256,), 0xCD, dtype=torch.uint8, device="cuda:0")
+    rc = lib.wb_det_pack_launch(None, P(det_d.data_ptr()), P(cnt_d.data_ptr()), C.c_uint32(cap), P(out.data_ptr()), C.c_uint32(out_cap))
+    assert rc == 0, lib.wb_last_error()
+    torch.cuda.synchronize()
+    h = out.cpu().numpy()
+    assert h[:16].view(np.int32).tolist() == header
+    present = header[2]
+    assert np.array_equal(h[16:16 + 16 * present].view(nat.DET_DTYPE), valid[:present])
+    assert (h[16 + 16 * present:] == 0xCD).all()
+
+
+@pytest.mark.parametrize("case", DESIGNED)
+def test_det_finish_on_designed_shards(case):
+    """wb_det_finish_launch against NumPy directly: keys of (level, r, c, packed position), boxes and scores at the
+    packed positions, header[3] = cap, nothing written behind the records present."""
+    from waldboost_amd import _native as nat
+    from waldboost_amd.readback import split_keys
+    lib = nat.load()
+    by, cap, out_cap = _designed(case)
+    valid, header = _expected(by, cap, out_cap)
+    inv = (1.0 / (1.0 + 0.09 * np.arange(40))).astype(np.float32)
+    m, n = 12, 14
+    hdr, keys, boxes, scores = _finish(lib, lib.wb_det_finish_launch, by, cap, inv, m, n, out_cap)
+    assert hdr.tolist() == header
+    present = header[2]
+    e = valid[:present]
+    level, r, c = split_keys(keys[:present])
+    assert np.array_equal(level, e["level"]) and np.array_equal(r, e["r"]) and np.array_equal(c, e["c"])
+    assert np.array_equal(keys[:present] & np.uint64((1 << 26) - 1), np.arange(present, dtype=np.uint64))
+    sc = inv[e["level"]]
+    c, r = e["c"].astype(np.int64), e["r"].astype(np.int64)
+    want = np.stack([c.astype(np.float32) * sc, r.astype(np.float32) * sc, (c + n).astype(np.float32) * sc, (r + m).astype(np.float32) * sc], 1)
+    assert np.array_equal(boxes[:present].view(np.uint32), want.view(np.uint32))
+    assert np.array_equal(scores[:present].view(np.uint32), e["score"].view(np.uint32))
+    for section in (keys, boxes, scores):
+        assert (section[present:].view(np.uint8) == 0xCD).all()

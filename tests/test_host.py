@@ -139,6 +139,36 @@ def test_channels_launch_checks_rank_and_rank_model_before_it_reads_the_model():
     assert b"rank and rank_model" in lib.wb_last_error()
 
 
+def test_finishing_entry_points_refuse_what_the_sort_key_cannot_hold_with_one_message():
+    """The key's limits (10-bit level, 14-bit row and column, 26-bit packed position) are stated once in the library
+    (wb_det.hip: det_key_fits) and agree with readback.key_fits: each of the three finishing entry points refuses each
+    excess with WB_ERR_UNSUPPORTED and the same message behind its own name.  Only refused calls are made: every
+    requirement precedes the first HIP call, so the dummy pointers are never followed."""
+    from waldboost_amd.readback import key_fits
+    lib = nat.load()
+    buf = np.zeros(64, np.uint64)
+    p = C.c_void_p((buf.ctypes.data + 15) & ~15)          # det, det_count, inv_scale, scratch and out
+    cap = C.c_uint32(16)
+    assert key_fits(1024, 16384, 16384)
+    for levels, rows, cols, out_cap in [(1025, 16384, 16384, 1 << 26), (1024, 16385, 16384, 1 << 26),
+                                        (1024, 16384, 16385, 1 << 26), (1024, 16384, 16384, (1 << 26) + 4)]:
+        assert key_fits(levels, rows, cols) == (out_cap > 1 << 26)
+        key = (C.c_int(levels), C.c_int(rows), C.c_int(cols), C.c_int(12), C.c_int(12))
+        tails = []
+        for name, call in [
+                ("wb_det_finish_launch", lambda: lib.wb_det_finish_launch(None, p, p, cap, p, *key, p, C.c_uint32(out_cap))),
+                ("wb_det_finish_sorted_launch",
+                 lambda: lib.wb_det_finish_sorted_launch(None, p, p, cap, p, *key, p, C.c_uint32(out_cap), None, C.c_uint32(0))),
+                ("wb_det_order_batch_launch",
+                 lambda: lib.wb_det_order_batch_launch(None, p, p, cap, C.c_int(2), p, *key, p, C.c_size_t(1 << 40), p, C.c_uint32(out_cap)))]:
+            assert call() == nat.WB_ERR_UNSUPPORTED, name
+            who, _, tail = lib.wb_last_error().decode().partition(": ")
+            assert who == name
+            tails.append(tail)
+        assert tails[0] == tails[1] == tails[2], tails
+        assert tails[0] == f"{levels} levels of up to {rows} x {cols} windows, {out_cap} records do not fit the 10/14/14/26-bit key"
+
+
 def test_compute_entry_points_fail_loudly_without_a_gpu():
     import torch
     if torch.cuda.is_available():

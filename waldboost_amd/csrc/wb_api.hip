@@ -9,10 +9,6 @@
 
 #include "wb_common.h"
 
-int wb_cascade_prepare(int depth, int rpw, int waves);  // wb_cascade.hip
-int wb_cascade_group(int depth);                        // stages evaluated per group
-int wb_cascade_lds_bytes(int eb, int C, int rows, int pitch, int TR, int waves, int T, int lds_stages,
-                         int depth);                    // dynamic LDS of the tile kernel
 int wb_jit_get(const int32_t *words, size_t n_words, int T, int D, int rpw, int waves, int C, int rows, int pitch, int eb,
                int lds_stages, void **func_out);                                 // wb_jit.hip
 void wb_jit_release(void *func);                        // wb_jit.hip
@@ -40,7 +36,7 @@ struct TreeView {
     const int32_t *rank;   // binned tiles: index of the node's threshold among its channel's sorted distinct thresholds (-1: NaN)
 };
 
-// cell of the linear lookup grid a value falls into -- the host mirror of bin_cell() in wb_cascade.hip
+// cell of the linear lookup grid a value falls into -- the host mirror of wb_bin_cell() in wb_common.h
 // (fmaf is correctly rounded on both sides, so both map every float to the same cell)
 inline uint32_t bin_cell(float v, float k, float b, int N) {
     const float q = fmaf(v, k, b);

@@ -149,6 +149,12 @@ struct WbModel {
     float *g_theta;             // [n_stages]
 };
 
+// ---- the tile kernel's host side (wb_cascade.hip), as wb_model_create needs it ----
+int wb_cascade_prepare(int depth, int rpw, int waves);  // the instances' dynamic-LDS limit raised; WB_ERR_UNSUPPORTED: no kernel for this shape
+int wb_cascade_group(int depth);                        // stages evaluated per group
+int wb_cascade_lds_bytes(int eb, int C, int rows, int pitch, int TR, int waves, int T, int lds_stages,
+                         int depth);                    // dynamic LDS of the tile kernel
+
 // ---- threshold ranks of float32 channel values (WbModel::bin_*, WB_DTYPE_RANK8) ----
 // cell of a channel's lookup grid (host mirror: bin_cell() in wb_api.hip): non-decreasing in v
 __device__ inline uint32_t wb_bin_cell(float v, float k, float b, float top = (float)(WB_BIN_CELLS - 1)) {
