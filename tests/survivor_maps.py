@@ -29,7 +29,7 @@ from oracle import wb_oracle as orc
 # (paths below: waldboost_amd/csrc/)
 TILE_COLS = 64            # WB_CASC_TC (wb_common.h): windows per tile row = lanes of a wave
 PHASE_A = 8               # S0 in wb_cascade_tile.h: dense stages before the workgroup-wide re-pack
-WAVES = 8                 # wb_api.hip, wb_model_create: `int rpw = 4, waves = 8;` (tile_rows = rpw * waves); wb_model_info does
+WAVES = 8                 # wb_model.hip, choose_geometry: `int rpw = 4, waves = 8;` (tile_rows = rpw * waves); wb_model_info does
 #                           not report it: the GPU module checks it, and queue_cap with it, through lds_bytes() below
 GENERIC_WAVES = 4         # ... and `M->waves = 4` for the node-walk kernel (tile_rows 4)
 SPAR = (32, 8, 16, 2)     # wb_cascade.hip, CascEnv: `int spar[4] = {32, 8, 16, 2};`

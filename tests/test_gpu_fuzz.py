@@ -64,7 +64,7 @@ def test_random_configuration(seed):
 # before the first scan: depth-3 trees under a permissive cascade (10k-89k detections, tiles with more than 1024
 # survivors after eight stages).  The code hiprtc produced for them wrote a few wrong records per such
 # tile; a specialised kernel is now self-tested against the generic one before use, and a model whose build fails stays on
-# the generic kernel (csrc/wb_api.hip jit_selftest).  Three passes each: the damage came and went.
+# the generic kernel (csrc/wb_jit.hip wb_jit_selftest).  Three passes each: the damage came and went.
 @pytest.mark.parametrize("seed", [558, 569, 644, 5, 18, 41])
 def test_random_configuration_through_the_specialised_kernel(seed):
     M, img = random_configuration(seed)

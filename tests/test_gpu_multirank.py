@@ -209,3 +209,54 @@ def test_bench_multi_rank_region_with_its_exchange():
     assert out["ranks"]["world_size_reported"] == 1 and out["ranks"]["parity_gate_passed"] == [True]
     assert "end of every timed region" in out["config"]["collective"]
     assert out["parity"]["bit_exact"] and out["parity"]["gathered"]["bit_exact"] and out["parity"]["gathered"]["step"] == 7
+
+
+def test_rank_group_views_of_designed_models_own_their_rank_form_only():
+    """A rank group of two of the designed (5, 6, 4) cascades (tests/golden/make_golden_stages.py: tree shapes with dummy
+    splits; NaN, infinite and duplicate thresholds): a member view is the group's to free -- wb_model_destroy refuses it --,
+    has the group's one-byte rank form, no two-byte one and no specialised kernel, and scans a 64 x 64 image to what the
+    oracle gives; then the group goes, then its models."""
+    import ctypes as C
+    import waldboost_amd as wb
+    from waldboost_amd import _native as nat
+    from waldboost_amd import engine
+    from waldboost_amd.synth import synth_image
+    from util import GOLDEN, oracle_detect
+    z = np.load(os.path.join(GOLDEN, "stage_records.npz"))
+    lib = nat.load()
+    models = []
+    for name in ("shapes", "thresholds"):
+        M = wb.Model((5, 6, 4), dict(wb.default_channel_opts))
+        off = z[f"{name}/node_off"]
+        for s in range(off.size - 1):
+            at = slice(int(off[s]), int(off[s + 1]))
+            M.append(wb.DTree(*(z[f"{name}/{k}"][at] for k in ("feature", "threshold", "left", "right", "prediction"))),
+                     float(z[f"{name}/theta"][s]))
+        models.append(M)
+    dms = [M.device_cascade() for M in models]
+    group = engine.RankGroup(dms)
+    views = [group.view(i) for i in range(2)]
+    for v in views:
+        assert lib.wb_model_destroy(v.handle) == nat.WB_ERR_INVALID
+        assert nat.last_error() == "wb_model_destroy: this handle is a member view of a rank group (wb_rankgroup_destroy frees it)"
+        info = nat.WbModelInfo()
+        nat.check(lib.wb_model_info(v.handle, C.byref(info)), "wb_model_info")
+        assert (info.rank_ok, info.rank16_ok, info.specialized) == (1, 0, 0)
+    img = synth_image(64, 64, 5)
+    shrink, n_per_oct, smooth, spec = wb.channels.read_opts(models[0].channel_opts)
+    eng = engine.get_engine(64, 64, img.dtype, shrink, n_per_oct, smooth, 1, channels=spec)
+    eng.load_images(img)
+    eng.run_channels(rank_dm=views[0], floats=False)
+    found = 0
+    for M, v in zip(models, views):
+        res, ref = M.scan_engine(eng, view=v), oracle_detect(M, img)
+        assert np.array_equal(res["alive"], ref["alive"])
+        assert np.array_equal(res["level"], ref["level"]) and np.array_equal(res["r"], ref["r"]) and np.array_equal(res["c"], ref["c"])
+        assert np.array_equal(res["scores"].view(np.uint32), ref["scores"].view(np.uint32))
+        found += ref["scores"].size
+    assert found > 0
+    nat.check(lib.wb_rankgroup_destroy(group.handle), "wb_rankgroup_destroy")
+    group.handle = None
+    for dm in dms:
+        nat.check(lib.wb_model_destroy(dm.handle), "wb_model_destroy")
+        dm.handle = None

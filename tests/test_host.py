@@ -169,6 +169,103 @@ def test_finishing_entry_points_refuse_what_the_sort_key_cannot_hold_with_one_me
         assert tails[0] == f"{levels} levels of up to {rows} x {cols} windows, {out_cap} records do not fit the 10/14/14/26-bit key"
 
 
+# ------------------------------------------------------------------------------ stage records (wb_model_create's host work)
+STAGE_FORMS = ("f32", "u8", "rank8", "rank16")          # the dump's order: bit f of its mask = form f
+STAGE_EXPECT = {"shapes": (15, 3), "thresholds": (15, 2), "cluster": (11, 3), "long": (11, 3), "c3": (3, 2), "c10": (3, 2),
+                "lds": (3, 2), "generic": None}         # (mask, depth) each designed model stands for; None: no records
+
+
+def stage_model(z, name):
+    keys = ("window", "node_off", "feature", "threshold", "left", "right", "prediction", "theta")
+    return {k: np.ascontiguousarray(z[f"{name}/{k}"]) for k in keys}
+
+
+def rank_records_mirror(model, n_records, SD, D, elem_bytes):
+    """The stage records of a rank form (wb_common.h: off[NI] | thr[NI] | pred[NL] | theta, BFS complete tree) rebuilt
+    from the model arrays with NumPy: offsets into the interleaved tile [row][pitch = 64 + n][C] of elem_bytes elements,
+    threshold words = the index among the channel's distinct non-NaN thresholds (-1: NaN)."""
+    (m, n, Cc), node_off, thr, left = model["window"], model["node_off"], model["threshold"], model["left"]
+    feat = model["feature"].reshape(-1, 3).astype(np.int64)
+    pitch, NI, NL = 64 + int(n), (1 << D) - 1, 1 << D
+    split = (left >= 0) & ~np.isnan(thr)
+    S = [np.unique(thr[split & (feat[:, 2] == c)]) for c in range(4)]
+    out = np.zeros((n_records, SD), np.int32)
+    out[:, 2 * NI + NL] = np.array([-np.inf], np.float32).view(np.int32)[0]              # (the trailing no-op records keep it)
+    for s in range(model["theta"].size):
+        o, rec = int(node_off[s]), out[s]
+
+        def fill(node, ci, d):
+            if d == D:
+                rec[2 * NI + ci - NI] = model["prediction"][o + node:o + node + 1].view(np.int32)[0]
+                return
+            l, r = int(left[o + node]), int(model["right"][o + node])
+            if l < 0:                                      # a leaf above depth D: dummy split, offset 0, threshold 0
+                l = r = node
+            else:
+                fr, fc, ch = feat[o + node]
+                t = thr[o + node]
+                rec[ci] = ((fr * pitch + fc) * Cc + ch) * elem_bytes
+                rec[NI + ci] = -1 if np.isnan(t) else int(np.searchsorted(S[ch], t, "left"))
+            fill(l, 2 * ci + 1, d + 1)
+            fill(r, 2 * ci + 2, d + 1)
+
+        fill(0, 0, 0)
+        rec[2 * NI + NL] = model["theta"][s:s + 1].view(np.int32)[0]
+    return out.reshape(-1)
+
+
+def test_stage_records_are_byte_identical_to_the_recorded_ones(tmp_path):
+    """wb_model_create on designed cascades, each the smallest that takes one branch of the canonicalisation
+    (tests/golden/make_golden_stages.py), with WB_DUMP_STAGES set: the float32, uint8 and rank8 tables equal, byte for
+    byte, what the library wrote before the model handle was reorganised (tests/golden/stage_records.npz); the rank16
+    table, which that version did not dump, equals a NumPy mirror of the record layout -- and so does the recorded rank8
+    table.  The dump is complete before the first device call, so this runs without a GPU (the call then ends in
+    WB_ERR_HIP)."""
+    import sys
+    sys.path.insert(0, GOLDEN)
+    from make_golden_stages import create, read_dump
+    z = np.load(os.path.join(GOLDEN, "stage_records.npz"))
+    lib = nat.load()
+    # the fixture itself first: every model is the case it was designed to be
+    assert {k.split("/")[0] for k in z.files} == set(STAGE_EXPECT)
+    for name, want in STAGE_EXPECT.items():
+        if want is None:
+            assert f"{name}/hdr" not in z.files and z[f"{name}/info"].tolist() == [1, 4, 4, 64, 0]    # 1 stage of depth 4, 4 x 64 tile, no LDS
+            continue
+        model, hdr = stage_model(z, name), z[f"{name}/hdr"]
+        assert (int(z[f"{name}/mask"]), int(hdr[2])) == want, name
+        assert [f for f in STAGE_FORMS[:3] if f"{name}/{f}" in z.files] == [f for k, f in enumerate(STAGE_FORMS[:3]) if want[0] >> k & 1]
+        G = 2 if hdr[2] >= 3 else 4
+        assert hdr[0] == model["theta"].size + G and hdr[1] == {1: 4, 2: 12, 3: 24}[int(hdr[2])]
+        if want[0] >> 2 & 1:
+            assert np.array_equal(z[f"{name}/rank8"], rank_records_mirror(model, hdr[0], hdr[1], hdr[2], 1)), name
+    assert z["lds/info"][2] == 8 and z["shapes/info"][2] == 32               # the LDS budget halved the rows per wave twice
+    thr = z["thresholds/threshold"]
+    assert np.isnan(thr).any() and np.isinf(thr).sum() >= 2 and (np.signbit(thr) & (thr == 0)).any() and (thr == 1e30).any()
+    assert np.isneginf(z["shapes/theta"]).any()
+    # the library, as it is now
+    for name, want in STAGE_EXPECT.items():
+        model, path = stage_model(z, name), str(tmp_path / (name + ".bin"))
+        rc, h = create(lib, model, path)
+        assert rc in (0, nat.WB_ERR_HIP), (name, lib.wb_last_error())
+        if rc == 0:
+            info = nat.WbModelInfo()
+            nat.check(lib.wb_model_info(h, C.byref(info)), "wb_model_info")
+            assert [info.n_stages, info.depth, info.tile_rows, info.tile_cols, info.lds_bytes] == z[f"{name}/info"].tolist(), name
+            assert want is None or 3 | info.rank_ok << 2 | info.rank16_ok << 3 == want[0], name
+            nat.check(lib.wb_model_destroy(h), "wb_model_destroy")
+        if want is None:
+            assert not os.path.exists(path)
+            continue
+        hdr, mask, tables = read_dump(path)
+        assert hdr.tolist() == z[f"{name}/hdr"].tolist() and mask == want[0], (name, hdr, mask)      # records, stage_dwords, depth
+        for k, form in enumerate(STAGE_FORMS[:3]):
+            if mask >> k & 1:
+                assert tables[k].tobytes() == z[f"{name}/{form}"].tobytes(), (name, form)
+        if mask >> 3 & 1:
+            assert np.array_equal(tables[3], rank_records_mirror(model, hdr[0], hdr[1], hdr[2], 2)), name
+
+
 def test_compute_entry_points_fail_loudly_without_a_gpu():
     import torch
     if torch.cuda.is_available():

@@ -326,17 +326,18 @@ extern "C" int wb_cascade_launch_z(void *stream, const WbModel *model, const voi
                "wb_cascade_launch: channel dtype %d (float32, uint8 or ranks)", chn_dtype);
     CascArgs a;
     a.chn = chn;
-    a.chn_u8 = chn_dtype == WB_DTYPE_F32 ? 0 : (chn_dtype == WB_DTYPE_RANK16 ? 2 : 1);      // element bytes of a byte tile
+    const int form = wb_tile_form(chn_dtype);
+    const WbFormRecords &rec = model->form[form];
+    a.chn_u8 = wb_form_elem_bytes(form);                     // element bytes of a byte tile
     a.chn_stride = chn_stride;
     a.levels = levels;
     a.tiles = tiles;
     a.n_levels = n_levels;
     // WB_DTYPE_RANK8: the bytes are threshold ranks of this model (wb_channels_launch wrote them): the uint8 tile
     // kernel with the rank records
-    const bool ranks = chn_dtype == WB_DTYPE_RANK8, ranks16 = chn_dtype == WB_DTYPE_RANK16;
-    WB_REQUIRE(!ranks || (model->bin_ok && !model->generic), "wb_cascade_launch: this model has no rank tables (wb_model_info: rank_ok)");
-    WB_REQUIRE(!ranks16 || (model->bin16_ok && !model->generic), "wb_cascade_launch: this model has no 16-bit rank tables (wb_model_info: rank16_ok)");
-    a.stages = ranks16 ? model->stages_bin16_dev : ranks ? model->stages_bin_dev : (a.chn_u8 ? model->stages_u8_dev : model->stages_dev);
+    WB_REQUIRE(form != WB_FORM_RANK8 || rec.present, "wb_cascade_launch: this model has no rank tables (wb_model_info: rank_ok)");
+    WB_REQUIRE(form != WB_FORM_RANK16 || rec.present, "wb_cascade_launch: this model has no 16-bit rank tables (wb_model_info: rank16_ok)");
+    a.stages = rec.stages_dev;
     a.T = model->n_stages;
     a.m = model->m;
     a.n = model->n;
@@ -366,9 +367,9 @@ extern "C" int wb_cascade_launch_z(void *stream, const WbModel *model, const voi
         WB_HIP_CHECK(hipGetLastError());
         return WB_OK;
     }
-    const size_t lds = (size_t)(ranks16 ? model->lds_bytes_u16 : a.chn_u8 ? model->lds_bytes_u8 : model->lds_bytes) + env.xlds;
+    const size_t lds = (size_t)rec.lds_bytes + env.xlds;
     // the model-specialised kernel, when wb_model_specialize has built one for this kind of byte tile
-    if (void *jf = a.chn_u8 && !env.jit_off && !model->jit_off ? (ranks16 ? model->jit_bin16 : ranks ? model->jit_bin : model->jit_u8) : nullptr) {
+    if (void *jf = !env.jit_off && !model->jit_off ? rec.jit : nullptr) {
         const int32_t *stages = a.stages;
         void *params[] = {&a, &stages};
         WB_HIP_CHECK(hipModuleLaunchKernel((hipFunction_t)jf, grid.x, grid.y, 1, (unsigned)model->waves * 64, 1, 1, (unsigned)lds, st,

@@ -38,7 +38,7 @@ struct ChanArgs {
     uint8_t *rank;       // [u][v][4] bytes per level, same element offsets as chn; nullptr = none
     int64_t rank_stride;
     const WbTilePatch *patches;   // optional (uint8 images): per tile, the source patch it stages (wb_channels_tile_patches)
-    const uint4 *rank_lut;   // WbModel::bin_lut_dev: float S[4][256], then uint8 base[4][WB_BIN_CELLS]
+    const uint4 *rank_lut;   // WbRankTable::lut_dev: float S[4][256], then uint8 base[4][WB_BIN_CELLS]
     int rank_iters;
     float rank_k[4], rank_b[4];
     int rank_wide;       // 0: WB_DTYPE_RANK8 (one dword per pixel), 1: WB_DTYPE_RANK16 (uint16 x 4 = 8 bytes per pixel; WB_BIN16_* tables)

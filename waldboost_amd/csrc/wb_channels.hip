@@ -725,13 +725,14 @@ extern "C" int wb_channels_launch_x(void *stream, const void *img, int64_t img_s
     WB_REQUIRE(img && levels && tiles && minmax && taps && (chn || rank), "wb_channels_launch: null pointer");
     WB_REQUIRE(!rank == !rank_model, "wb_channels_launch: rank and rank_model go together");
     WB_REQUIRE(!rank || rank_dtype == WB_DTYPE_RANK8 || rank_dtype == WB_DTYPE_RANK16, "wb_channels_launch_x: rank_dtype %d (WB_DTYPE_RANK8 or WB_DTYPE_RANK16)", rank_dtype);
-    const bool wide = rank && rank_dtype == WB_DTYPE_RANK16;
-    WB_REQUIRE(!wide || rank_model->bin16_ok, "wb_channels_launch_x: this model has no 16-bit rank tables (wb_model_info: rank16_ok)");
+    const int rank_form = rank ? wb_tile_form(rank_dtype) : -1;
+    const bool wide = rank_form == WB_FORM_RANK16;
+    WB_REQUIRE(!wide || rank_model->form[WB_FORM_RANK16].present, "wb_channels_launch_x: this model has no 16-bit rank tables (wb_model_info: rank16_ok)");
     WB_REQUIRE(!wide || reinterpret_cast<uintptr_t>(rank) % 8 == 0, "wb_channels_launch_x: 16-bit ranks must be 8-byte aligned");
     WB_REQUIRE(!patches || (dtype == WB_DTYPE_U8 && channel_func != WB_CHN_GRAD_MAG),
                "wb_channels_launch_x: the patch table goes with uint8 images and the gradient-histogram kernels");
     WB_REQUIRE(!rank || channel_func == WB_CHN_GRAD_HIST, "wb_channels_launch: ranks are written for grad_hist channels only");
-    WB_REQUIRE(!rank || wide || rank_model->bin_ok, "wb_channels_launch: this model has no rank tables (wb_model_info: rank_ok)");
+    WB_REQUIRE(!rank || wide || rank_model->form[WB_FORM_RANK8].present, "wb_channels_launch: this model has no rank tables (wb_model_info: rank_ok)");
     WB_REQUIRE(!rank || reinterpret_cast<uintptr_t>(rank) % 4 == 0, "wb_channels_launch: rank must be 4-byte aligned");
     WB_REQUIRE(cs_sn || channel_func != WB_CHN_GRAD_HIST, "wb_channels_launch: grad_hist needs the orientation constants");
     WB_REQUIRE(batch >= 1 && n_levels >= 1 && n_tiles >= 1, "wb_channels_launch: empty launch");
@@ -758,11 +759,12 @@ extern "C" int wb_channels_launch_x(void *stream, const void *img, int64_t img_s
     a.patches = patches;
     a.rank_wide = wide ? 1 : 0;
     if (rank) {
-        a.rank_lut = reinterpret_cast<const uint4 *>(wide ? rank_model->bin16_lut_dev : rank_model->bin_lut_dev);
-        a.rank_iters = wide ? rank_model->bin16_iters : rank_model->bin_iters;
+        const WbRankTable &rt = wb_rank_table(rank_model, rank_form);
+        a.rank_lut = reinterpret_cast<const uint4 *>(rt.lut_dev);
+        a.rank_iters = rt.iters;
         for (int k = 0; k < 4; ++k) {
-            a.rank_k[k] = wide ? rank_model->bin16_k[k] : rank_model->bin_k[k];
-            a.rank_b[k] = wide ? rank_model->bin16_b[k] : rank_model->bin_b[k];
+            a.rank_k[k] = rt.k[k];
+            a.rank_b[k] = rt.b[k];
         }
     }
     if (cs_sn) set_constants(a, cs_sn);

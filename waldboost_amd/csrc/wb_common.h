@@ -6,12 +6,11 @@
 #include <stdarg.h>
 
 #include "../../include/waldboost_hip.h"
+#include "wb_stage_records.h"   // tile forms, cascade geometry constants, the stage record, host canonicalisation
 
 #define WB_WAVE 64
 
-// ---- error plumbing (thread-local message, never throws across the ABI) ----
-void wb_set_error(const char *fmt, ...);
-
+// ---- error plumbing: wb_set_error and WB_REQUIRE are in wb_stage_records.h (no HIP in them) ----
 #define WB_HIP_CHECK(expr)                                                             \
     do {                                                                               \
         hipError_t _e = (expr);                                                        \
@@ -19,14 +18,6 @@ void wb_set_error(const char *fmt, ...);
             wb_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
             return WB_ERR_HIP;                                                         \
         }                                                                              \
-    } while (0)
-
-#define WB_REQUIRE(cond, ...)            \
-    do {                                 \
-        if (!(cond)) {                   \
-            wb_set_error(__VA_ARGS__);   \
-            return WB_ERR_INVALID;       \
-        }                                \
     } while (0)
 
 // ---- order-preserving uint32 keys for min/max atomics ----
@@ -66,33 +57,27 @@ __device__ inline double wb_round_f16(double x) {
     return (double)(float)(_Float16)f;
 }
 
-// ---- cascade geometry ----
-#define WB_CASC_TC 64        // windows per tile row = one per lane
-#define WB_CASC_MAX_DEPTH 3
-#define WB_BIN_MAX 254       // distinct thresholds per channel a binned tile can rank in one byte: ranks 0..254, 255 = NaN
-                             // pixel; S[254] and S[255] of a channel's table are then always the +inf padding, so the
-                             // channel kernel may read S[r] and S[r + 1] together for every rank r <= 254
-#define WB_BIN_SLOTS 256     // entries of a channel's sorted threshold table
-#define WB_BIN_CELLS 2048    // cells of a channel's lookup grid
-#define WB_BIN_LUT_BYTES (4 * WB_BIN_SLOTS * 4 + 4 * WB_BIN_CELLS)   // float S[4][256], then uint8 base[4][N]
-// ... and in two bytes (WB_DTYPE_RANK16): cascades with more distinct thresholds per channel than a byte ranks -- long soft
-// cascades (reference __init__.py:230-269 appends stages without bound), deep trees.  The tables still live in LDS while
-// a channel tile is ranked, so the count is bounded by that: 1020 thresholds per channel (S[1020..1023] = +inf padding: the
-// channel kernel reads S[r .. r + 3] together), 512 grid cells with 16-bit base counts = 20 KiB.
-#define WB_BIN16_MAX 1020
-#define WB_BIN16_SLOTS 1024
-#define WB_BIN16_CELLS 512
-#define WB_BIN16_LUT_BYTES (4 * WB_BIN16_SLOTS * 4 + 4 * WB_BIN16_CELLS * 2)   // float S[4][1024], then uint16 base[4][512]
+// One tile form of a model (WbTileForm): its stage records and the tile kernel's needs for them
+struct WbFormRecords {
+    int present;            // 1 = the model can be scanned in this form (the rank forms: its thresholds fit the tables)
+    int owned;              // 1 = the two stage tables are this handle's to free (0: a member view sharing its model's)
+    int32_t *stages_dev;    // (n_stages + G) stage records
+    int32_t *stages_host;   // the byte forms: host copy the generator of the specialised kernel bakes in
+    int lds_bytes;          // dynamic LDS of the tile kernel
+    int elem_bytes;         // wb_form_elem_bytes
+    void *jit;              // model-specialised kernel (wb_jit.hip, wb_model_specialize): hipFunction_t, or null; always the handle's own
+    int refused;            // 1 = its specialised kernel failed the self-test, no retry
+};
 
-// The canonical stage record the cascade kernels read with scalar loads:
-//   int   off[NI]   LDS byte offset of each internal node's feature (BFS order)
-//   float thr[NI]
-//   float pred[NL]  leaf predictions, left to right
-//   float theta
-// NI = 2^D - 1, NL = 2^D; padded to WB_STAGE_DWORDS(D) dwords.
-#define WB_STAGE_NI(D) ((1 << (D)) - 1)
-#define WB_STAGE_NL(D) (1 << (D))
-#define WB_STAGE_DWORDS(D) ((((2 * WB_STAGE_NI(D) + WB_STAGE_NL(D) + 1) + 3) / 4) * 4)
+// Threshold ranks of float32 channel values (written by the channel kernel, scanned by the byte-tile cascade kernels): per
+// channel the model's distinct thresholds are sorted, a pixel is replaced by the number of them below it (its rank), and a
+// node test `v <= thr` becomes `rank(v) <= index(thr)` -- the same decision for every float, in a quarter or half of the bytes
+struct WbRankTable {
+    int iters;              // K: most thresholds that share one cell of the lookup grid (refinement steps per pixel)
+    float k[4], b[4];       // cell(v) = trunc(clamp(fma(v, k[c], b[c]), 0, cells - 1))
+    uint8_t *lut_dev;       // float S[4][slots] (sorted thresholds, +inf padded), then base[4][cells]: WB_BIN_* / WB_BIN16_*
+    int owned;              // 1 = lut_dev is this handle's to free (0: a member view: the group's)
+};
 
 struct WbModel {
     int n_stages, depth, m, n, C;
@@ -101,44 +86,19 @@ struct WbModel {
     int tile_rows;    // = rpw * waves
     int lds_rows;     // tile_rows + m - 1
     int lds_pitch;    // WB_CASC_TC + n - 1 pixels + 1 pad column
-    int lds_bytes;
     int lds_stages;   // stage records mirrored in LDS (n_stages if the table is <= 16 KiB, else 0)
     int stage_dwords;
-    int32_t *stages_dev;        // (n_stages + G) stage records with LDS byte offsets (planar float32 tile)
-    int32_t *stages_u8_dev;     // the same for uint8 channels: offsets into the interleaved byte tile, integer thresholds
-    int lds_bytes_u8;           // dynamic LDS of the kernel on uint8 channels
-    // float32 channels as threshold RANKS (written by the channel kernel, scanned by the uint8 cascade tile): per
-    // channel the model's distinct thresholds are sorted, a pixel is replaced by the number of them below it (its
-    // rank, one byte), and a node test `v <= thr` becomes `rank(v) <= index(thr)` -- the same decision for every
-    // float, in a quarter of the bytes
-    int bin_ok;                 // 1 = every channel has <= WB_BIN_MAX distinct thresholds and the tables fit
-    int bin_cells;              // N: cells of the linear lookup grid per channel
-    int bin_iters;              // K: most thresholds that share one cell (refinement steps per pixel)
-    float bin_k[4], bin_b[4];   // cell(v) = trunc(clamp(fma(v, k[c], b[c]), 0, N - 1))
-    int bin_lut_vec;            // size of the table block in 16-byte units
-    uint8_t *bin_lut_dev;       // float S[4][256] (sorted thresholds, +inf padded), then uint8 base[4][N]
-    int32_t *stages_bin_dev;    // stage records for the binned tile: byte-tile offsets, thresholds = ranks
-    // the same with 16-bit ranks (WB_DTYPE_RANK16): up to WB_BIN16_MAX distinct thresholds per channel
-    int bin16_ok, bin16_iters;
-    float bin16_k[4], bin16_b[4];
-    uint8_t *bin16_lut_dev;     // float S[4][WB_BIN16_SLOTS], then uint16 base[4][WB_BIN16_CELLS]
-    int32_t *stages_bin16_dev;  // stage records for the 16-bit tile [rows][pitch][C] x 2 bytes: byte offsets, thresholds = ranks
-    int32_t *stages_bin16_host;
-    int lds_bytes_u16;          // dynamic LDS of the kernel on the 16-bit tile
-    void *jit_bin16;
+    size_t stage_words;                   // (n_stages + G) * stage_dwords: words of every form's stage table
+    WbFormRecords form[WB_FORM_COUNT];    // none present on a generic model
+    WbRankTable ranks[2];                 // of WB_FORM_RANK8 and WB_FORM_RANK16 (wb_rank_table)
+    int jit_off;                // 1 = wb_cascade_launch ignores the loaded specialised kernels (wb_model_use_specialized)
+    int proxy;                  // 1 = a member view of a WbRankGroup: everything below is its model's
     // host copy of the caller's tree arrays (wb_rankgroup_create derives stage records for a shared rank table from them)
     int n_nodes;
     int32_t *h_node_off;        // [n_stages + 1]
     uint8_t *h_feature;         // [n_nodes][3]
     float *h_threshold, *h_prediction, *h_theta;
     int8_t *h_left, *h_right;
-    int proxy;                  // 1 = a member view of a WbRankGroup: shares every pointer but the rank tables with its model
-    // model-specialised kernels (wb_jit.hip, wb_model_specialize): hipFunction_t per byte-tile stage table, or null
-    int32_t *stages_u8_host, *stages_bin_host;   // host copies of the two byte-tile tables the generator bakes in
-    size_t stage_words;                          // (n_stages + G) * stage_dwords
-    void *jit_u8, *jit_bin;
-    int jit_off;                // 1 = wb_cascade_launch ignores the loaded specialised kernels (wb_model_use_specialized)
-    int jit_refused;            // bit per byte-tile kind (1 uint8, 2 ranks, 4 16-bit ranks): its specialised kernel failed the self-test, no retry
     // trees deeper than WB_CASC_MAX_DEPTH: generic node-walk kernel on the reference's own flat arrays
     int generic;                // 1 = use cascade_generic_kernel
     int32_t *g_node_off;        // [n_stages + 1]
@@ -148,6 +108,7 @@ struct WbModel {
     float *g_pred;              // [n_nodes]
     float *g_theta;             // [n_stages]
 };
+inline const WbRankTable &wb_rank_table(const WbModel *model, int form) { return model->ranks[form - WB_FORM_RANK8]; }
 
 // ---- the tile kernel's host side (wb_cascade.hip), as wb_model_create needs it ----
 int wb_cascade_prepare(int depth, int rpw, int waves);  // the instances' dynamic-LDS limit raised; WB_ERR_UNSUPPORTED: no kernel for this shape
@@ -155,8 +116,14 @@ int wb_cascade_group(int depth);                        // stages evaluated per 
 int wb_cascade_lds_bytes(int eb, int C, int rows, int pitch, int TR, int waves, int T, int lds_stages,
                          int depth);                    // dynamic LDS of the tile kernel
 
-// ---- threshold ranks of float32 channel values (WbModel::bin_*, WB_DTYPE_RANK8) ----
-// cell of a channel's lookup grid (host mirror: bin_cell() in wb_api.hip): non-decreasing in v
+// ---- model-specialised kernels (wb_jit.hip), as wb_model_specialize needs them ----
+int wb_jit_get(const int32_t *words, size_t n_words, int T, int D, int rpw, int waves, int C, int rows, int pitch, int eb,
+               int lds_stages, void **func_out);
+void wb_jit_release(void *func);
+int wb_jit_selftest(WbModel *model, int chn_dtype, WbFormRecords *rec);   // WB_ERR_UNSUPPORTED: rec->jit disagreed with the generic kernel
+
+// ---- threshold ranks of float32 channel values (WbRankTable, WB_DTYPE_RANK8) ----
+// cell of a channel's lookup grid (host mirror: bin_cell() in wb_stage_records.h): non-decreasing in v
 __device__ inline uint32_t wb_bin_cell(float v, float k, float b, float top = (float)(WB_BIN_CELLS - 1)) {
     const float q = __builtin_amdgcn_fmed3f(__builtin_fmaf(v, k, b), 0.0f, top);
     return (uint32_t)q;
