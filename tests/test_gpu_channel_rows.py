@@ -63,6 +63,31 @@ def test_every_split_of_the_bottom_tile_rows(H, W):
     check_pyramid(image("noise", H, W))
 
 
+def check_cell_pyramid(img, shrink, smooth):
+    opts = dict(shrink=shrink, n_per_oct=4, smooth=smooth)
+    got = list(wb.channels.channel_pyramid(img, dict(opts, channels=wb.channels.grad_hist)))
+    ref = list(orc.channel_pyramid(img, dict(opts, channels=orc.grad_hist)))
+    assert len(got) == len(ref)
+    for l, ((c, s), (rc, rs)) in enumerate(zip(got, ref)):
+        assert s == rs and c.shape == rc.shape
+        assert np.array_equal(bits(c), bits(rc)), (img.shape, shrink, smooth, l, c.shape)
+
+
+@pytest.mark.parametrize("shrink,smooth", [(1, 0), (1, 1), (2, 0), (4, 0), (4, 1)])
+def test_every_bottom_tile_height_in_the_other_grad_hist_cells(shrink, smooth):
+    """channels_kernel is the only kernel that trims a bottom tile's rows to its level, so every grad_hist cell splits the
+    rows of step 1 over its waves in its own way (its own tile height, halo and strip length).  The tests above walk the
+    cell of the detection path; this one walks the other five: a full top tile and a bottom tile of 1 .. TU output rows --
+    every u mod TU, with the tile shape the library reports -- at one narrow width and at one of two tile columns."""
+    from waldboost_amd import _native as nat
+    from waldboost_amd.plan import chan_tile
+    tu, tv = chan_tile(nat.WB_CHN_GRAD_HIST, shrink)
+    for u in range(tu + 1, 2 * tu + 1):
+        for v in (tv // 2 + 8, tv + 6):
+            H, W = shrink * u, shrink * v
+            check_cell_pyramid(synth_image(H, W, H + W), shrink, smooth)
+
+
 @pytest.mark.parametrize("kind", ["noise", "checkerboard", "flat_blocks"])
 @pytest.mark.parametrize("W", WIDTHS)
 @pytest.mark.parametrize("H", [36, 64])
