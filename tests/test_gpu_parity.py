@@ -11,6 +11,7 @@ import os
 import numpy as np
 import pytest
 
+import gradient_designs as gd
 import waldboost_amd as wb
 from oracle import wb_oracle as orc
 from waldboost_amd.synth import synth_image, random_tree_arrays
@@ -144,6 +145,12 @@ def test_clean_edges_hit_the_projection_leftovers():
             assert s == rs and np.array_equal(bits(c), bits(rc))
             tiny += int(((rc > 0) & (rc < 1e-6)).sum())
         assert tiny > 0, "the image no longer produces leftover values"
+    # what the image holds at level 0 (gradient_designs.classify, exact arithmetic): blocks the shrink-2 kernel redoes, and
+    # residue-only blocks in channels 1, 2, 3.  Its ramp has ONE slope, so at shrink 2 no 3 x 3 window of level 0 tells the
+    # two forms of the smooth apart -- the designed windows of test_gpu_gradient_designs.py do
+    m = gd.classify(img, 2)
+    assert int(m["redo"].sum()) == 961 and m["residue_only"].sum(axis=(0, 1)).tolist()[1:] == [81, 713, 165]
+    assert [len(np.unique(m["words"][..., k])) for k in (1, 2, 3)] == [21, 27, 22]
 
 
 @pytest.mark.parametrize("seed", [0, 1, 2, 3])
@@ -170,6 +177,12 @@ def test_low_entropy_images_mix_residues_and_ordinary_values(seed):
             assert s == rs and np.array_equal(bits(c), bits(rc))
             total_tiny += int(((rc > 0) & (rc < 1e-6)).sum())
     assert total_tiny > 0
+    # the regime in numbers (gradient_designs.classify): redone blocks of the shrink-2 kernel at level 0, distinct block
+    # words of {Z, R, O}^4 in channels 1, 2, 3
+    m = gd.classify(img, 2)
+    words = [len(np.unique(m["words"][..., k])) for k in (1, 2, 3)]
+    assert (int(m["redo"].sum()), words) == {0: (1894, [24, 43, 40]), 1: (1896, [63, 55, 48]), 2: (2149, [42, 45, 56]),
+                                             3: (2315, [54, 46, 24])}[seed]
 
 
 def test_shrink4_extension_vs_oracle():
