@@ -444,9 +444,10 @@ __global__ __launch_bounds__(256) void pool_f64_kernel(const double *src_base, i
         double v;
         if (bits > 0) {
             // each add wraps in the array's dtype; wrapping once at the end is the same residue
-            v = trunc(wrap_int(((a + b) + cc) + d, bits, sgn) / 4.0);
+            // (+ 0.0: a sum of -1 .. -3 truncates to -0.0, and an integer has one zero -- the pixel and its key are +0.0's)
+            v = trunc(wrap_int(((a + b) + cc) + d, bits, sgn) / 4.0) + 0.0;
         } else if (bits == -WB_CAST_TRUNC) {
-            v = trunc((((a + b) + cc) + d) / 4.0);          // int64 / uint64 values exact in float64: no rounding, no wrap
+            v = trunc((((a + b) + cc) + d) / 4.0) + 0.0;    // int64 / uint64 values exact in float64: no rounding, no wrap
         } else if (bits == -WB_CAST_BOOL) {
             v = (a != 0.0 || b != 0.0 || cc != 0.0 || d != 0.0) ? 1.0 : 0.0;    // bool + bool is logical or; x / 4 != 0
         } else if (bits == -WB_CAST_F16) {
