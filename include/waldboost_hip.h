@@ -44,6 +44,10 @@
  *   reference waldboost/fpga/training.py:15-57 (H, _fit_threshold, _find_split: the split search of fpga.DTree.fit) and
  *        :133-138 (the samples of a split node move to its children)
  *        -> wb_fit_level_launch, wb_fit_route_launch
+ *   reference waldboost/training.py:33-50 (DTree.fit: scikit-learn's DecisionTreeClassifier(class_weight="balanced"),
+ *        gini criterion, best splitter, on float32 samples): the sort of every feature column and the split search,
+ *        routing and re-partitioning of one tree level
+ *        -> wb_cart_sort_launch, wb_cart_level_launch
  */
 #ifndef WALDBOOST_HIP_H
 #define WALDBOOST_HIP_H
@@ -537,6 +541,50 @@ int wb_fit_level_launch(void *stream, const uint8_t *xt, int64_t n_samples, int6
 int wb_fit_route_launch(void *stream, const uint8_t *xt, int64_t n_samples, int64_t n_features, int32_t *node,
                         int level_base, int n_level, const int8_t *slot, int n_open, const WbFitSplit *splits,
                         int child_base);
+
+/* Split search of the base tree learner on float32 samples (reference training.py:33-50: scikit-learn's
+ * DecisionTreeClassifier(class_weight="balanced"), gini, best splitter).  New symbols of ABI 8 (the version number did not
+ * change: nothing that existed did).  The exact rules are stated at the head of csrc/wb_cart.hip.
+ *
+ * wb_cart_sort_launch, once per fit:
+ *   xt       dev float32 [n_features][n_samples]: the samples, FEATURE-major; finite values
+ *   order    dev int32 [n_features][n_samples], written: per feature the sample indices sorted by (value, index), -0.0
+ *            equal to +0.0
+ * n_samples <= WB_CART_MAX_SAMPLES, n_features <= WB_CART_MAX_FEATURES (WB_ERR_UNSUPPORTED beyond).  One workgroup per
+ * column, 32 KiB of LDS.
+ *
+ * wb_cart_level_launch, once per tree level: four launches (scan, best, move, part), no host synchronisation.
+ *   q        dev uint64 [n_samples], 8-byte aligned: the split weights as integers; a sum converts back as
+ *            double(sum) * scale, scale a power of two
+ *   cls      dev uint8 [n_samples]: 0 / 1
+ *   order_in dev int32 [n_features][n_samples]: every column sorted and partitioned by node: the level's open node k is
+ *            positions begin[k] .. end[k] - 1 of EVERY column (the root: 0 .. n_samples - 1 of wb_cart_sort_launch's output)
+ *   order_out dev, like order_in and not the same buffer, written: for every open node that was split, its segment with
+ *            the left child's samples first (begin[k] .. begin[k] + n_left - 1), then the right child's, each still sorted.
+ *            Other positions are not written.
+ *   node     dev int32 [n_samples], updated: a sample of a split open node k gets child_base + 2 * k (left) or
+ *            child_base + 2 * k + 1 (right); other entries stay
+ *   begin, end, t0, t1   HOST arrays [n_open]: the segments (ascending, disjoint, non-empty) and the nodes' integer class
+ *            totals (each below 2^62)
+ *   scratch  dev, 16-byte aligned, wb_cart_scratch_bytes(n_features, n_open) bytes
+ *   splits   dev WbCartSplit [n_open], 8-byte aligned: per open node the winning candidate, feature = -1 when no feature
+ *            has one (the node is a leaf and nothing of it moves).  The node routes with
+ *            double(x[feature]) <= lo / 2.0 + hi / 2.0 (lo when that sum equals hi or is infinite). */
+#define WB_CART_MAX_SAMPLES 65536
+#define WB_CART_MAX_FEATURES 65536
+typedef struct {
+    int32_t feature;    /* flat index into the (m, n, C) sample, -1: no candidate */
+    int32_t n_left;     /* p: the number of samples that go left */
+    float lo, hi;       /* xs[p - 1], xs[p] of the node's samples sorted by the feature */
+    double proxy;       /* -inf when there is no candidate */
+    double t0, t1;      /* the node's class totals, double(T) * scale */
+} WbCartSplit;          /* 40 bytes */
+int wb_cart_sort_launch(void *stream, const float *xt, int64_t n_samples, int64_t n_features, int32_t *order);
+int wb_cart_scratch_bytes(int64_t n_features, int n_open, size_t *bytes);
+int wb_cart_level_launch(void *stream, const float *xt, int64_t n_samples, int64_t n_features, const uint64_t *q,
+                         const uint8_t *cls, const int32_t *order_in, int32_t *order_out, int32_t *node, int n_open,
+                         const int32_t *begin, const int32_t *end, const uint64_t *t0, const uint64_t *t1, double scale,
+                         int min_samples_leaf, int child_base, void *scratch, size_t scratch_bytes, WbCartSplit *splits);
 
 /* Device self-test: the uint8 fast path of the orientation projection (fp32 arithmetic that is
  * proven equal to the reference's fp64 formula for integer gradients) is compared with the fp64

@@ -1,0 +1,183 @@
+"""training.DTree.fit on the GPU: every tree the reference's own fit gave (tests/golden/cart_trees.npz) bit for bit,
+random cases node by node against the NumPy statement (tests/cart_reference.py) through fit_detail, independence of the
+sample order and of the run, device-tensor inputs, the default Learner and waldboost_amd.train end to end.
+
+Without the feature the fixture, fit_stage and train tests fail (NotImplementedError, AttributeError).
+
+Nothing is tolerated anywhere: the weight sums are integers and every float64 operation of the proxy is rounded on its
+own, so the kernels and the statement compute the same bits."""
+import numpy as np
+import pytest
+
+import cart_reference as cr
+import waldboost_amd as wb
+from cart_fixture import assert_tree_equal, case, case_names
+from waldboost_amd import training
+from waldboost_amd.synth import synth_image
+
+pytestmark = pytest.mark.gpu
+
+
+def bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+@pytest.mark.parametrize("name", case_names())
+def test_fit_equals_every_reference_tree(name):
+    X0, W0, X1, W1, kw, want = case(name)
+    tree = training.DTree.fit(X0, W0, X1, W1, **kw)
+    assert isinstance(tree, training.DTree)
+    assert_tree_equal(tree, want, name)
+
+
+def assert_detail_equals_statement(X0, W0, X1, W1, kw):
+    tree, info = training.fit_detail(X0, W0, X1, W1, **kw)
+    want, nodes = cr.fit(X0, W0, X1, W1, **kw)
+    assert bytes(tree.content()) == bytes(want.content())
+    assert len(nodes) == len(info["samples"])
+    for i, n in enumerate(nodes):
+        assert np.array_equal(info["samples"][i], n["samples"]) and info["depth"][i] == n["depth"]
+        assert info["T0"][i] == n["T0"] and info["T1"][i] == n["T1"] and info["t0"][i] == n["t0"] and info["t1"][i] == n["t1"]
+        assert info["searched"][i] == ("table" in n)
+        if "table" in n:
+            assert info["kernel_t0"][i] == n["t0"] and info["kernel_t1"][i] == n["t1"]
+        assert info["flat_feature"][i] == n["feature"]
+        if n["left"] >= 0:
+            assert info["p"][i] == n["p"] == info["n_left"][i] == nodes[n["left"]]["samples"].size
+            assert info["lo"][i] == n["lo"] and info["hi"][i] == n["hi"] and info["threshold"][i] == n["threshold"]
+            assert np.float64(info["proxy"][i]).view(np.uint64) == np.float64(n["proxy"]).view(np.uint64)
+        elif "table" in n:
+            assert info["proxy"][i] == -np.inf and info["p"][i] == 0                     # searched, no candidate
+    return tree
+
+
+def random_case(seed, n0, n1, shape, grid=None, dtype=np.float32):
+    rng = np.random.default_rng(seed)
+    F = int(np.prod(shape))
+    X0, X1 = rng.random((n0, F)), rng.random((n1, F)) + 0.15 * (np.arange(F) % 5 == 0)
+    if grid:
+        X0, X1 = np.round(X0 * grid) / grid, np.round(X1 * grid) / grid
+    if dtype == np.uint8:
+        X0, X1 = np.clip(X0 * 200, 0, 255), np.clip(X1 * 200, 0, 255)
+    X0[:, 1] = 0.25                                                                       # a constant column
+    X1[:, 1] = 0.25
+    return (X0.astype(dtype).reshape((n0,) + shape), np.exp(rng.normal(0, 1.5, n0)), X1.astype(dtype).reshape((n1,) + shape),
+            np.exp(rng.normal(0, 1.5, n1)))
+
+
+@pytest.mark.parametrize("seed,n0,n1,shape,grid,dtype,kw", [
+    (1, 40, 23, (3, 3, 2), None, np.float32, dict(max_depth=4)),                          # small nodes, exact ties: the build's rule
+    (2, 300, 211, (4, 4, 2), 16, np.float32, dict(max_depth=4, min_samples_leaf=3)),      # 17 values per column
+    (3, 700, 400, (6, 6, 2), None, np.float32, dict(max_depth=3, min_samples_split=90)),
+    (4, 500, 300, (4, 4, 2), None, np.uint8, dict(max_depth=3, min_samples_leaf=10)),
+    (5, 3000, 2000, (2, 3, 2), 1024, np.float32, dict(max_depth=4, min_samples_leaf=25)),  # above the sort's chunk
+    (6, 2, 1, (1, 2, 1), None, np.float32, dict(max_depth=2)),
+])
+def test_random_cases_hold_node_by_node(seed, n0, n1, shape, grid, dtype, kw):
+    assert_detail_equals_statement(*random_case(seed, n0, n1, shape, grid, dtype), kw)
+
+
+def test_device_tensors_and_uint8_samples():
+    import torch
+    X0, W0, X1, W1 = random_case(7, 150, 90, (4, 4, 2))
+    want = training.DTree.fit(X0, W0, X1, W1, max_depth=3, min_samples_leaf=5)
+    got = training.DTree.fit(torch.from_numpy(X0).cuda(), W0, torch.from_numpy(X1).cuda(), W1, max_depth=3, min_samples_leaf=5)
+    assert bytes(got.content()) == bytes(want.content())
+    U0, _, U1, _ = random_case(8, 150, 90, (4, 4, 2), dtype=np.uint8)
+    a = training.DTree.fit(U0, W0, U1, W1, max_depth=2)
+    b = training.DTree.fit(U0.astype(np.float32), W0, U1.astype(np.float32), W1, max_depth=2)     # uint8 is widened
+    c = training.DTree.fit(torch.from_numpy(U0).cuda(), W0, torch.from_numpy(U1).cuda(), W1, max_depth=2)
+    assert bytes(a.content()) == bytes(b.content()) == bytes(c.content())
+    bad = torch.from_numpy(X0).cuda()
+    bad[3, 0, 0, 0] = float("nan")
+    with pytest.raises(ValueError):
+        training.DTree.fit(bad, W0, torch.from_numpy(X1).cuda(), W1, max_depth=2)
+    with pytest.raises(NotImplementedError):
+        training.DTree.fit(torch.from_numpy(X0).cuda().double(), W0, X1, W1, max_depth=2)
+
+
+def test_sample_order_and_run_do_not_change_the_tree():
+    """Duplicated values (a grid of 32) and weights over twelve orders of magnitude: running float sums would depend on
+    the order in which equal values arrive.  The split search's integer sums do not; the predictions are the reference's
+    NumPy sums over the whole sample array and may differ in the last float64 bit, which float32 storage absorbs here."""
+    X0, W0, X1, W1 = random_case(9, 600, 450, (4, 4, 2), grid=32)
+    rng = np.random.default_rng(99)
+    W0, W1 = 10.0 ** rng.uniform(-12, 0, 600), 10.0 ** rng.uniform(-12, 0, 450)
+    kw = dict(max_depth=4, min_samples_leaf=4)
+    first, info = training.fit_detail(X0, W0, X1, W1, **kw)
+    again, info2 = training.fit_detail(X0, W0, X1, W1, **kw)
+    assert bytes(first.content()) == bytes(again.content())
+    assert np.array_equal(info["proxy"].view(np.uint64), info2["proxy"].view(np.uint64))
+    p0, p1 = rng.permutation(600), rng.permutation(450)
+    shuffled, info3 = training.fit_detail(X0[p0], W0[p0], X1[p1], W1[p1], **kw)
+    assert bytes(first.content()) == bytes(shuffled.content())
+    assert np.array_equal(info["proxy"].view(np.uint64), info3["proxy"].view(np.uint64)) and info["T0"] == info3["T0"]
+
+
+def test_default_learner_fits_a_stage():
+    class Stages(list):
+        def append(self, weak, theta):
+            list.append(self, (weak, theta))
+
+    X0, _, X1, _ = random_case(10, 300, 200, (4, 4, 2))
+    rng = np.random.default_rng(11)
+    H0, H1 = rng.normal(-0.3, 0.5, 300), rng.normal(0.3, 0.5, 200)
+    L = training.Learner(max_depth=2)
+    assert L.wh is training.DTree
+    M = Stages()
+    loss, fpr, tpr = L.fit_stage(M, X0, H0, X1, H1)
+    weak, theta = M[0]
+    want, _ = cr.fit(X0, training.weights(H0), X1, training.weights(-H1), max_depth=2)
+    assert bytes(weak.content()) == bytes(want.content()) and len(L) == 1 and np.isfinite(loss) and 0 <= fpr <= 1 and 0 < tpr <= 1
+    with pytest.raises(NotImplementedError, match=r"Learner\(max_depth=2\)"):
+        training.Learner().fit_stage(Stages(), X0, H0, X1, H1)                            # the default carries no max_depth
+
+
+def _training_images():
+    items = []
+    for seed in range(8):
+        img = synth_image(128, 160, 100 + seed).astype(np.int32)
+        rng = np.random.default_rng(seed)
+        gt = []
+        for size, x_lo in ((24, 4), (32, 84)):
+            x, y = x_lo + int(rng.integers(0, 40)), 4 + int(rng.integers(0, 128 - size - 8))
+            img[y:y + size, x:x + size] += 90
+            gt.append([x, y, x + size, y + size])
+        items.append(dict(image=np.clip(img, 0, 255).astype(np.uint8), groundtruth_boxes=wb.Boxes(np.array(gt, "f"))))
+    return items
+
+
+def test_train_end_to_end(tmp_path):
+    np.random.seed(0)                                       # (select_candidates draws from np.random)
+    items = _training_images()
+    M = wb.Model((8, 8, 4), wb.default_channel_opts)
+    pool = wb.SamplePool(min_tp=40, min_fp=200, min_tp_iou=0.5, max_fp_iou=0.3)
+    seen = []
+
+    def capture(model, learner, stage):
+        X0, H0 = pool.get_false_positives()
+        X1, H1 = pool.get_true_positives()
+        seen.append((stage, len(model), len(learner), X0, H0, X1, H1))
+
+    with pytest.raises(NotImplementedError, match=r"Learner\(max_depth=2\)"):
+        wb.train(wb.Model((8, 8, 4), wb.default_channel_opts), items, pool=wb.SamplePool(min_tp=40, min_fp=200, min_tp_iou=0.5, max_fp_iou=0.3),
+                 length=1)
+    L = wb.train(M, items, learner=wb.Learner(max_depth=2), pool=pool, length=3, callbacks=[capture])
+    assert len(M) == 3 and len(L) == 3 and L.wh is training.DTree and [s[0] for s in seen] == [0, 1, 2]
+    for (stage, n_model, n_learner, X0, H0, X1, H1), weak in zip(seen, M.classifier):
+        assert n_model == n_learner == stage + 1 and X0.dtype == np.float32 and X0.shape[0] > 0 and X1.shape[0] > 0
+        W0, W1 = training.weights(H0), training.weights(-H1)
+        again = training.DTree.fit(X0, W0, X1, W1, max_depth=2)
+        assert bytes(again.content()) == bytes(weak.content()), stage
+        stated, _ = cr.fit(X0, W0, X1, W1, max_depth=2)
+        assert bytes(stated.content()) == bytes(weak.content()), stage
+        assert weak.depth() >= 1
+    assert wb.train(M, items, learner=L, pool=pool, length=3) is None          # long enough already
+    path = str(tmp_path / "trained.pb")
+    M.save(path)
+    K = wb.load(path)
+    assert len(K) == 3
+    for it in items[:2]:
+        a, b = M.detect_raw(it["image"]), K.detect_raw(it["image"])
+        assert np.array_equal(a["boxes"], b["boxes"]) and np.array_equal(bits(a["scores"]), bits(b["scores"]))
+        assert np.array_equal(a["level"], b["level"]) and a["scores"].size > 0

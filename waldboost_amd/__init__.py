@@ -1,7 +1,8 @@
 """waldboost_amd -- MI355X-native drop-in for the detection hot path of RomanJuranek/waldboost.
 
 Keeps the reference surface for that path (reference waldboost/__init__.py:50-72):
-``Model``, ``DTree``, ``channels.channel_pyramid``/``grad_hist``, ``load``/``save``, ``detect``.
+``Model``, ``DTree``, ``channels.channel_pyramid``/``grad_hist``, ``load``/``save``, ``detect``, and
+``train`` with ``Learner`` and ``BasicRejectionSchedule`` (reference waldboost/__init__.py:133-227).
 All compute runs in hand-written HIP kernels (csrc/) through the C ABI in
 include/waldboost_hip.h; there is no CPU fallback.
 """
@@ -9,7 +10,7 @@ from . import channels, fpga, model_pb2, samples, testing
 from .boxes import Boxes, concatenate, non_max_suppression
 from .model import Model
 from .samples import SamplePool
-from .training import DTree
+from .training import BasicRejectionSchedule, DTree, Learner
 
 __version__ = "0.1.0"
 
@@ -92,7 +93,42 @@ def detect(image, *models, channel_opts=None, response_scale=None, iou_threshold
     return out
 
 
+def train(model, training_images, learner=None, pool=None, length=64, theta_schedule=BasicRejectionSchedule(), callbacks=[],
+          logger=None):
+    """Train or continue training a detection model (reference waldboost/__init__.py:133-227): stages are appended to
+    `model` until it has `length` of them.
+
+    training_images : iterable of dicts with 'image' and 'groundtruth_boxes' (what SamplePool.update scans).
+    learner, pool : continue with these (the learner's length must agree with the model's); new ones otherwise.  The
+        default ``Learner()`` carries no ``max_depth``, which ``DTree.fit`` requires here (1 .. 4): pass
+        ``Learner(max_depth=2)``.
+    theta_schedule : callable (stage, false positive rate) -> -inf or None (estimate the rejection threshold).
+    callbacks : called as cb(model, learner, stage) after every stage.
+
+    Returns the learner (None when the model is long enough already).
+    """
+    import logging
+    logger = logger or logging.getLogger("Training")
+    if len(model) >= length:
+        return
+    learner = learner or Learner()
+    if len(model) != len(learner):
+        raise RuntimeError("Model length and learner length are not consistent")
+    if len(model) > 0:
+        logger.info(f"{len(model)} stages are already present, continuing")
+    pool = pool or SamplePool()
+    for stage in range(len(model), length):
+        pool.update(model, training_images)
+        X0, H0 = pool.get_false_positives()
+        X1, H1 = pool.get_true_positives()
+        loss, p0, p1 = learner.fit_stage(model, X0, H0, X1, H1, theta=theta_schedule(stage, learner.false_positive_rate))
+        logger.log(15, f"Stage {stage}: loss: {loss:g}, fpr: {p0:g}, tpr: {p1:g}")
+        for cb in callbacks:
+            cb(model, learner, stage)
+    return learner
+
+
 default_channel_opts = dict(shrink=2, n_per_oct=8, smooth=1, channels=channels.grad_hist)
 
 __all__ = ["Model", "DTree", "Boxes", "concatenate", "non_max_suppression", "SamplePool", "channels", "fpga", "samples", "testing", "detect", "load", "load_model", "save", "save_model",
-           "default_channel_opts"]
+           "default_channel_opts", "train", "Learner", "BasicRejectionSchedule"]

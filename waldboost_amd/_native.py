@@ -36,6 +36,11 @@ assert PATCH_DTYPE.itemsize == 16
 FIT_SPLIT_DTYPE = np.dtype([("feature", "<i4"), ("threshold", "<i4"), ("metric", "<f8"), ("t0", "<f8"), ("t1", "<f8")], align=True)   # WbFitSplit
 assert FIT_SPLIT_DTYPE.itemsize == 32
 WB_FIT_MAX_OPEN = 8
+CART_SPLIT_DTYPE = np.dtype([("feature", "<i4"), ("n_left", "<i4"), ("lo", "<f4"), ("hi", "<f4"), ("proxy", "<f8"), ("t0", "<f8"),
+                             ("t1", "<f8")], align=True)   # WbCartSplit
+assert CART_SPLIT_DTYPE.itemsize == 40
+WB_CART_MAX_SAMPLES = 65536
+WB_CART_MAX_FEATURES = 65536
 
 
 class WbModelInfo(C.Structure):
@@ -102,6 +107,10 @@ SYMBOLS = {
     "wb_fit_level_launch": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, _P, C.c_int, C.c_int, _P, C.c_int, _P, C.c_int, _P,
                                       C.c_size_t, _P]),
     "wb_fit_route_launch": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, C.c_int, C.c_int, _P, C.c_int, _P, C.c_int]),
+    "wb_cart_sort_launch": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P]),
+    "wb_cart_scratch_bytes": (C.c_int, [C.c_int64, C.c_int, C.POINTER(C.c_size_t)]),
+    "wb_cart_level_launch": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, C.c_double,
+                                       C.c_int, C.c_int, _P, C.c_size_t, _P]),
 }
 
 _lib = None

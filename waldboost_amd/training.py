@@ -4,14 +4,21 @@ learner around it (reference training.py:14-20, 99-253).
 Same constructor, attributes, proto I/O and ``predict_on_image``/``apply``/``predict``
 signatures as the reference so that ``from waldboost_amd.training import DTree`` is a drop-in;
 the evaluation runs in a HIP kernel (csrc/wb_cascade.hip: tree_eval_kernel).  ``DTree.fit``
-(sklearn training, reference training.py:33-50) is out of scope of this build: the weak learner
-that trains here is ``waldboost_amd.fpga.DTree`` (csrc/wb_fit.hip).
+(reference training.py:33-50: scikit-learn's ``DecisionTreeClassifier(class_weight="balanced")``,
+gini criterion, best splitter) trains on the GPU: the sort of every feature column and the split
+search, routing and re-partitioning of each tree level are HIP kernels (csrc/wb_cart.hip); the
+class weights, the leaf decisions, the pre-order numbering and the node predictions -- the
+reference's own NumPy expressions -- run on the host.  tests/cart_reference.py is the NumPy
+statement of what it computes.  ``waldboost_amd.fpga.DTree`` (csrc/wb_fit.hip) is the FPGA
+flavour's learner on uint8 samples.
 
 ``Learner``, ``fit_rejection_threshold``, ``BasicRejectionSchedule``, ``weights``, ``loss`` and
 ``as_features`` are the reference's host arithmetic on a pool's scores; ``Learner.fit_stage`` calls
 ``wh.fit`` and ``weak.predict``, which run on the GPU.
 """
+import ctypes as C
 import logging
+import math
 import pickle
 
 import numpy as np
@@ -99,9 +106,32 @@ class DTree:
         return b"".join([np.ascontiguousarray(getattr(self, a)).tobytes() + b"|" for a in _ARRAYS])
 
     @staticmethod
-    def fit(*args, **kwargs):
-        raise NotImplementedError("training.DTree.fit (the sklearn learner) has no kernel in this build; "
-                                  "waldboost_amd.fpga.DTree.fit trains on the GPU")
+    def fit(X0, W0, X1, W1, **kwargs):
+        """Train a decision tree on the GPU as the reference does with scikit-learn's
+        ``DecisionTreeClassifier(class_weight="balanced", **kwargs)`` (reference training.py:33-50).
+
+        X0, X1 : float32 or uint8 ndarrays or device tensors (N, m, n, C): samples of class 0 and class 1 (uint8 is
+            widened to float32, as sklearn does).  Anything else raises NotImplementedError; non-finite values raise
+            ValueError.  At most 65536 samples and 65536 features (NotImplementedError beyond).
+        W0, W1 : sample weights, finite and non-negative with a positive total per class (ValueError otherwise).
+        max_depth : required, an int 1 .. 4 (a tree level is one launch group over at most 8 open nodes); None or a larger
+            value raises NotImplementedError.
+        min_samples_leaf (default 1), min_samples_split (default 2) : ints, as in sklearn; fractions raise
+            NotImplementedError.
+        criterion="gini", splitter="best" are accepted, random_state is accepted and ignored; any other keyword raises
+            NotImplementedError.
+
+        Returns a ``DTree`` with sklearn's arrays: nodes in pre-order (left first), float32 thresholds (a node routes with
+        ``x <= threshold``), leaves with threshold -2 and children -1, and the reference's node predictions.
+
+        Stated deviations from sklearn.  (1) Ties: among candidates of exactly equal proxy the smallest flat feature index
+        wins, then the smallest position; sklearn visits the features in a random permutation and keeps the first strict
+        improvement, so its pick among exact ties depends on ``random_state``.  (2) The balanced sample weights are turned
+        into integers of 2^-k (k chosen so that their total stays below 2^62) and every sum of the split search is an
+        integer sum, where sklearn accumulates float64: the result does not depend on the order of the samples or on the
+        run, and equals sklearn's whenever the best split of every node leads by more than float64 rounding.
+        """
+        return fit_detail(X0, W0, X1, W1, **kwargs)[0]
 
     # ---- wire format (reference training.py:51-72, model.proto DTree)
     @staticmethod
@@ -184,6 +214,211 @@ class DTree:
         return d(0)
 
 
+MAX_DEPTH = 4           # a level holds at most WB_FIT_MAX_OPEN = 8 open nodes: depths 0 .. 3 are split
+_FIT_KEYS = ("max_depth", "min_samples_leaf", "min_samples_split", "criterion", "splitter", "random_state")
+
+
+def _is_tensor(x):
+    return type(x).__module__.startswith("torch")
+
+
+def _cart_check_samples(X, name):
+    if not (isinstance(X, np.ndarray) or _is_tensor(X)) or str(X.dtype).replace("torch.", "") not in ("float32", "uint8"):
+        what = str(getattr(X, "dtype", type(X).__name__)).replace("torch.", "")
+        raise NotImplementedError(f"training.DTree.fit: no kernel for {what} samples ({name}); float32 or uint8 ndarrays or "
+                                  "device tensors (N, m, n, C) are accepted")
+
+
+def _cart_int(kwargs, key, default, least):
+    v = kwargs.get(key, default)
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+        raise NotImplementedError(f"training.DTree.fit: {key} must be an int (fractions of the sample count are not built), got {v!r}")
+    if v < least:
+        raise ValueError(f"training.DTree.fit: {key} must be at least {least}, got {v}")
+    return int(v)
+
+
+def _cart_args(kwargs):
+    unknown = sorted(set(kwargs) - set(_FIT_KEYS))
+    if unknown:
+        raise NotImplementedError(f"training.DTree.fit: no kernel for the arguments {unknown}; accepted: {list(_FIT_KEYS)}")
+    if kwargs.get("criterion", "gini") != "gini" or kwargs.get("splitter", "best") != "best":
+        raise NotImplementedError('training.DTree.fit: only criterion="gini" and splitter="best" are built')
+    d = kwargs.get("max_depth")
+    if d is None or isinstance(d, bool) or not isinstance(d, (int, np.integer)) or not 1 <= d <= MAX_DEPTH:
+        raise NotImplementedError(f"training.DTree.fit: max_depth must be an int 1 .. {MAX_DEPTH} (a level of at most "
+                                  f"{nat.WB_FIT_MAX_OPEN} open nodes per launch), got {d!r}; e.g. Learner(max_depth=2)")
+    return int(d), _cart_int(kwargs, "min_samples_leaf", 1, 1), _cart_int(kwargs, "min_samples_split", 2, 2)
+
+
+def _cart_weights(W, n, name):
+    W = np.asarray(W)
+    if W.ndim != 1 or W.size != n:
+        raise ValueError(f"{name} must hold one weight per sample ({n}), got shape {W.shape}")
+    if W.dtype.kind != "f":
+        W = W.astype(np.float64)
+    if not np.all(np.isfinite(W)) or np.any(W < 0):
+        raise ValueError(f"{name} must be finite and non-negative")
+    return W
+
+
+def cart_split_weights(W, Y):
+    """(q, k): the balanced sample weights sw = W * (N / (2 * count(Y == y))) (sklearn's, on unweighted counts) as
+    integers q = rint(sw * 2^k), uint64, k the power that keeps their total below 2^62."""
+    N = Y.size
+    counts = np.bincount(Y, minlength=2)
+    with np.errstate(all="ignore"):
+        sw = W.astype(np.float64) * (N / (2.0 * counts))[Y]
+        total = math.fsum(sw) if np.all(np.isfinite(sw)) else np.inf
+    if not np.isfinite(total) or total <= 0:
+        raise ValueError("training.DTree.fit: the weights must have a finite positive total")
+    k = min(61 - math.frexp(total)[1], 1000)
+    q = np.rint(np.ldexp(sw, k)).astype(np.uint64)
+    for c in (0, 1):
+        if not int(q[Y == c].sum()) > 0:
+            raise ValueError(f"training.DTree.fit: the weights of class {c} must have a positive total")
+    return q, k
+
+
+def fit_detail(X0, W0, X1, W1, **kwargs):
+    """``DTree.fit`` with its working: returns (tree, info), info a dict with per node (pre-order id) ``samples`` (indices
+    into the concatenated class-0, class-1 samples, ascending), ``depth``, ``T0``/``T1`` (the integer class totals),
+    ``t0``/``t1`` (the same as float64), ``k`` (weights are integers of 2^-k), and for the nodes the GPU searched
+    ``flat_feature`` (-1: a leaf), ``proxy``, ``p``, ``n_left``, ``lo``, ``hi`` as the kernel wrote them (NaN / 0 / -1
+    for the others) and the float64 ``threshold``."""
+    import torch
+    _cart_check_samples(X0, "X0")
+    _cart_check_samples(X1, "X1")
+    max_depth, min_leaf, min_split = _cart_args(kwargs)
+    if len(X0.shape) != 4 or len(X1.shape) != 4:
+        raise ValueError(f"X0 and X1 must have shape (N, m, n, C), got {tuple(X0.shape)}, {tuple(X1.shape)}")
+    shape = tuple(int(s) for s in X0.shape[1:])
+    if shape != tuple(int(s) for s in X1.shape[1:]):
+        raise ValueError(f"X0 and X1 hold samples of different shapes: {shape}, {tuple(X1.shape[1:])}")
+    n0, n1 = int(X0.shape[0]), int(X1.shape[0])
+    N, F = n0 + n1, int(np.prod(shape))
+    if n0 < 1 or n1 < 1 or F < 1:
+        raise ValueError("training.DTree.fit: both classes need at least one sample")
+    W0, W1 = _cart_weights(W0, n0, "W0"), _cart_weights(W1, n1, "W1")
+    W = np.concatenate([W0, W1])
+    Y = np.array([0] * n0 + [1] * n1)
+    q, k = cart_split_weights(W, Y)
+    scale = math.ldexp(1.0, -k)
+    for X in (X0, X1):
+        if isinstance(X, np.ndarray) and X.dtype.kind == "f" and not np.all(np.isfinite(X)):
+            raise ValueError("training.DTree.fit: the samples must be finite")
+    if N > nat.WB_CART_MAX_SAMPLES or F > nat.WB_CART_MAX_FEATURES:
+        raise NotImplementedError(f"training.DTree.fit: at most {nat.WB_CART_MAX_SAMPLES} samples and {nat.WB_CART_MAX_FEATURES} "
+                                  f"features, got {N} and {F}")
+
+    lib = nat.load()
+    dev = nat.require_gpu()
+    parts = [(X if _is_tensor(X) else torch.from_numpy(np.ascontiguousarray(X))).to(dev).reshape(int(X.shape[0]), F) for X in (X0, X1)]
+    xt = torch.cat(parts).to(torch.float32).t().contiguous()          # feature-major: a column is contiguous
+    if not bool(torch.isfinite(xt).all()):
+        raise ValueError("training.DTree.fit: the samples must be finite")
+    q_d = torch.from_numpy(q.view(np.int64)).to(dev)
+    cls_d = torch.from_numpy(Y.astype(np.uint8)).to(dev)
+    node_d = torch.zeros(N, dtype=torch.int32, device=dev)
+    order = torch.empty((F, N), dtype=torch.int32, device=dev)
+    order_next = torch.empty_like(order)
+    stream = nat.stream_ptr()
+    nat.check(lib.wb_cart_sort_launch(stream, nat.ptr(xt), N, F, nat.ptr(order)), "wb_cart_sort_launch")
+
+    def new_node(samples, depth, begin):
+        y = Y[samples]
+        T0, T1 = int(q[samples[y == 0]].sum()), int(q[samples[y == 1]].sum())
+        return dict(samples=samples, depth=depth, begin=begin, T0=T0, T1=T1, t0=float(T0) * scale, t1=float(T1) * scale,
+                    feature=-1, left=-1, right=-1)
+
+    nodes = {0: new_node(np.arange(N), 0, 0)}       # by the GPU's ids: level by level
+    level = [0]
+    next_id = 1
+    for depth in range(max_depth):
+        open_ids = []
+        for nid in level:
+            nd = nodes[nid]
+            n, t0, t1 = nd["samples"].size, nd["t0"], nd["t1"]
+            with np.errstate(all="ignore"):
+                impurity = np.float64(1.0) - (np.float64(t0) * t0 + np.float64(t1) * t1) / ((np.float64(t0) + t1) * (np.float64(t0) + t1))
+            if not (n < min_split or n < 2 * min_leaf or impurity <= np.finfo(np.float64).eps):
+                open_ids.append(nid)
+        if not open_ids:
+            break
+        n_open = len(open_ids)
+        begin = np.array([nodes[i]["begin"] for i in open_ids], np.int32)
+        end = np.array([nodes[i]["begin"] + nodes[i]["samples"].size for i in open_ids], np.int32)
+        t0 = np.array([nodes[i]["T0"] for i in open_ids], np.uint64)
+        t1 = np.array([nodes[i]["T1"] for i in open_ids], np.uint64)
+        need = C.c_size_t()
+        nat.check(lib.wb_cart_scratch_bytes(F, n_open, C.byref(need)), "wb_cart_scratch_bytes")
+        scratch = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        splits_d = torch.empty(n_open * nat.CART_SPLIT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        hp = lambda a: a.ctypes.data_as(C.c_void_p)
+        nat.check(lib.wb_cart_level_launch(stream, nat.ptr(xt), N, F, nat.ptr(q_d), nat.ptr(cls_d), nat.ptr(order), nat.ptr(order_next),
+                                           nat.ptr(node_d), n_open, hp(begin), hp(end), hp(t0), hp(t1), scale, min_leaf, next_id,
+                                           nat.ptr(scratch), need.value, nat.ptr(splits_d)), "wb_cart_level_launch")
+        splits = splits_d.cpu().numpy().view(nat.CART_SPLIT_DTYPE)
+        where = node_d.cpu().numpy()
+        children = []
+        for j, nid in enumerate(open_ids):
+            s, nd = splits[j], nodes[nid]
+            nd.update(searched=True, proxy=float(s["proxy"]), p=int(s["n_left"]), n_left=int(s["n_left"]), lo=float(s["lo"]),
+                      hi=float(s["hi"]), k_t0=float(s["t0"]), k_t1=float(s["t1"]))
+            if s["feature"] < 0:
+                continue
+            lo, hi = np.float64(s["lo"]), np.float64(s["hi"])
+            thr = lo / 2.0 + hi / 2.0
+            if thr == hi or np.isinf(thr):
+                thr = lo
+            left, right = next_id + 2 * j, next_id + 2 * j + 1
+            nd.update(feature=int(s["feature"]), threshold=float(thr), left=left, right=right)
+            nodes[left] = new_node(np.flatnonzero(where == left), depth + 1, nd["begin"])
+            nodes[right] = new_node(np.flatnonzero(where == right), depth + 1, nd["begin"] + int(s["n_left"]))
+            children += [left, right]
+        level = children
+        next_id += 2 * n_open
+        order, order_next = order_next, order
+        if not level:
+            break
+
+    # sklearn's numbering: pre-order, left first (a parent's index is below its children's)
+    pre = []
+
+    def walk(g):
+        pre.append(g)
+        if nodes[g]["left"] >= 0:
+            walk(nodes[g]["left"])
+            walk(nodes[g]["right"])
+    walk(0)
+    index = {g: i for i, g in enumerate(pre)}
+    n_nodes = len(pre)
+    feature = [np.unravel_index(nodes[g]["feature"], shape) if nodes[g]["feature"] >= 0 else None for g in pre]
+    threshold = np.array([nodes[g].get("threshold", -2.0) for g in pre], np.float64)
+    left = np.array([index.get(nodes[g]["left"], -1) for g in pre])
+    right = np.array([index.get(nodes[g]["right"], -1) for g in pre])
+    # the node predictions: the reference's expressions (training.py:43-49) on the leaf each sample reached
+    leaf = np.empty(N, np.int64)
+    for g in pre:
+        if nodes[g]["left"] < 0:
+            leaf[nodes[g]["samples"]] = index[g]
+    pred = np.empty(n_nodes)
+    for n in range(n_nodes):
+        mask = leaf == n
+        w0 = (W * mask * (Y == 0)).sum() + 1e-3
+        w1 = (W * mask * (Y == 1)).sum() + 1e-3
+        pred[n] = np.log(w1 / w0) / 2
+    col = lambda key, default, dt: np.array([nodes[g].get(key, default) for g in pre], dt)
+    info = dict(samples=[nodes[g]["samples"] for g in pre], depth=col("depth", 0, np.int64), k=k,
+                T0=[nodes[g]["T0"] for g in pre], T1=[nodes[g]["T1"] for g in pre],
+                t0=col("t0", np.nan, np.float64), t1=col("t1", np.nan, np.float64),
+                kernel_t0=col("k_t0", np.nan, np.float64), kernel_t1=col("k_t1", np.nan, np.float64),
+                searched=col("searched", False, bool), flat_feature=col("feature", -1, np.int64),
+                proxy=col("proxy", np.nan, np.float64), p=col("p", 0, np.int64), n_left=col("n_left", 0, np.int64),
+                lo=col("lo", np.nan, np.float32), hi=col("hi", np.nan, np.float32), threshold=threshold)
+    return DTree(feature, threshold, left, right, pred), info
+
+
 def loss(H0, H1):
     """Exponential loss of the two score sets (reference training.py:99-102)."""
     W0 = weights(H0)
@@ -193,8 +428,8 @@ def loss(H0, H1):
 
 class Learner:
     """Training algorithm (reference training.py:105-188): fits one weak classifier and one rejection threshold per
-    stage and keeps the per-stage pass rates and losses.  The default ``wh`` is ``training.DTree``, whose ``fit`` is not
-    part of this build; ``fpga.train`` passes ``fpga.DTree``."""
+    stage and keeps the per-stage pass rates and losses.  The default ``wh`` is ``training.DTree``, whose ``fit`` needs a
+    ``max_depth`` of 1 .. 4 among the ``wh_args`` (``Learner(max_depth=2)``); ``fpga.train`` passes ``fpga.DTree``."""
 
     def __init__(self, alpha=0.1, wh=DTree, **wh_args):
         self.alpha = alpha
