@@ -73,9 +73,10 @@ def statement_winner(d, k):
     return f, p, xs[p - 1, f], xs[p, f], table[p - 1, f]
 
 
-def emulated_winner(d, k, ge=False, global_pred=False, f64_add=False):
+def emulated_winner(d, k, ge=False, global_pred=False, f64_add=False, last_f=False, last_p=False):
     """The winner of a kernel that gets the 1e-7 rule wrong: `>=` for `>`, the predecessor in the whole column instead
-    of in the node, or the add in float64."""
+    of in the node, or the add in float64; or of a reduction that prefers the larger feature or the larger position among
+    equal proxies."""
     X, Y, q, S = d["X"], d["Y"], d["q"], d["nodes"][k]
     n = S.size
     everyone = np.concatenate(d["nodes"])
@@ -94,8 +95,9 @@ def emulated_winner(d, k, ge=False, global_pred=False, f64_add=False):
                 l0, l1 = np.float64(q0[:p].sum()), np.float64(q1[:p].sum())
                 r0, r1 = np.float64(q0[p:].sum()), np.float64(q1[p:].sum())
                 m = cr.half_proxy(l0, l1) + cr.half_proxy(r0, r1)
-            if not np.isnan(m) and (best is None or m > best[0]):
-                best = (m, f, p, xs[p - 1], xs[p])
+            key = (m, f if last_f else -f, p if last_p else -p)
+            if not np.isnan(m) and (best is None or key > best[0]):
+                best = (key, f, p, xs[p - 1], xs[p])
     return None if best is None else best[1:]
 
 
@@ -187,6 +189,21 @@ def designs():
                 [None, None, None], min_leaf=2)
     d["expect"] = [exact_winner(d, k) for k in range(3)]
     out.append(d)
+
+    # an exact tie the workgroup reduction has to break: two nodes of 300 and 200 samples, columns 10, 200 and 290 count
+    # 0, 1, 2, ... within each node, class 1 (weight 7) sits on a node's first and last sample, class 0 (weight 3) between.
+    # p = 1 and p = n - 1 mirror L and R -- the same two float64 terms, added in the other order -- so six candidates per
+    # node share the best proxy: in the scan the rival position lies in another 256-position step (n = 300) or in wave 3 of
+    # the same step (n = 200), in the pick the rival features lie in wave 3 (200) and in the second turn of the strided
+    # feature loop (290).  Column 100 varies too and is worse; every other column is constant.
+    sizes, F = (300, 200), 300
+    within = np.concatenate([np.arange(n) for n in sizes])
+    X = np.full((within.size, F), 0.5, np.float32)
+    X[:, [10, 200, 290]] = within[:, None]
+    X[:, 100] = np.concatenate([(np.arange(n) * 7 + 3) % n for n in sizes])          # (7 is coprime to both sizes)
+    Y = np.concatenate([np.r_[1, np.zeros(n - 2, np.int64), 1] for n in sizes])
+    out.append(_design("tie_across_waves_steps_features", X, Y, np.where(Y == 1, 7, 3), [np.arange(300), np.arange(300, 500)],
+                       [(10, 1, F32(0.0), F32(1.0))] * 2))
     return out
 
 

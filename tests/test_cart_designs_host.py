@@ -6,7 +6,7 @@ import pytest
 
 import cart_designs as cd
 import cart_reference as cr
-from cart_fixture import case
+from tree_fixture import cart_case as case
 
 DESIGNS = {d["name"]: d for d in cd.designs()}
 
@@ -63,6 +63,23 @@ def test_designs_cover_what_they_are_named_for():
         assert p == d["min_leaf"] or d["nodes"][0].size - p == d["min_leaf"]
         free = dict(d, min_leaf=1)
         assert cd.exact_winner(free, 0)[1] in (2, 8)                                  # without the limit the pure split wins
+
+
+def test_a_reduction_that_breaks_ties_the_other_way_shows():
+    d = DESIGNS["tie_across_waves_steps_features"]
+    for k, n in enumerate((300, 200)):
+        table, _ = cr.proxy_table(d["X"], d["Y"], d["q"], d["nodes"][k], 1.0, 1)
+        best = table.max()
+        p, f = np.nonzero(table == best)                                                # (row p - 1 of the table is position p)
+        assert sorted(zip((p + 1).tolist(), f.tolist())) == [(1, 10), (1, 200), (1, 290), (n - 1, 10), (n - 1, 200), (n - 1, 290)]
+        assert n - 1 >= 256 or (n - 1) // 64 == 3                                     # another step, or wave 3 of the same one
+        assert table[:, 100].max() < best and np.isfinite(table[:, 100].max())          # an ordinary column, worse
+        assert np.flatnonzero(np.isfinite(table).any(axis=0)).tolist() == [10, 100, 200, 290]
+        assert same(cd.emulated_winner(d, k), d["expect"][k])
+        assert cd.emulated_winner(d, k, last_p=True)[:2] == (10, n - 1)
+        assert cd.emulated_winner(d, k, last_f=True)[:2] == (290, 1)
+    table, _ = cr.proxy_table(d["X"], d["Y"], d["q"], d["nodes"][0], 1.0, 1)
+    assert abs(table.max() - 894.108768035516) < 1e-9 and np.sort(table[:, 10])[-3] < 890
 
 
 def test_a_wrong_comparison_in_the_step_rule_shows():

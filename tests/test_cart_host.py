@@ -1,16 +1,20 @@
 """CPU tests of training.DTree.fit: the NumPy statement (tests/cart_reference.py) against the trees the reference's own
 fit gave (tests/golden/cart_trees.npz), the argument and dtype errors, the package's exports and the resource metadata of
 the CART kernels."""
+from functools import partial
+
 import numpy as np
 import pytest
 
 import cart_reference as cr
 import waldboost_amd as wb
-from cart_fixture import assert_tree_equal, case, case_names, fixture
+import tree_fixture
 from test_host import _kernel_scratch_sizes
 from waldboost_amd import _native as nat
 from waldboost_amd import training
 
+assert_tree_equal, case = tree_fixture.assert_tree_equal, tree_fixture.cart_case
+case_names, fixture = partial(tree_fixture.case_names, "cart"), partial(tree_fixture.fixture, "cart")
 KERNELS = ("cart_sort_kernel", "cart_scan_kernel", "cart_best_kernel", "cart_move_kernel", "cart_part_kernel")
 
 

@@ -3,16 +3,20 @@ arithmetic of the stage learner (rejection threshold, schedule, banks, weights, 
 values the reference computed (tests/golden/fit_trees.npz), and the resource metadata of the split-search kernels."""
 import logging
 import pickle
+from functools import partial
 
 import numpy as np
 import pytest
 
 import fit_reference as fr
 import waldboost_amd as wb
-from fit_fixture import assert_tree_equal, case, case_names, fixture
+import tree_fixture
 from test_host import _kernel_scratch_sizes
 from waldboost_amd import _native as nat
 from waldboost_amd import fpga, training
+
+assert_tree_equal, case = tree_fixture.assert_tree_equal, tree_fixture.fit_case
+case_names, fixture = partial(tree_fixture.case_names, "fit"), partial(tree_fixture.fixture, "fit")
 
 
 @pytest.mark.parametrize("name", case_names())

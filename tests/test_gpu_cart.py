@@ -6,16 +6,20 @@ Without the feature the fixture, fit_stage and train tests fail (NotImplementedE
 
 Nothing is tolerated anywhere: the weight sums are integers and every float64 operation of the proxy is rounded on its
 own, so the kernels and the statement compute the same bits."""
+from functools import partial
+
 import numpy as np
 import pytest
 
 import cart_reference as cr
 import waldboost_amd as wb
-from cart_fixture import assert_tree_equal, case, case_names
+import tree_fixture
 from waldboost_amd import training
 from waldboost_amd.synth import synth_image
 
 pytestmark = pytest.mark.gpu
+assert_tree_equal, case = tree_fixture.assert_tree_equal, tree_fixture.cart_case
+case_names = partial(tree_fixture.case_names, "cart")
 
 
 def bits(a):

@@ -2,6 +2,7 @@
 (tests/golden/fit_trees.npz) and against the NumPy yardstick (tests/fit_reference.py) node by node, its independence of
 the sample order, Learner.fit_stage against the reference's values, and fpga.train end to end."""
 import os
+from functools import partial
 
 import numpy as np
 import pytest
@@ -9,12 +10,14 @@ import pytest
 import fit_designs as fd
 import fit_reference as fr
 import waldboost_amd as wb
-from fit_fixture import assert_tree_equal, case, case_names, fixture
+import tree_fixture
 from waldboost_amd import fpga, training
 from waldboost_amd.fpga.training import fit_detail
 from waldboost_amd.synth import synth_image
 
 pytestmark = pytest.mark.gpu
+assert_tree_equal, case = tree_fixture.assert_tree_equal, tree_fixture.fit_case
+case_names, fixture = partial(tree_fixture.case_names, "fit"), partial(tree_fixture.fixture, "fit")
 
 
 def bits(a):

@@ -30,11 +30,13 @@
 //                     neighbour.  The workgroup walks the segment 256 positions at a time with an exclusive scan of the
 //                     two class sums (wave shuffles, then the four wave totals through LDS, a running carry across
 //                     steps), rates its candidates and reduces them to one record per (node, feature).
-//   cart_best_kernel  one workgroup per open node: the first best record over the features -> WbCartSplit.
+//   cart_best_kernel  one workgroup per open node: the first best record over the features -> WbCartSplit.  Both
+//                     reductions are wb_best_reduce (wb_best_reduce.h, shared with wb_fit.hip) under CartBest's order.
 //   cart_move_kernel  one thread per position of the open segments: the sample there moves to the node's left or right
 //                     child (node[sample] = child_base + 2 * slot + side).
 //   cart_part_kernel  one workgroup per feature: the stable partition of every split segment into left | right.
 // No accumulation crosses workgroups, no floating-point atomics; no kernel uses scratch memory.
+#include "wb_best_reduce.h"
 #include "wb_common.h"
 
 #define WB_CART_THREADS 256
@@ -164,14 +166,14 @@ struct CartBest {
     double m;
     int32_t idx, ok;
     float lo, hi;
+    __device__ static bool better(const CartBest &a, const CartBest &b) {
+        if (a.ok != b.ok) return a.ok > b.ok;
+        if (!a.ok) return false;
+        if (a.m != b.m) return a.m > b.m;
+        return a.idx < b.idx;
+    }
 };
-
-__device__ inline bool cart_better(const CartBest &a, const CartBest &b) {
-    if (a.ok != b.ok) return a.ok > b.ok;
-    if (!a.ok) return false;
-    if (a.m != b.m) return a.m > b.m;
-    return a.idx < b.idx;
-}
+static_assert(sizeof(CartBest) == 24, "CartBest is 6 dwords, no padding");
 
 __device__ inline CartBest cart_none() {
     CartBest c;
@@ -180,28 +182,6 @@ __device__ inline CartBest cart_none() {
     c.ok = 0;
     c.lo = 0.0f;
     c.hi = 0.0f;
-    return c;
-}
-
-// the best candidate of the workgroup, valid in thread 0; `part` has one entry per wave
-__device__ inline CartBest cart_reduce(CartBest c, CartBest *part) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        CartBest o;
-        o.m = __shfl_xor(c.m, off);
-        o.idx = __shfl_xor(c.idx, off);
-        o.ok = __shfl_xor(c.ok, off);
-        o.lo = __shfl_xor(c.lo, off);
-        o.hi = __shfl_xor(c.hi, off);
-        if (cart_better(o, c)) c = o;
-    }
-    const int wave = threadIdx.x / WB_WAVE;
-    __syncthreads();                            // (part may still be read from the previous reduction)
-    if (threadIdx.x % WB_WAVE == 0) part[wave] = c;
-    __syncthreads();
-    if (threadIdx.x == 0)
-        for (int w = 1; w < WB_CART_WAVES; ++w)
-            if (cart_better(part[w], c)) c = part[w];
     return c;
 }
 
@@ -269,12 +249,12 @@ __global__ __launch_bounds__(WB_CART_THREADS) void cart_scan_kernel(
                         c.ok = m == m ? 1 : 0;
                         c.lo = x_prev;
                         c.hi = x;
-                        if (cart_better(c, best)) best = c;
+                        if (CartBest::better(c, best)) best = c;
                     }
                 }
             }
         }
-        best = cart_reduce(best, part);
+        best = wb_best_reduce<WB_CART_WAVES>(best, part);
         if (tid == 0) {
             const size_t r = (size_t)k * (size_t)n_features + (size_t)f;
             rec_proxy[r] = best.ok ? best.m : -__builtin_inf();
@@ -301,9 +281,9 @@ __global__ __launch_bounds__(WB_CART_THREADS) void cart_best_kernel(const double
         c.ok = rec_p[row + f] > 0 ? 1 : 0;
         c.lo = 0.0f;
         c.hi = 0.0f;
-        if (cart_better(c, best)) best = c;
+        if (CartBest::better(c, best)) best = c;
     }
-    best = cart_reduce(best, part);
+    best = wb_best_reduce<WB_CART_WAVES>(best, part);
     if (threadIdx.x == 0) {
         WbCartSplit s;
         s.feature = best.ok ? best.idx : -1;

@@ -26,10 +26,12 @@
 //                     are kept per thread in registers and merged once with LDS min / max.  Phase 2 turns every histogram
 //                     into its inclusive prefix sum in place, phase 3 rates the 257 candidates (thread j rates t = j,
 //                     thread 0 also t = 256) and reduces them to one record (metric, t) per (node, entry of A).
-//   fit_pick_kernel   one workgroup per open node: the first best record over A -> WbFitSplit.
+//   fit_pick_kernel   one workgroup per open node: the first best record over A -> WbFitSplit.  Both argmaxes end in
+//                     wb_best_reduce (wb_best_reduce.h, shared with wb_cart.hip) under FitBest's order.
 //   fit_route_kernel  one thread per sample: a sample of an open node moves to the node's left child when
 //                     x[feature] <= t, to the right child otherwise.
 // No accumulation crosses workgroups; no kernel uses scratch memory.
+#include "wb_best_reduce.h"
 #include "wb_common.h"
 
 #define WB_FIT_THREADS 256
@@ -55,39 +57,19 @@ __device__ inline int fit_slot(const FitLevel &lv, int32_t node) {
 struct FitBest {
     double m;
     int32_t idx, rank;
+    __device__ static bool better(const FitBest &a, const FitBest &b) {
+        if (a.rank != b.rank) return a.rank > b.rank;
+        if (a.rank == 1 && a.m != b.m) return a.m > b.m;
+        return a.idx < b.idx;
+    }
 };
-
-__device__ inline bool fit_better(const FitBest &a, const FitBest &b) {
-    if (a.rank != b.rank) return a.rank > b.rank;
-    if (a.rank == 1 && a.m != b.m) return a.m > b.m;
-    return a.idx < b.idx;
-}
+static_assert(sizeof(FitBest) == 16, "FitBest is 4 dwords, no padding");
 
 __device__ inline FitBest fit_make(double m, int32_t idx) {
     FitBest c;
     c.m = m;
     c.idx = idx;
     c.rank = m != m ? 2 : 1;
-    return c;
-}
-
-// the best candidate of the workgroup, valid in thread 0; `part` has one entry per wave
-__device__ inline FitBest fit_reduce(FitBest c, FitBest *part) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        FitBest o;
-        o.m = __shfl_xor(c.m, off);
-        o.idx = __shfl_xor(c.idx, off);
-        o.rank = __shfl_xor(c.rank, off);
-        if (fit_better(o, c)) c = o;
-    }
-    const int wave = threadIdx.x / WB_WAVE;
-    __syncthreads();                            // (part may still be read from the previous reduction)
-    if (threadIdx.x % WB_WAVE == 0) part[wave] = c;
-    __syncthreads();
-    if (threadIdx.x == 0)
-        for (int w = 1; w < WB_FIT_THREADS / WB_WAVE; ++w)
-            if (fit_better(part[w], c)) c = part[w];
     return c;
 }
 
@@ -186,9 +168,9 @@ __global__ __launch_bounds__(WB_FIT_THREADS) void fit_hist_kernel(
             const double lw = (l0 + l1) / tsum, rw = (r0 + r1) / tsum;
             const double m = h_all - (lw * fit_entropy(l0 + 1e-4, l1 + 1e-4) + rw * fit_entropy(r0 + 1e-4, r1 + 1e-4));
             const FitBest c = fit_make(m, t);
-            if (fit_better(c, best)) best = c;
+            if (FitBest::better(c, best)) best = c;
         }
-        best = fit_reduce(best, part);
+        best = wb_best_reduce<WB_FIT_THREADS / WB_WAVE>(best, part);
         if (tid == 0) {
             const bool ok = f_ok && best.rank != 0;                         // (an open node holds samples, so rank != 0)
             rec_metric[(size_t)k * n_allowed + a] = ok ? best.m : -__builtin_inf();
@@ -214,9 +196,9 @@ __global__ __launch_bounds__(WB_FIT_THREADS) void fit_pick_kernel(const double *
     best.rank = 0;
     for (int a = threadIdx.x; a < n_allowed; a += WB_FIT_THREADS) {
         const FitBest c = fit_make(rec_metric[(size_t)k * n_allowed + a], a);
-        if (fit_better(c, best)) best = c;
+        if (FitBest::better(c, best)) best = c;
     }
-    best = fit_reduce(best, part);
+    best = wb_best_reduce<WB_FIT_THREADS / WB_WAVE>(best, part);
     if (threadIdx.x == 0) {
         WbFitSplit s;
         s.feature = allowed[best.idx];

@@ -5,10 +5,11 @@ What runs where:
 
 * the split search -- per open node and feature two weighted histograms, their prefix sums, the metric of every
   threshold and the two argmaxes -- and the routing of samples to child nodes are HIP kernels (csrc/wb_fit.hip,
-  ``wb_fit_level_launch`` / ``wb_fit_route_launch``), one launch group per tree level;
+  ``wb_fit_level_launch`` / ``wb_fit_route_launch``), one launch group per tree level, launched by ``_level_search``;
 * the weight normalisation (float64, the class sums correctly rounded so that they do not depend on the sample order),
   the leaf/split decision per node and the node predictions -- the reference's own NumPy expressions over the node
-  membership the GPU returns, so they are bit-equal -- run on the host;
+  membership the GPU returns, so they are bit-equal -- run on the host, around the growth loop shared with
+  ``training.DTree.fit`` (``waldboost_amd/_grow.py``: ``grow``, ``check_weights``, ``stage``, ``MAX_DEPTH``);
 * ``SamplePool.update``, ``weak.predict`` and ``model.append`` run on the GPU as before.
 
 tests/fit_reference.py is the NumPy statement of what ``DTree.fit`` computes.
@@ -20,59 +21,37 @@ import math
 import numpy as np
 
 from .. import _native as nat
+from .._grow import MAX_DEPTH, check_weights, grow, stage
 from ..samples import SamplePool
 from ..training import BasicRejectionSchedule
 from ..training import DTree as BaseDTree
 from ..training import Learner
 from .banks import BankScheduler, PixelBanks
 
-MAX_DEPTH = 4           # a level holds at most WB_FIT_MAX_OPEN = 8 nodes: depths 0 .. 3 are split
-
-
-def _is_tensor(x):
-    return type(x).__module__.startswith("torch")
-
-
-def _samples(X, name):
-    """(device tensor (N, F) uint8, N, sample shape) of an ndarray or tensor (N, m, n, C)."""
-    import torch
+def _check_samples(X, name):
+    """(N, sample shape) of an ndarray or tensor (N, m, n, C) of uint8."""
     dt = str(X.dtype).replace("torch.", "")
     if dt != "uint8":
         raise NotImplementedError(f"fpga.DTree.fit: no kernel for {dt} samples ({name}); the split search is built on "
                                   "256-bin histograms of uint8 channels")
     if len(X.shape) != 4:
         raise ValueError(f"{name} must have shape (N, m, n, C), got {tuple(X.shape)}")
-    shape = tuple(int(s) for s in X.shape[1:])
-    t = X if _is_tensor(X) else torch.from_numpy(np.ascontiguousarray(X))
-    n = int(X.shape[0])
-    return t.reshape(n, int(np.prod(shape))), n, shape
-
-
-def _weights(W, n, name):
-    W = np.asarray(W)
-    if W.ndim != 1 or W.size != n:
-        raise ValueError(f"{name} must hold one weight per sample ({n}), got shape {W.shape}")
-    if W.dtype.kind != "f":
-        W = W.astype(np.float64)
-    if not np.all(np.isfinite(W)) or np.any(W < 0):
-        raise ValueError(f"{name} must be finite and non-negative")
-    return W
+    return int(X.shape[0]), tuple(int(s) for s in X.shape[1:])
 
 
 def fit_detail(X0, W0, X1, W1, max_depth=2, min_samples_leaf=10, allowed_features=None, clip=3, quantizer=32):
     """``DTree.fit`` with its working: returns (tree, info), info a dict with per node (breadth-first id) ``samples``
     (indices into the concatenated class-0, class-1 samples, ascending), ``depth``, and for split nodes ``metric``,
     ``t0``, ``t1`` (the best metric and the node's normalised class weights as the kernel saw them; NaN on leaves)."""
-    import torch
     if not 1 <= int(max_depth) <= MAX_DEPTH:
         raise NotImplementedError(f"fpga.DTree.fit: max_depth must be 1 .. {MAX_DEPTH} (a level of at most "
                                   f"{nat.WB_FIT_MAX_OPEN} nodes per launch), got {max_depth}")
     max_depth = int(max_depth)
-    x0, n0, shape = _samples(X0, "X0")
-    x1, n1, shape1 = _samples(X1, "X1")
+    n0, shape = _check_samples(X0, "X0")
+    n1, shape1 = _check_samples(X1, "X1")
     if shape != shape1:
         raise ValueError(f"X0 and X1 hold samples of different shapes: {shape}, {shape1}")
-    W = np.concatenate([_weights(W0, n0, "W0"), _weights(W1, n1, "W1")])
+    W = np.concatenate([check_weights(W0, n0, "W0"), check_weights(W1, n1, "W1")])
     N, F = n0 + n1, int(np.prod(shape))
     Y = np.array([0] * n0 + [1] * n1)
     if allowed_features is not None:
@@ -95,61 +74,19 @@ def fit_detail(X0, W0, X1, W1, max_depth=2, min_samples_leaf=10, allowed_feature
         wq[Y == c] = wq[Y == c] / (total * 2) if total > 0 else 0.0
     q = np.rint(np.ldexp(wq, 62)).astype(np.uint64)
 
-    lib = nat.load()
-    dev = nat.require_gpu()
-    xt = torch.cat([x0.to(dev), x1.to(dev)]).t().contiguous()          # feature-major: a column is contiguous
-    q_d = torch.from_numpy(q.view(np.int64)).to(dev)
-    cls_d = torch.from_numpy(Y.astype(np.uint8)).to(dev)
-    node_d = torch.zeros(N, dtype=torch.int32, device=dev)
-    allowed_d = {}
-    stream = nat.stream_ptr()
+    def opens(nd):
+        if nd["depth"] == max_depth or nd["samples"].size < min_samples_leaf:
+            return False
+        if nd["samples"].size == 0:
+            raise ValueError("fpga.DTree.fit: cannot split an empty node (min_samples_leaf must be at least 1)")
+        return True
 
-    nodes = {0: dict(samples=np.arange(N), depth=0)}
-    level = [0]                                                         # the tree ids of the current depth
-    next_id = 1
-    for depth in range(max_depth + 1):
-        slot = np.full(len(level), -1, np.int8)
-        n_open = 0
-        for j, nid in enumerate(level):
-            nd = nodes[nid]
-            if depth == max_depth or nd["samples"].size < min_samples_leaf:
-                nd.update(feature=-1, threshold=-1, left=-1, right=-1)
-            else:
-                if nd["samples"].size == 0:
-                    raise ValueError("fpga.DTree.fit: cannot split an empty node (min_samples_leaf must be at least 1)")
-                slot[j] = n_open
-                n_open += 1
-        if n_open == 0:
-            break
-        A = allowed[depth]
-        key = id(A)
-        if key not in allowed_d:
-            allowed_d[key] = torch.from_numpy(A.astype(np.int32)).to(dev)
-        need = C.c_size_t()
-        nat.check(lib.wb_fit_scratch_bytes(A.size, n_open, C.byref(need)), "wb_fit_scratch_bytes")
-        scratch = torch.empty(need.value, dtype=torch.uint8, device=dev)
-        splits_d = torch.empty(n_open * nat.FIT_SPLIT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-        slot_p = slot.ctypes.data_as(C.c_void_p)
-        nat.check(lib.wb_fit_level_launch(stream, nat.ptr(xt), N, F, nat.ptr(q_d), nat.ptr(cls_d), nat.ptr(node_d), level[0],
-                                          len(level), slot_p, n_open, nat.ptr(allowed_d[key]), A.size, nat.ptr(scratch),
-                                          need.value, nat.ptr(splits_d)), "wb_fit_level_launch")
-        nat.check(lib.wb_fit_route_launch(stream, nat.ptr(xt), N, F, nat.ptr(node_d), level[0], len(level), slot_p, n_open,
-                                          nat.ptr(splits_d), next_id), "wb_fit_route_launch")
-        splits = splits_d.cpu().numpy().view(nat.FIT_SPLIT_DTYPE)
-        where = node_d.cpu().numpy()
-        children = []
-        for j, nid in enumerate(level):
-            if slot[j] < 0:
-                continue
-            s = splits[slot[j]]
-            left, right = next_id + 2 * int(slot[j]), next_id + 2 * int(slot[j]) + 1
-            nodes[nid].update(feature=int(s["feature"]), threshold=int(s["threshold"]), left=left, right=right,
-                              metric=float(s["metric"]), t0=float(s["t0"]), t1=float(s["t1"]))
-            for c in (left, right):
-                nodes[c] = dict(samples=np.flatnonzero(where == c), depth=depth + 1)
-                children.append(c)
-        level = children
-        next_id += 2 * n_open
+    def split(nd, s):                   # every open node splits
+        nd.update(feature=int(s["feature"]), threshold=int(s["threshold"]), metric=float(s["metric"]), t0=float(s["t0"]), t1=float(s["t1"]))
+        return {}, {}
+
+    nodes = grow(N, lambda samples, depth: dict(samples=samples, depth=depth, feature=-1, threshold=-1), opens,
+                 _level_search(X0, X1, F, Y, q, allowed), split)
 
     # the tree and the node predictions: the reference's expressions (fpga/training.py:144-171)
     n_nodes = len(nodes)
@@ -172,12 +109,51 @@ def fit_detail(X0, W0, X1, W1, max_depth=2, min_samples_leaf=10, allowed_feature
         pred = np.clip(pred, -clip, clip)
     if quantizer is not None:
         pred = np.round(quantizer * pred) / quantizer
+    col = lambda key: np.array([nodes[i].get(key, np.nan) for i in range(n_nodes)])
     info = dict(samples=[nodes[i]["samples"] for i in range(n_nodes)], depth=np.array([nodes[i]["depth"] for i in range(n_nodes)]),
-                flat_feature=np.array([nodes[i]["feature"] for i in range(n_nodes)]),
-                metric=np.array([nodes[i].get("metric", np.nan) for i in range(n_nodes)]),
-                t0=np.array([nodes[i].get("t0", np.nan) for i in range(n_nodes)]),
-                t1=np.array([nodes[i].get("t1", np.nan) for i in range(n_nodes)]))
+                flat_feature=np.array([nodes[i]["feature"] for i in range(n_nodes)]), metric=col("metric"), t0=col("t0"), t1=col("t1"))
     return BaseDTree(feature, threshold, left, right, pred), info
+
+
+def _slots(level, opened):
+    """slot[j]: the index among the open nodes of the level's j-th node, -1 for a leaf (a level's ids are consecutive:
+    every open node of the level before it split)."""
+    slot = np.full(len(level), -1, np.int8)
+    for j, nd in enumerate(opened):
+        slot[nd["id"] - level[0]["id"]] = j
+    return slot
+
+
+def _level_search(X0, X1, F, Y, q, allowed):
+    """The level search of ``fit_detail`` on the GPU (csrc/wb_fit.hip), for ``_grow.grow``: stages the samples and per level
+    launches the histograms, the pick over ``allowed[depth]`` and the routing."""
+    import torch
+    lib = nat.load()
+    dev = nat.require_gpu()
+    N = Y.size
+    xt, q_d, cls_d, node_d = stage(X0, X1, F, torch.uint8, q, Y, dev)
+    allowed_d = {}
+    stream = nat.stream_ptr()
+
+    def search(depth, level, opened, child_base):
+        n_open, base = len(opened), level[0]["id"]
+        slot = _slots(level, opened)
+        A = allowed[depth]
+        key = id(A)
+        if key not in allowed_d:
+            allowed_d[key] = torch.from_numpy(A.astype(np.int32)).to(dev)
+        need = C.c_size_t()
+        nat.check(lib.wb_fit_scratch_bytes(A.size, n_open, C.byref(need)), "wb_fit_scratch_bytes")
+        scratch = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        splits_d = torch.empty(n_open * nat.FIT_SPLIT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        slot_p = slot.ctypes.data_as(C.c_void_p)
+        nat.check(lib.wb_fit_level_launch(stream, nat.ptr(xt), N, F, nat.ptr(q_d), nat.ptr(cls_d), nat.ptr(node_d), base,
+                                          len(level), slot_p, n_open, nat.ptr(allowed_d[key]), A.size, nat.ptr(scratch),
+                                          need.value, nat.ptr(splits_d)), "wb_fit_level_launch")
+        nat.check(lib.wb_fit_route_launch(stream, nat.ptr(xt), N, F, nat.ptr(node_d), base, len(level), slot_p, n_open,
+                                          nat.ptr(splits_d), child_base), "wb_fit_route_launch")
+        return splits_d.cpu().numpy().view(nat.FIT_SPLIT_DTYPE), node_d.cpu().numpy()
+    return search
 
 
 class DTree:

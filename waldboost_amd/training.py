@@ -6,10 +6,12 @@ signatures as the reference so that ``from waldboost_amd.training import DTree``
 the evaluation runs in a HIP kernel (csrc/wb_cascade.hip: tree_eval_kernel).  ``DTree.fit``
 (reference training.py:33-50: scikit-learn's ``DecisionTreeClassifier(class_weight="balanced")``,
 gini criterion, best splitter) trains on the GPU: the sort of every feature column and the split
-search, routing and re-partitioning of each tree level are HIP kernels (csrc/wb_cart.hip); the
-class weights, the leaf decisions, the pre-order numbering and the node predictions -- the
-reference's own NumPy expressions -- run on the host.  tests/cart_reference.py is the NumPy
-statement of what it computes.  ``waldboost_amd.fpga.DTree`` (csrc/wb_fit.hip) is the FPGA
+search, routing and re-partitioning of each tree level are HIP kernels (csrc/wb_cart.hip, launched
+by ``_level_search``); the class weights, the leaf decisions, the pre-order numbering and the node
+predictions -- the reference's own NumPy expressions -- run on the host, around the growth loop
+this learner shares with the FPGA flavour's (``_grow.grow``; ``check_weights``, ``is_tensor``,
+``stage`` and ``MAX_DEPTH`` live there too).  tests/cart_reference.py is the NumPy statement of
+what it computes.  ``waldboost_amd.fpga.DTree`` (csrc/wb_fit.hip) is the FPGA
 flavour's learner on uint8 samples.
 
 ``Learner``, ``fit_rejection_threshold``, ``BasicRejectionSchedule``, ``weights``, ``loss`` and
@@ -24,6 +26,7 @@ import pickle
 import numpy as np
 
 from . import _native as nat
+from ._grow import MAX_DEPTH, check_weights, grow, is_tensor, stage
 from .compare import channel_tensor
 
 logger = logging.getLogger(__name__)
@@ -214,16 +217,11 @@ class DTree:
         return d(0)
 
 
-MAX_DEPTH = 4           # a level holds at most WB_FIT_MAX_OPEN = 8 open nodes: depths 0 .. 3 are split
 _FIT_KEYS = ("max_depth", "min_samples_leaf", "min_samples_split", "criterion", "splitter", "random_state")
 
 
-def _is_tensor(x):
-    return type(x).__module__.startswith("torch")
-
-
 def _cart_check_samples(X, name):
-    if not (isinstance(X, np.ndarray) or _is_tensor(X)) or str(X.dtype).replace("torch.", "") not in ("float32", "uint8"):
+    if not (isinstance(X, np.ndarray) or is_tensor(X)) or str(X.dtype).replace("torch.", "") not in ("float32", "uint8"):
         what = str(getattr(X, "dtype", type(X).__name__)).replace("torch.", "")
         raise NotImplementedError(f"training.DTree.fit: no kernel for {what} samples ({name}); float32 or uint8 ndarrays or "
                                   "device tensors (N, m, n, C) are accepted")
@@ -251,17 +249,6 @@ def _cart_args(kwargs):
     return int(d), _cart_int(kwargs, "min_samples_leaf", 1, 1), _cart_int(kwargs, "min_samples_split", 2, 2)
 
 
-def _cart_weights(W, n, name):
-    W = np.asarray(W)
-    if W.ndim != 1 or W.size != n:
-        raise ValueError(f"{name} must hold one weight per sample ({n}), got shape {W.shape}")
-    if W.dtype.kind != "f":
-        W = W.astype(np.float64)
-    if not np.all(np.isfinite(W)) or np.any(W < 0):
-        raise ValueError(f"{name} must be finite and non-negative")
-    return W
-
-
 def cart_split_weights(W, Y):
     """(q, k): the balanced sample weights sw = W * (N / (2 * count(Y == y))) (sklearn's, on unweighted counts) as
     integers q = rint(sw * 2^k), uint64, k the power that keeps their total below 2^62."""
@@ -286,7 +273,6 @@ def fit_detail(X0, W0, X1, W1, **kwargs):
     ``t0``/``t1`` (the same as float64), ``k`` (weights are integers of 2^-k), and for the nodes the GPU searched
     ``flat_feature`` (-1: a leaf), ``proxy``, ``p``, ``n_left``, ``lo``, ``hi`` as the kernel wrote them (NaN / 0 / -1
     for the others) and the float64 ``threshold``."""
-    import torch
     _cart_check_samples(X0, "X0")
     _cart_check_samples(X1, "X1")
     max_depth, min_leaf, min_split = _cart_args(kwargs)
@@ -299,8 +285,7 @@ def fit_detail(X0, W0, X1, W1, **kwargs):
     N, F = n0 + n1, int(np.prod(shape))
     if n0 < 1 or n1 < 1 or F < 1:
         raise ValueError("training.DTree.fit: both classes need at least one sample")
-    W0, W1 = _cart_weights(W0, n0, "W0"), _cart_weights(W1, n1, "W1")
-    W = np.concatenate([W0, W1])
+    W = np.concatenate([check_weights(W0, n0, "W0"), check_weights(W1, n1, "W1")])
     Y = np.array([0] * n0 + [1] * n1)
     q, k = cart_split_weights(W, Y)
     scale = math.ldexp(1.0, -k)
@@ -311,76 +296,32 @@ def fit_detail(X0, W0, X1, W1, **kwargs):
         raise NotImplementedError(f"training.DTree.fit: at most {nat.WB_CART_MAX_SAMPLES} samples and {nat.WB_CART_MAX_FEATURES} "
                                   f"features, got {N} and {F}")
 
-    lib = nat.load()
-    dev = nat.require_gpu()
-    parts = [(X if _is_tensor(X) else torch.from_numpy(np.ascontiguousarray(X))).to(dev).reshape(int(X.shape[0]), F) for X in (X0, X1)]
-    xt = torch.cat(parts).to(torch.float32).t().contiguous()          # feature-major: a column is contiguous
-    if not bool(torch.isfinite(xt).all()):
-        raise ValueError("training.DTree.fit: the samples must be finite")
-    q_d = torch.from_numpy(q.view(np.int64)).to(dev)
-    cls_d = torch.from_numpy(Y.astype(np.uint8)).to(dev)
-    node_d = torch.zeros(N, dtype=torch.int32, device=dev)
-    order = torch.empty((F, N), dtype=torch.int32, device=dev)
-    order_next = torch.empty_like(order)
-    stream = nat.stream_ptr()
-    nat.check(lib.wb_cart_sort_launch(stream, nat.ptr(xt), N, F, nat.ptr(order)), "wb_cart_sort_launch")
-
-    def new_node(samples, depth, begin):
+    def new_node(samples, depth, begin=0):
         y = Y[samples]
         T0, T1 = int(q[samples[y == 0]].sum()), int(q[samples[y == 1]].sum())
-        return dict(samples=samples, depth=depth, begin=begin, T0=T0, T1=T1, t0=float(T0) * scale, t1=float(T1) * scale,
-                    feature=-1, left=-1, right=-1)
+        return dict(samples=samples, depth=depth, begin=begin, T0=T0, T1=T1, t0=float(T0) * scale, t1=float(T1) * scale, feature=-1)
 
-    nodes = {0: new_node(np.arange(N), 0, 0)}       # by the GPU's ids: level by level
-    level = [0]
-    next_id = 1
-    for depth in range(max_depth):
-        open_ids = []
-        for nid in level:
-            nd = nodes[nid]
-            n, t0, t1 = nd["samples"].size, nd["t0"], nd["t1"]
-            with np.errstate(all="ignore"):
-                impurity = np.float64(1.0) - (np.float64(t0) * t0 + np.float64(t1) * t1) / ((np.float64(t0) + t1) * (np.float64(t0) + t1))
-            if not (n < min_split or n < 2 * min_leaf or impurity <= np.finfo(np.float64).eps):
-                open_ids.append(nid)
-        if not open_ids:
-            break
-        n_open = len(open_ids)
-        begin = np.array([nodes[i]["begin"] for i in open_ids], np.int32)
-        end = np.array([nodes[i]["begin"] + nodes[i]["samples"].size for i in open_ids], np.int32)
-        t0 = np.array([nodes[i]["T0"] for i in open_ids], np.uint64)
-        t1 = np.array([nodes[i]["T1"] for i in open_ids], np.uint64)
-        need = C.c_size_t()
-        nat.check(lib.wb_cart_scratch_bytes(F, n_open, C.byref(need)), "wb_cart_scratch_bytes")
-        scratch = torch.empty(need.value, dtype=torch.uint8, device=dev)
-        splits_d = torch.empty(n_open * nat.CART_SPLIT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-        hp = lambda a: a.ctypes.data_as(C.c_void_p)
-        nat.check(lib.wb_cart_level_launch(stream, nat.ptr(xt), N, F, nat.ptr(q_d), nat.ptr(cls_d), nat.ptr(order), nat.ptr(order_next),
-                                           nat.ptr(node_d), n_open, hp(begin), hp(end), hp(t0), hp(t1), scale, min_leaf, next_id,
-                                           nat.ptr(scratch), need.value, nat.ptr(splits_d)), "wb_cart_level_launch")
-        splits = splits_d.cpu().numpy().view(nat.CART_SPLIT_DTYPE)
-        where = node_d.cpu().numpy()
-        children = []
-        for j, nid in enumerate(open_ids):
-            s, nd = splits[j], nodes[nid]
-            nd.update(searched=True, proxy=float(s["proxy"]), p=int(s["n_left"]), n_left=int(s["n_left"]), lo=float(s["lo"]),
-                      hi=float(s["hi"]), k_t0=float(s["t0"]), k_t1=float(s["t1"]))
-            if s["feature"] < 0:
-                continue
-            lo, hi = np.float64(s["lo"]), np.float64(s["hi"])
-            thr = lo / 2.0 + hi / 2.0
-            if thr == hi or np.isinf(thr):
-                thr = lo
-            left, right = next_id + 2 * j, next_id + 2 * j + 1
-            nd.update(feature=int(s["feature"]), threshold=float(thr), left=left, right=right)
-            nodes[left] = new_node(np.flatnonzero(where == left), depth + 1, nd["begin"])
-            nodes[right] = new_node(np.flatnonzero(where == right), depth + 1, nd["begin"] + int(s["n_left"]))
-            children += [left, right]
-        level = children
-        next_id += 2 * n_open
-        order, order_next = order_next, order
-        if not level:
-            break
+    def opens(nd):
+        n, t0, t1 = nd["samples"].size, nd["t0"], nd["t1"]
+        if nd["depth"] == max_depth:
+            return False
+        with np.errstate(all="ignore"):
+            impurity = np.float64(1.0) - (np.float64(t0) * t0 + np.float64(t1) * t1) / ((np.float64(t0) + t1) * (np.float64(t0) + t1))
+        return not (n < min_split or n < 2 * min_leaf or impurity <= np.finfo(np.float64).eps)
+
+    def split(nd, s):
+        nd.update(searched=True, proxy=float(s["proxy"]), p=int(s["n_left"]), n_left=int(s["n_left"]), lo=float(s["lo"]),
+                  hi=float(s["hi"]), k_t0=float(s["t0"]), k_t1=float(s["t1"]))
+        if s["feature"] < 0:
+            return None
+        lo, hi = np.float64(s["lo"]), np.float64(s["hi"])
+        thr = lo / 2.0 + hi / 2.0
+        if thr == hi or np.isinf(thr):
+            thr = lo
+        nd.update(feature=int(s["feature"]), threshold=float(thr))
+        return dict(begin=nd["begin"]), dict(begin=nd["begin"] + int(s["n_left"]))
+
+    nodes = grow(N, new_node, opens, _level_search(X0, X1, F, Y, q, scale, min_leaf), split)      # by the GPU's ids: level by level
 
     # sklearn's numbering: pre-order, left first (a parent's index is below its children's)
     pre = []
@@ -417,6 +358,37 @@ def fit_detail(X0, W0, X1, W1, **kwargs):
                 proxy=col("proxy", np.nan, np.float64), p=col("p", 0, np.int64), n_left=col("n_left", 0, np.int64),
                 lo=col("lo", np.nan, np.float32), hi=col("hi", np.nan, np.float32), threshold=threshold)
     return DTree(feature, threshold, left, right, pred), info
+
+
+def _level_search(X0, X1, F, Y, q, scale, min_leaf):
+    """The level search of ``fit_detail`` on the GPU (csrc/wb_cart.hip), for ``_grow.grow``: stages the samples, sorts every
+    column once, and per level launches the scan, the pick, the routing and the re-partitioning of the sorted columns."""
+    import torch
+    lib = nat.load()
+    dev = nat.require_gpu()
+    N = Y.size
+    xt, q_d, cls_d, node_d = stage(X0, X1, F, torch.float32, q, Y, dev)
+    if not bool(torch.isfinite(xt).all()):
+        raise ValueError("training.DTree.fit: the samples must be finite")
+    orders = [torch.empty((F, N), dtype=torch.int32, device=dev) for _ in range(2)]        # sorted by value within each node: in, out
+    stream = nat.stream_ptr()
+    nat.check(lib.wb_cart_sort_launch(stream, nat.ptr(xt), N, F, nat.ptr(orders[0])), "wb_cart_sort_launch")
+    hp = lambda values, dt: np.array(values, dt).ctypes.data_as(C.c_void_p)
+
+    def search(depth, level, opened, child_base):
+        n_open = len(opened)
+        need = C.c_size_t()
+        nat.check(lib.wb_cart_scratch_bytes(F, n_open, C.byref(need)), "wb_cart_scratch_bytes")
+        scratch = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        splits_d = torch.empty(n_open * nat.CART_SPLIT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        nat.check(lib.wb_cart_level_launch(
+            stream, nat.ptr(xt), N, F, nat.ptr(q_d), nat.ptr(cls_d), nat.ptr(orders[0]), nat.ptr(orders[1]), nat.ptr(node_d), n_open,
+            hp([nd["begin"] for nd in opened], np.int32), hp([nd["begin"] + nd["samples"].size for nd in opened], np.int32),
+            hp([nd["T0"] for nd in opened], np.uint64), hp([nd["T1"] for nd in opened], np.uint64), scale, min_leaf, child_base,
+            nat.ptr(scratch), need.value, nat.ptr(splits_d)), "wb_cart_level_launch")
+        orders.reverse()
+        return splits_d.cpu().numpy().view(nat.CART_SPLIT_DTYPE), node_d.cpu().numpy()
+    return search
 
 
 def loss(H0, H1):
