@@ -123,16 +123,16 @@ def test_model_detect_replays_one_graph_per_cascade_vs_oracle(channels):
         check(M, im, ref)
     eng = next(iter(E._ENGINES.values()))
     stt = eng._casc_state(M.device_cascade())
-    assert stt.get("graph") is not None and stt["detect_calls"] >= 8
+    assert stt.graph is not None and stt.detect_calls >= 8
     # a detection buffer too small for the image: the replay reports the overflow, the buffer grows, the graph is dropped
     # and captured again against the new buffer
     assert refs[0]["scores"].size > 64
     eng.det_capacity = 64
     eng._alloc_det()
-    assert "graph" not in stt
+    assert stt.graph is None
     for im, ref in zip(imgs, refs):
         check(M, im, ref)
-    assert eng.detb.cap * nat.WB_DET_SHARDS > 64 and stt.get("graph") is not None
+    assert eng.detb.cap * nat.WB_DET_SHARDS > 64 and stt.graph is not None
     # another cascade on the same engine (one cascade resident per engine): the first one's graph goes with its state
     M2 = wb.load(os.path.join(GOLDEN, "models", MODELS[channels]))
     M2.theta = [t - 0.25 if np.isfinite(t) else t for t in M2.theta]

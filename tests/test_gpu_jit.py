@@ -211,7 +211,7 @@ def test_a_fresh_specialised_kernel_is_cross_checked_on_the_first_real_image(mon
     kind = dm.rank_dtype if dm.rank_dtype is not None else nat.WB_DTYPE_U8
     for im, ref in zip(imgs, refs):
         assert_same(M.detect_raw(im), ref)
-    assert kind in dm.specialized() and dm.live_checks_left(kind) == 0 and not dm.__dict__.get("_spec_off")
+    assert kind in dm.specialized() and dm.live_checks_left(kind) == 0 and not dm._spec_off
     # 2. a kernel that "disagrees"
     E._ENGINES.clear()
     M2 = wb.load(path)
@@ -229,7 +229,7 @@ def test_a_fresh_specialised_kernel_is_cross_checked_on_the_first_real_image(mon
     with caplog.at_level(logging.WARNING, logger=E._log.name):
         for im, ref in zip(imgs, refs):
             assert_same(M2.detect_raw(im), ref)
-    assert dm2.__dict__.get("_spec_off") is True and dm2.live_checks_left(kind) == 0
+    assert dm2._spec_off is True and dm2.live_checks_left(kind) == 0
     assert any("switched off" in r.getMessage() for r in caplog.records)
     monkeypatch.setattr(E, "sort_records", real)
     for im, ref in zip(imgs, refs):                          # the generic kernel from here on

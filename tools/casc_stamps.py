@@ -21,7 +21,7 @@ fused = e.ranks_for(dm)                      # the detection path's form: ranks 
 for _ in range(3):
     stt = e.run_cascade(dm, ranks=fused)
 torch.cuda.synchronize()
-n_wg = min(stt["n_tiles"] * B, 1 << 16)
+n_wg = min(stt.n_tiles * B, 1 << 16)
 out = (C.c_double * 7)(); life = C.c_double()
 lib.wb_debug_cascade_stamps(n_wg, out, C.byref(life))
 names = ["init+tile load+barrier", "phase A (stages 0-7) + queue", "segments to 8 + re-pack", "segments 8..", "stage-parallel tail", "epilogue barrier+atomic", "copy out"]

@@ -29,7 +29,7 @@ def chan(n, td):
 def casc(n, td):
     nat.check(e.lib.wb_cascade_launch(nat.stream_ptr(), dm.handle, nat.ptr(e.rank), nat.WB_DTYPE_RANK8, e.chn_stride, 1, nat.ptr(e.levels),
                                       p.n_levels, nat.ptr(td), n, nat.ptr(e.detb.recs), nat.ptr(e.detb.counts), e.detb.cap,
-                                      nat.ptr(stt["alive"])), "casc")
+                                      nat.ptr(stt.alive)), "casc")
 KEEP = []          # the tile tables a captured graph reads must outlive it
 def build(groups):
     parts = [(subset(ctiles, g), subset(ktiles, g)) for g in groups]

@@ -333,7 +333,7 @@ class _ShardScan:
                 eng.pack(out=self.slots[k])
                 self.hdr_d[k].copy_(self.slots[k][0])
                 if T:
-                    al = stt["alive"][:, :, :T]
+                    al = stt.alive[:, :, :T]
                     self.alive_sum[k % len(self.streams), :, :T] += al.sum(dim=0, dtype=torch.int64)
                     if self.alive_d is not None:
                         self.alive_d[lo:hi, :, :T] = al
@@ -385,6 +385,7 @@ def detect_sharded(model, images, group=None, dst=0, batch=64, per_image_alive=T
     plain sums over the images scanned; the loop this replaces is scripts/waldboost-detect.py:64-67)."""
     import torch.distributed as dist
     from ._native import DET_DTYPE
+    from .engine import alive_host
     scan = _ShardScan(model, images, batch, per_image_alive)
     b, T, plan = scan.b, scan.T, scan.plan
     if plan.n_levels == 0:
@@ -412,7 +413,7 @@ def detect_sharded(model, images, group=None, dst=0, batch=64, per_image_alive=T
     LAST_TIMING["gather_s"] = time.perf_counter() - t1
     alive = None
     if per_image_alive:
-        alive = (scan.alive_d[:, :, :T].cpu().numpy().astype(np.int64) if b else np.zeros((0, L, T), np.int64)).reshape(b, L, T)
+        alive = (alive_host(scan.alive_d, T) if b else np.zeros((0, L, T), np.int64)).reshape(b, L, T)
     mine = scan.alive_sum.sum(dim=0)[:, :T].cpu().numpy().reshape(-1) if (b and T) else np.zeros(L * T, np.int64)
     tot = reduce_alive(np.concatenate([mine, [b]]), group)
     total, n_images = tot[:-1].reshape(L, T), int(tot[-1])

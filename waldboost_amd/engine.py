@@ -10,6 +10,7 @@ csrc/*.hip.  Nothing here falls back to the CPU.
 """
 import contextlib
 import ctypes as C
+import dataclasses
 import logging
 import os
 import weakref
@@ -154,19 +155,19 @@ class DeviceCascade:
         vp = lambda a: a.ctypes.data_as(C.c_void_p)
         nat.check(lib.wb_model_create(T, vp(node_off), vp(feature), vp(threshold), vp(left), vp(right), vp(pred),
                                       vp(th), m, n, Cc, C.byref(h)), "wb_model_create")
-        self.handle = h
-        self._lib = lib
-        self._owned = True
-        self._scans = {}                 # byte-tile scans so far, per channel dtype code
-        self._jit_failed = set()
         # whose rank tables this cascade scans: its own (a RankGroup's for a member view).  An opaque token, compared by
         # identity -- never the cascade or the group itself: a self-reference (or view -> group -> views) is a cycle, and
         # a cycle's __del__ (wb_model_destroy / wb_rankgroup_destroy: hipFree) would run whenever the cyclic collector
         # happens to, e.g. inside somebody's stream capture or between a lane's enqueue and collect
-        self.rank_key = object()
-        self._read_info()
+        self._setup(lib, h, True, object())
 
-    def _read_info(self):
+    def _setup(self, lib, handle, owned, rank_key):
+        """What a cascade of its own and a group's member view share: the handle, the per-instance bookkeeping, the info."""
+        self._lib, self.handle, self._owned, self.rank_key = lib, handle, owned, rank_key
+        self._scans = {}                 # byte-tile scans so far, per channel dtype code
+        self._jit_failed = set()
+        self._live_left = {}             # live checks a freshly specialised kernel still owes, per channel dtype code
+        self._spec_off = False           # use_specialized(False) is in force
         info = nat.WbModelInfo()
         nat.check(self._lib.wb_model_info(self.handle, C.byref(info)), "wb_model_info")
         self.n_stages, self.depth = info.n_stages, info.depth
@@ -185,13 +186,8 @@ class DeviceCascade:
     def _view(cls, handle, group):
         """A member view of a RankGroup: same interface, handle owned by the group."""
         self = cls.__new__(cls)
-        self._lib = nat.load()
-        self.handle = handle
-        self._owned = False
-        self._scans, self._jit_failed = {}, set()
-        self.rank_key = group.token      # (a token, not the group: see __init__)
         self.group = group               # keeps the handle's owner alive; the group does NOT refer back to its views
-        self._read_info()
+        self._setup(nat.load(), handle, False, group.token)      # (a token, not the group: see __init__)
         return self
 
     def specialized(self):
@@ -212,16 +208,23 @@ class DeviceCascade:
             return False
         nat.check(rc, "wb_model_specialize")
         if not had:
-            self.__dict__.setdefault("_live_left", {})[chn_dtype] = _LIVE_CHECKS      # (PyramidEngine.live_check)
+            self._live_left[chn_dtype] = _LIVE_CHECKS      # (PyramidEngine.live_check)
         return True
 
     def use_specialized(self, enable):
         """The loaded specialised kernels on / off for every later scan of this cascade (off: the generic kernel)."""
         nat.check(self._lib.wb_model_use_specialized(self.handle, 1 if enable else 0), "wb_model_use_specialized")
-        self.__dict__["_spec_off"] = not enable
+        self._spec_off = not enable
 
     def live_checks_left(self, chn_dtype):
-        return 0 if self.__dict__.get("_spec_off") else self.__dict__.get("_live_left", {}).get(chn_dtype, 0)
+        return 0 if self._spec_off else self._live_left.get(chn_dtype, 0)
+
+    def take_live_check(self, chn_dtype, all_left=False):
+        """Consume one of the live checks owed for this tile kind (all_left: every one -- the kernel has been switched
+        off); False when none was left."""
+        left = self._live_left.get(chn_dtype, 0)
+        self._live_left[chn_dtype] = 0 if all_left else max(left - 1, 0)
+        return left > 0
 
     def note_scan(self, chn_dtype, force=False):
         """Called by the engine before a scan on byte tiles: after _JIT_AFTER scans (force: now -- Model.detect is about
@@ -377,6 +380,99 @@ class CapturedStep:
         self.graph.replay()
 
 
+@dataclasses.dataclass(eq=False)
+class NmsBuffers:
+    """What wb_nms_finish_launch needs for `images` finish blocks of `rows` rows; a scan state or the batch's order
+    buffers hold one."""
+    rows: int
+    images: int
+    scratch: object                  # device
+    res: object                      # device: per image 16 bytes of info + `rows` keep flags
+    h_res: object                    # its page-locked copy
+    h: np.ndarray                    # ... as uint8 [images, 16 + rows]
+
+
+@dataclasses.dataclass(eq=False)
+class FinalBuffers:
+    """The one-image finish read-back of a scan state: finish block | alive[B, L, T], one copy."""
+    dev: object                      # device block
+    host: object                     # its page-locked copy
+    views: tuple                     # FinishBlock.views of the copy: (header, keys, boxes, scores)
+    alive: np.ndarray                # the copy's alive[B, L, T], int32
+
+
+@dataclasses.dataclass(eq=False)
+class ScanState:
+    """What an engine keeps per cascade it scans (PyramidEngine._casc_state).  None: not there (yet, or any more)."""
+    dm: DeviceCascade                # (held: the states are keyed by id(dm))
+    tiles: object                    # the cascade's tile list on the device (None: no tile)
+    n_tiles: int
+    alive: object                    # alive[B, L, T]: a view into the control block
+    ranks: bool = False              # the form of the last scan (a re-scan after a buffer overflow repeats it)
+    graph: object = None             # detect_enqueue's captured sequence        } dropped by
+    step: CapturedStep = None        # batch_enqueue's captured step             } PyramidEngine._buffers_moved
+    detect_calls: int = 0
+    batch_calls: int = 0
+    n_loc: int = None                # plan.n_loc of the cascade's window (Model._collect)
+    final: FinalBuffers = None
+    nms: NmsBuffers = None
+
+    def __getitem__(self, name):
+        return getattr(self, name)   # (bench.py reads e._casc_state(dm)["alive"])
+
+
+@dataclasses.dataclass(eq=False)
+class OrderBuffers:
+    """The batch's ordered read-back (fetch_ordered_batch).  fits False: the form does not apply, nothing else is set."""
+    fits: bool
+    scratch: object = None           # device
+    out: object = None               # device: 16 bytes of info | one finish block per image
+    h_out: object = None             # its page-locked copy
+    ev: object = None                # recorded behind the copies
+    info: np.ndarray = None          # the copy's info words, int32
+    views: list = None               # per image FinishBlock.views of the copy
+    nms: NmsBuffers = None
+
+
+@dataclasses.dataclass(eq=False)
+class MultiState:
+    """One cascade list's sequence in detect_multi_run."""
+    stts: list                       # the scan states it was built on
+    dms: list                        # (held: the sequences are keyed by id(dm))
+    calls: int = 0
+    graph: object = None
+    skip: int = 0                    # calls left to sit out after its results did not fit
+    fails: int = 0
+
+
+def checked_input(images, dtype, store_dtype, want):
+    """The host or device tensor to copy into an engine's image buffer: `images` (ndarray or tensor, of the engine's image
+    dtype `dtype`) as a tensor of shape `want` -- [B, H, W], which a 2-D image also fills when B is 1, or [H, W] for one
+    slot -- of the storage dtype (integer types travel as float64: exact); a contiguous ndarray of that dtype is not
+    copied.  Checked in this order: the dtype (TypeError), the shape (ValueError), the range of 64-bit integers
+    (NotImplementedError: they are held as float64, exact -- also their 2x2 sums -- below 2**51)."""
+    import torch
+    host = isinstance(images, np.ndarray)
+    if (images.dtype if host else array_dtype(images)) != dtype:
+        raise TypeError(f"engine built for {dtype} images, got {images.dtype}")
+    shape = tuple(images.shape)
+    if shape != want and (len(want) != 3 or (1,) + shape != want):
+        raise ValueError(f"expected images of shape {want}, got {shape}")
+    if len(shape) < len(want):
+        images = images[None]
+    t = torch.from_numpy(np.ascontiguousarray(images, store_dtype)) if host else images.to(_torch_dtype(store_dtype))
+    # (as float64 already: a 64-bit integer is below 2**51 exactly when the float64 nearest to it is)
+    if dtype.itemsize == 8 and dtype.kind in "iu" and t.numel() and float(t.abs().max()) >= float(1 << 51):
+        raise NotImplementedError("64 bit integer images are supported for values below 2**51 (they are held as float64)")
+    return t
+
+
+def alive_host(alive, T):
+    """alive[B, L, :T] of a scan -- device tensor, page-locked tensor or ndarray -- as a fresh int64 ndarray."""
+    a = alive if isinstance(alive, np.ndarray) else alive.cpu().numpy()
+    return a[:, :, :T].astype(np.int64)
+
+
 class PyramidEngine:
     # detection records read back with the first copy of fetch() / the one copy of fetch_final() (28 bytes each; the
     # copies inside a captured graph have this fixed size).  WB_FETCH_ROWS: diagnostic override
@@ -417,6 +513,8 @@ class PyramidEngine:
         self._alive_words = 0
         self.generation = 0           # bumped whenever a buffer a captured graph may address is re-allocated
         self._mm_clean = False        # the octaves' (min, max) keys are known to be zero (see run)
+        self._casc = {}               # ScanState by id(cascade)
+        self._multi = {}              # detect_multi_run's MultiState by cascade list
         self._alloc_ctrl(0)
         table, total = p.level_table()
         self.chn_stride = int(total)
@@ -433,17 +531,17 @@ class PyramidEngine:
         self.chn = self._chn_flat[: self.batch * self.chn_stride].view(self.batch, self.chn_stride)
         self.cs_sn = orientation_constants()
         self._oct_off = (C.c_int64 * max(p.n_oct, 1))(*[int(x) for x in p.oct_off[:max(p.n_oct, 1)]])
-        self.rank = self._rank_flat = self.rank_owner = None
+        self.rank = self.rank_owner = None
         self._rank_wide = False
         self._level_tiles = None
         self.epoch = 0
         self.det_capacity = int(det_capacity)
         self._h_packed = self._h_alive = None
         self._fetch_ev = torch.cuda.Event()                        # what fetch, fetch_final and detect_multi_run wait on
-        self._h2d_ev, self._upload_async = None, False
+        self._h2d_ev, self._upload_async = torch.cuda.Event(), False       # what wait_upload waits on
         self._mm_host = None
         self._inv_scales_d = self._key_dims = None
-        self._order = None            # buffers of fetch_ordered_batch (scratch, out, page-locked copy), on first use
+        self._order = None            # OrderBuffers of fetch_ordered_batch, on first use
         self._alloc_det()
         if exact_single:
             # a channel function on a bare image: no resize happens, so the clip range is (-inf, +inf)
@@ -477,7 +575,8 @@ class PyramidEngine:
         """(Re)allocate the control block with room for `alive_words` statistics words; the views into it follow."""
         import torch
         old = getattr(self, "ctrl", None)
-        self.generation += 1
+        self._buffers_moved()
+        self._casc.clear()            # (every state's alive[] is a view into the old block)
         NS = nat.WB_DET_SHARDS
         self._alive_words = int(alive_words)
         self.ctrl = torch.zeros(self._mm_words + NS + max(self._alive_words, 1), dtype=torch.int32, device=self.dev)
@@ -488,8 +587,15 @@ class PyramidEngine:
         self._counts = self.ctrl[self._mm_words: self._mm_words + NS]
         if getattr(self, "detb", None) is not None:
             self.detb.counts = self._counts
-        self._casc = {}
-        self._multi = {}              # detect_multi_run's captured sequences, by cascade list
+
+    def _buffers_moved(self):
+        """A buffer that captured graphs address -- the control block, the detection buffer, the rank buffer -- has been
+        re-allocated.  THE place where the engine's kept graphs die: every scan state's graph and step, every multi-model
+        sequence; a CapturedStep a caller holds is refused by its generation stamp."""
+        self.generation += 1
+        for stt in self._casc.values():
+            stt.graph = stt.step = None
+        self._multi.clear()
 
     def _alive_view(self, T1):
         L = max(self.plan.n_levels, 1)
@@ -503,7 +609,7 @@ class PyramidEngine:
         """ONE memset: the accumulators the coming launches add into -- the octaves' (min, max) keys (unless they
         are preset / not recomputed), the detection counters and, with a cascade state, its alive[B, L, T]."""
         lo = 0 if (octaves and not self.exact_single) else self._mm_words
-        hi = self._mm_words + (nat.WB_DET_SHARDS + stt["alive"].numel() if stt is not None else 0)
+        hi = self._mm_words + (nat.WB_DET_SHARDS + stt.alive.numel() if stt is not None else 0)
         if hi > lo:
             self.ctrl[lo:hi].zero_()
 
@@ -512,52 +618,24 @@ class PyramidEngine:
         the shards."""
         cap = max(16, -(-self.det_capacity // nat.WB_DET_SHARDS))
         self.det_capacity = cap * nat.WB_DET_SHARDS
-        self.generation += 1
+        self._buffers_moved()
         self.detb = DetBuffer(cap, self.dev, counts=self._counts)
         self.packed = None            # header + all valid records back to back (wb_det_pack_launch), allocated on first use
-        for stt in getattr(self, "_casc", {}).values():
-            stt.pop("graph", None)    # (a captured detect_run holds the old buffer's address)
 
     # ------------------------------------------------------------------ input
     def load_images(self, images):
         """images: ndarray / tensor [B,H,W] (or [H,W]) of the engine's dtype."""
-        import torch
+        # (a page-locked staging buffer was measured: memcpy + DMA came out 10 % slower per Model.detect call
+        # than torch's own pipelined upload from pageable memory; for detect_stream's lanes, where the DMA would
+        # overlap other work, the host copy alone -- np.copyto, 45 us -- costs what the pageable upload blocks the
+        # host for, 48 us, and torch's multi-threaded CPU copy, 26 us in a tight loop, takes milliseconds once its
+        # worker threads have gone to sleep between images: tools/upload_probe.py)
+        self._load(self.img, images, (self.batch, self.plan.H, self.plan.W))
+
+    def _load(self, dst, images, want):
         self.epoch += 1                       # (lazy consumers notice that the resident images changed)
-        want = (self.batch, self.plan.H, self.plan.W)
-        if isinstance(images, np.ndarray):
-            if images.dtype != self.dtype:
-                raise TypeError(f"engine built for {self.dtype} images, got {images.dtype}")
-            if images.dtype != self.store_dtype:
-                if images.dtype.itemsize == 8 and images.dtype.kind in "iu" and images.size:
-                    # (64-bit integers are held as float64: exact -- also their 2x2 sums -- below 2^51)
-                    if max(abs(int(images.max())), abs(int(images.min()))) >= 1 << 51:
-                        raise NotImplementedError("64 bit integer images are supported for values below 2**51 (they are held as float64)")
-                images = images.astype(self.store_dtype)           # integer types travel as float64 (exact)
-            if images.ndim == 2:
-                images = images[None]
-            if tuple(images.shape) != want:
-                raise ValueError(f"expected images of shape {want}, got {tuple(images.shape)}")
-            t = None
-        else:
-            if array_dtype(images) != self.dtype:
-                raise TypeError(f"engine built for {self.dtype} images, got {images.dtype}")
-            t = images[None] if images.dim() == 2 else images
-            if t.dtype != self.tdtype:
-                t = t.to(self.tdtype)                                   # (integer types travel as float64: exact)
-            if self.dtype.itemsize == 8 and self.dtype.kind in "iu" and t.numel():
-                if float(t.to(torch.float64).abs().max()) >= float(1 << 51):
-                    raise NotImplementedError("64 bit integer images are supported for values below 2**51 (they are held as float64)")
-            if tuple(t.shape) != want:
-                raise ValueError(f"expected images of shape {want}, got {tuple(t.shape)}")
         self._upload_async = False
-        if t is None:
-            # (a page-locked staging buffer was measured: memcpy + DMA came out 10 % slower per Model.detect call
-            # than torch's own pipelined upload from pageable memory; for detect_stream's lanes, where the DMA would
-            # overlap other work, the host copy alone -- np.copyto, 45 us -- costs what the pageable upload blocks the
-            # host for, 48 us, and torch's multi-threaded CPU copy, 26 us in a tight loop, takes milliseconds once its
-            # worker threads have gone to sleep between images: tools/upload_probe.py)
-            t = torch.from_numpy(np.ascontiguousarray(images))
-        self._copy_in(self.img, t)
+        self._copy_in(dst, checked_input(images, self.dtype, self.store_dtype, want))
 
     def _copy_in(self, dst, t):
         """Host or device tensor -> resident image buffer on the current stream.  From PAGE-LOCKED host memory (a caller
@@ -566,15 +644,11 @@ class PyramidEngine:
         stay untouched until `wait_upload` (Model.detect returns after the whole call; detect_stream waits before it takes
         the next image from the caller's iterable).  From pageable memory torch stages the bytes itself and the call
         returns once they have left the caller's array (0.05 ms for a 1080p image)."""
-        if t.device.type == "cpu" and t.is_pinned():
-            import torch
-            dst.copy_(t, non_blocking=True)
-            if self._h2d_ev is None:
-                self._h2d_ev = torch.cuda.Event()
+        pinned = t.device.type == "cpu" and t.is_pinned()
+        dst.copy_(t, non_blocking=True)
+        if pinned:
             self._h2d_ev.record()
             self._upload_async = True
-        else:
-            dst.copy_(t, non_blocking=True)
 
     def wait_upload(self):
         """Block until the last asynchronous upload has left the caller's page-locked buffer (no-op otherwise)."""
@@ -584,29 +658,7 @@ class PyramidEngine:
 
     def load_slot(self, b, image):
         """One 2-D host image into slot b of the batch (Model.detect_stream fills a batch image by image)."""
-        import torch
-        self.epoch += 1
-        self._upload_async = False
-        if not isinstance(image, np.ndarray):
-            if array_dtype(image) != self.dtype:
-                raise TypeError(f"engine built for {self.dtype} images, got {image.dtype}")
-            if tuple(image.shape) != (self.plan.H, self.plan.W):
-                raise ValueError(f"expected an image of shape {(self.plan.H, self.plan.W)}, got {tuple(image.shape)}")
-            if self.dtype.itemsize == 8 and self.dtype.kind in "iu" and image.numel():
-                if float(image.to(torch.float64).abs().max()) >= float(1 << 51):
-                    raise NotImplementedError("64 bit integer images are supported for values below 2**51 (they are held as float64)")
-            self._copy_in(self.img[b], image)
-            return
-        if image.dtype != self.dtype:
-            raise TypeError(f"engine built for {self.dtype} images, got {getattr(image, 'dtype', type(image))}")
-        if tuple(image.shape) != (self.plan.H, self.plan.W):
-            raise ValueError(f"expected an image of shape {(self.plan.H, self.plan.W)}, got {tuple(image.shape)}")
-        if image.dtype != self.store_dtype:
-            if image.dtype.itemsize == 8 and image.dtype.kind in "iu" and image.size:
-                if max(abs(int(image.max())), abs(int(image.min()))) >= 1 << 51:
-                    raise NotImplementedError("64 bit integer images are supported for values below 2**51 (they are held as float64)")
-            image = image.astype(self.store_dtype)
-        self._copy_in(self.img[b], torch.from_numpy(np.ascontiguousarray(image)))
+        self._load(self.img[b], image, (self.plan.H, self.plan.W))
 
     # ------------------------------------------------------------------ launches
     def launch_octaves(self, zero=None):
@@ -639,6 +691,10 @@ class PyramidEngine:
         cascade `dm` (float32 channels never reach HBM)."""
         return dm is not None and dm.rank_dtype is not None and self.spec.key == "grad_hist" and not _NO_RANKS
 
+    def scan_dtype(self, dm):
+        """The channel dtype code the detection path scans cascade `dm` on: its rank form, or the channel function's."""
+        return dm.rank_dtype if self.ranks_for(dm) else self.spec.wb_dtype
+
     def launch_channels(self, rank_dm=None, floats=True):
         """The channel pyramid of every resident image.  rank_dm: also (floats=False: only) write the channels as
         WB_DTYPE_RANK8 bytes for that cascade into self.rank."""
@@ -649,27 +705,29 @@ class PyramidEngine:
         wide = rank_dm is not None and rank_dm.rank_dtype == nat.WB_DTYPE_RANK16
         if rank_dm is not None and (self.rank is None or self._rank_wide != wide):
             # one byte per value, or two (WB_DTYPE_RANK16); 16 spare elements for the cascade's 16-byte group loads
-            tdt = torch.int16 if wide else torch.uint8
-            self._rank_flat = torch.zeros(self.batch * self.chn_stride + 16, dtype=tdt, device=self.dev)
-            self.rank = self._rank_flat[: self.batch * self.chn_stride].view(self.batch, self.chn_stride)
+            flat = torch.zeros(self.batch * self.chn_stride + 16, dtype=torch.int16 if wide else torch.uint8, device=self.dev)
+            self.rank = flat[: self.batch * self.chn_stride].view(self.batch, self.chn_stride)
             self._rank_wide = wide
-            self.generation += 1          # (captured graphs address the old buffer)
-            for stt in self._casc.values():
-                stt.pop("graph", None)
-                stt.pop("step", None)
+            self._buffers_moved()
+        self._channels_call(self.chan_tiles, self.n_chan_tiles, self.chan_patches,
+                            self.chn if floats or rank_dm is None else None, rank_dm)
+        self.rank_owner = rank_dm.rank_key if rank_dm is not None else None      # whose ranks self.rank holds (None: stale)
+
+    def _channels_call(self, tiles, n_tiles, patches, chn, rank_dm=None):
+        """wb_channels_launch_x over a tile list (with its patch table, or None) into `chn` and / or, as ranks of `rank_dm`,
+        into self.rank."""
+        p = self.plan
+        ranked = rank_dm is not None
         nat.check(self.lib.wb_channels_launch_x(nat.stream_ptr(), nat.ptr(self.img), p.H * p.W, nat.ptr(self.oct),
                                                 p.oct_total, self.wb_dtype, self.batch, nat.ptr(self.levels),
-                                                p.n_levels, nat.ptr(self.chan_tiles), self.n_chan_tiles,
+                                                p.n_levels, nat.ptr(tiles), n_tiles,
                                                 nat.ptr(self.minmax), max(p.n_oct, 1), nat.ptr(self.taps),
                                                 self.spec.func_id, p.shrink, p.smooth,
                                                 self.cs_sn.ctypes.data_as(C.POINTER(C.c_double)),
-                                                nat.ptr(self.chn if floats or rank_dm is None else None), self.chn_stride,
-                                                rank_dm.handle if rank_dm is not None else None,
-                                                nat.ptr(self.rank if rank_dm is not None else None), self.chn_stride,
-                                                nat.ptr(self.chan_patches),
-                                                rank_dm.rank_dtype if rank_dm is not None else nat.WB_DTYPE_RANK8),
+                                                nat.ptr(chn), self.chn_stride, rank_dm.handle if ranked else None,
+                                                nat.ptr(self.rank if ranked else None), self.chn_stride, nat.ptr(patches),
+                                                rank_dm.rank_dtype if ranked else nat.WB_DTYPE_RANK8),
                   "wb_channels_launch")
-        self.rank_owner = rank_dm.rank_key if rank_dm is not None else None      # whose ranks self.rank holds (None: stale)
 
     def launch_level(self, l):
         """The float/uint8 channels of ONE level of every resident image (after launch_octaves): what a lazy
@@ -687,16 +745,7 @@ class PyramidEngine:
         n, tiles_d, patches_d = self._level_tiles[l]
         if n == 0:
             return
-        nat.check(self.lib.wb_channels_launch_x(nat.stream_ptr(), nat.ptr(self.img), p.H * p.W, nat.ptr(self.oct),
-                                                p.oct_total, self.wb_dtype, self.batch, nat.ptr(self.levels),
-                                                p.n_levels, nat.ptr(tiles_d), n,
-                                                nat.ptr(self.minmax), max(p.n_oct, 1), nat.ptr(self.taps),
-                                                self.spec.func_id, p.shrink, p.smooth,
-                                                self.cs_sn.ctypes.data_as(C.POINTER(C.c_double)),
-                                                nat.ptr(self.chn), self.chn_stride, None, None, 0, nat.ptr(patches_d),
-                                                nat.WB_DTYPE_RANK8),
-                  "wb_channels_launch")
-
+        self._channels_call(tiles_d, n, patches_d, self.chn)
 
     # ------------------------------------------------------------------ around a caller's channel function
     def resize_level(self, l):
@@ -740,10 +789,8 @@ class PyramidEngine:
             tiles = self.plan.casc_tiles(dm.m, dm.n, dm.tile_rows, dm.tile_cols)
             T1 = max(dm.n_stages, 1)
             alive = self._alive_view(T1)                # (may re-allocate the control block and drop other states)
-            stt = dict(
-                dm=dm, n_tiles=int(tiles.size),
-                tiles=torch.from_numpy(tiles.view(np.uint8).copy()).to(self.dev) if tiles.size else None,
-                alive=alive)
+            stt = ScanState(dm, torch.from_numpy(tiles.view(np.uint8).copy()).to(self.dev) if tiles.size else None,
+                            int(tiles.size), alive)
             if len(self._casc) >= 4:         # a few cascades resident per engine (waldboost.detect scans several models)
                 self._casc.pop(next(iter(self._casc)))
             self._casc[key] = stt
@@ -754,7 +801,7 @@ class PyramidEngine:
         ranks=True scans self.rank (written for `dm` by launch_channels) instead of the channel buffer.
         zero_keys: the launch's first workgroup also resets the octaves' (min, max) keys for the next step (see run)."""
         stt = self._casc_state(dm)
-        if stt["n_tiles"] == 0:
+        if stt.n_tiles == 0:
             return stt
         if ranks and self.rank_owner is not dm.rank_key:
             raise RuntimeError("the rank buffer does not hold this cascade's ranks (launch_channels(rank_dm=...) first)")
@@ -764,9 +811,9 @@ class PyramidEngine:
                                                dm.rank_dtype if ranks else self.spec.wb_dtype,
                                                self.chn_stride,
                                                self.batch, nat.ptr(self.levels), self.plan.n_levels,
-                                               nat.ptr(stt["tiles"]), stt["n_tiles"],
+                                               nat.ptr(stt.tiles), stt.n_tiles,
                                                nat.ptr(self.detb.recs), nat.ptr(self.detb.counts), self.detb.cap,
-                                               nat.ptr(stt["alive"] if stats else None), nat.ptr(zk),
+                                               nat.ptr(stt.alive if stats else None), nat.ptr(zk),
                                                0 if zk is None else zk.numel()),
                   "wb_cascade_launch")
         if zero_keys:
@@ -777,7 +824,7 @@ class PyramidEngine:
         """Reset the counters and statistics, then scan every level of every image with cascade `dm`."""
         stt = self._casc_state(dm)
         self.reset_step(stt, octaves=False)
-        stt["ranks"] = ranks                       # (a re-scan after a buffer overflow repeats the same form)
+        stt.ranks = ranks                          # (a re-scan after a buffer overflow repeats the same form)
         return self.launch_cascade(dm, ranks=ranks)
 
     def run_channels(self, rank_dm=None, floats=True):
@@ -795,11 +842,11 @@ class PyramidEngine:
         # alive[B, L, T] -- nothing touches them before it), the cascade's first workgroup resets what the next step's
         # OCTAVE kernel accumulates into (the (min, max) keys -- the channel kernel has finished with them).  The keys
         # must be zero on entry: ensure_clean_keys (one memset after anything else has used the engine's octaves).
-        if self.exact_single or _NO_FUSED_RESET or stt["n_tiles"] == 0 or self.plan.n_levels == 0:
+        if self.exact_single or _NO_FUSED_RESET or stt.n_tiles == 0 or self.plan.n_levels == 0:
             self.reset_step(stt, octaves=True)
             self.launch_octaves()
             self.launch_channels(dm if fused else None, floats=not fused)
-            stt["ranks"] = fused
+            stt.ranks = fused
             return self.launch_cascade(dm, ranks=fused)
         import torch
         if not torch.cuda.is_current_stream_capturing():
@@ -807,9 +854,9 @@ class PyramidEngine:
         elif not self._mm_clean:
             raise RuntimeError("capture a step only after an eager one (PyramidEngine.capture does): the octaves' keys must be clean")
         o = self._mm_words
-        self.launch_octaves(zero=self.ctrl[o: o + nat.WB_DET_SHARDS + stt["alive"].numel()])
+        self.launch_octaves(zero=self.ctrl[o: o + nat.WB_DET_SHARDS + stt.alive.numel()])
         self.launch_channels(dm if fused else None, floats=not fused)
-        stt["ranks"] = fused
+        stt.ranks = fused
         return self.launch_cascade(dm, ranks=fused, zero_keys=True)
 
     # ------------------------------------------------------------------ hipGraph
@@ -845,7 +892,7 @@ class PyramidEngine:
         buffer, and the same scan again on the resident channels.  Returns the scan state."""
         self.det_capacity = (int(worst * 1.5) + 16) * nat.WB_DET_SHARDS
         self._alloc_det()
-        return self.run_cascade(dm, ranks=stt.get("ranks", False))
+        return self.run_cascade(dm, ranks=stt.ranks)
 
     def pack(self, out=None):
         """Pack the valid records of all shards behind a 4-word header (wb_det_pack_launch) into self.packed --
@@ -883,7 +930,7 @@ class PyramidEngine:
             if worst <= self.detb.cap:
                 break
             stt = self._grow_and_rescan(dm, stt, worst)
-        alive = self._h_alive.numpy()[:, :, :dm.n_stages].astype(np.int64)
+        alive = alive_host(self._h_alive, dm.n_stages)
         if limit is not None and total > limit:
             return Packed(total, None, alive)
         recs = self._h_packed[1:1 + min(total, rows - 1)].numpy().copy()
@@ -894,9 +941,9 @@ class PyramidEngine:
     def _alive_enqueue(self, stt):
         """The copy of alive[B, L, T] of the scan `stt` into page-locked memory (self._h_alive), no synchronisation."""
         import torch
-        if self._h_alive is None or self._h_alive.shape != stt["alive"].shape:
-            self._h_alive = torch.empty(stt["alive"].shape, dtype=torch.int32).pin_memory()
-        self._h_alive.copy_(stt["alive"], non_blocking=True)
+        if self._h_alive is None or self._h_alive.shape != stt.alive.shape:
+            self._h_alive = torch.empty(stt.alive.shape, dtype=torch.int32).pin_memory()
+        self._h_alive.copy_(stt.alive, non_blocking=True)
 
     def _key_extent(self):
         """(whether this pyramid fits the sort key's bit fields, its largest u, its largest v) -- what the finish launches
@@ -921,24 +968,23 @@ class PyramidEngine:
         belong to the cascade's scan state: several cascades can be scanned back to back on one engine (waldboost.detect)
         and read back with ONE wait -- the shared detection buffer is free again as soon as this launch has run."""
         import torch
-        n_alive = stt["alive"].numel()
-        if "final" not in stt or stt["final_alive_words"] != n_alive:
+        n_alive = stt.alive.numel()
+        fb = stt.final
+        if fb is None:
             # the finish block | alive[B, L, T] (the kernel copies the statistics behind it: one read-back copy, not two)
             blk = FinishBlock(self._FETCH_ROWS)
             nbytes = blk.nbytes + 4 * n_alive
-            stt["final"] = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
-            stt["h_final"] = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
-            stt["final_alive_words"] = n_alive
-            h = stt["h_final"].numpy()
-            stt["h_final_views"] = blk.views(h)
-            stt["h_alive"] = h[blk.nbytes:].view(np.int32).reshape(tuple(stt["alive"].shape))
+            host = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
+            h = host.numpy()
+            fb = stt.final = FinalBuffers(torch.empty(nbytes, dtype=torch.uint8, device=self.dev), host, blk.views(h),
+                                          h[blk.nbytes:].view(np.int32).reshape(tuple(stt.alive.shape)))
         # (one workgroup sorts up to 4096 keys in LDS and writes the sections in the reference's order: header[3])
         nat.check(self.lib.wb_det_finish_sorted_launch(nat.stream_ptr(), nat.ptr(self.detb.recs), nat.ptr(self.detb.counts),
                                                        self.detb.cap, nat.ptr(self._inv_scales_d), self.plan.n_levels,
                                                        self._key_dims[1], self._key_dims[2], dm.m, dm.n,
-                                                       nat.ptr(stt["final"]), self._FETCH_ROWS, nat.ptr(stt["alive"]), n_alive),
+                                                       nat.ptr(fb.dev), self._FETCH_ROWS, nat.ptr(stt.alive), n_alive),
                   "wb_det_finish_sorted_launch")
-        stt["h_final"].copy_(stt["final"], non_blocking=True)
+        fb.host.copy_(fb.dev, non_blocking=True)
 
     def _nms_enqueue(self, holder, fin_ptr, rows, n_images, nms):
         """wb_nms_finish_launch on the `n_images` finish blocks of `rows` rows at `fin_ptr` + the copy of its keep flags
@@ -949,30 +995,29 @@ class PyramidEngine:
         import torch
         if rows < 4 or rows % 4:
             return
-        nb = holder.get("nms")
-        if nb is None or nb["rows"] != rows or nb["images"] != n_images:
+        nb = holder.nms
+        if nb is None or nb.rows != rows or nb.images != n_images:
             need = C.c_size_t()
             nat.check(self.lib.wb_nms_finish_scratch_bytes(rows, n_images, C.byref(need)), "wb_nms_finish_scratch_bytes")
-            nb = holder["nms"] = dict(rows=rows, images=n_images,
-                                      scratch=torch.empty(need.value, dtype=torch.uint8, device=self.dev),
-                                      res=torch.empty(n_images * (16 + rows), dtype=torch.uint8, device=self.dev),
-                                      h_res=torch.empty(n_images * (16 + rows), dtype=torch.uint8).pin_memory())
-            nb["h"] = nb["h_res"].numpy().reshape(n_images, 16 + rows)
+            h_res = torch.empty(n_images * (16 + rows), dtype=torch.uint8).pin_memory()
+            nb = holder.nms = NmsBuffers(rows, n_images, torch.empty(need.value, dtype=torch.uint8, device=self.dev),
+                                         torch.empty(n_images * (16 + rows), dtype=torch.uint8, device=self.dev),
+                                         h_res, h_res.numpy().reshape(n_images, 16 + rows))
         iou_t, score_t = nms
         nat.check(self.lib.wb_nms_finish_launch(nat.stream_ptr(), C.c_void_p(fin_ptr), rows, n_images, float(iou_t),
                                                 0 if score_t is None else 1, 0.0 if score_t is None else float(score_t),
-                                                nat.ptr(nb["scratch"]), nb["scratch"].numel(), nat.ptr(nb["res"])),
+                                                nat.ptr(nb.scratch), nb.scratch.numel(), nat.ptr(nb.res)),
                   "wb_nms_finish_launch")
-        nb["h_res"].copy_(nb["res"], non_blocking=True)
+        nb.h_res.copy_(nb.res, non_blocking=True)
 
     @staticmethod
     def _nms_keep(holder, b, rows, total):
         """Image b's keep flags (bool [total]) from the read-back of _nms_enqueue; None when the device did not
         suppress this image (more detections than a block holds)."""
-        nb = holder.get("nms")
-        if nb is None or nb["rows"] != rows:
+        nb = holder.nms
+        if nb is None or nb.rows != rows:
             return None
-        row = nb["h"][b]
+        row = nb.h[b]
         info = row[:16].view(np.uint32)
         if int(info[2]) != 1 or int(info[1]) != total:
             return None
@@ -996,11 +1041,11 @@ class PyramidEngine:
             if not enqueued:
                 self._final_enqueue(dm, stt)
                 if nms is not None:
-                    self._nms_enqueue(stt, stt["final"].data_ptr(), self._FETCH_ROWS, 1, nms)
+                    self._nms_enqueue(stt, stt.final.dev.data_ptr(), self._FETCH_ROWS, 1, nms)
             enqueued = False
             self._fetch_ev.record(stream)                     # (None: the current stream)
             self._fetch_ev.synchronize()
-            worst = int(stt["h_final_views"][0][1])
+            worst = int(stt.final.views[0][1])
             if worst <= self.detb.cap:
                 break
             if stream is not None:
@@ -1011,11 +1056,11 @@ class PyramidEngine:
     def _finished(self, stt, T, nms=False):
         """The Finished of the read-back in the scan state `stt` (T stages; nms: with the keep flags _nms_enqueue left),
         None when there are more detections than the block holds."""
-        hdr, keys, boxes, scores = stt["h_final_views"]
+        hdr, keys, boxes, scores = stt.final.views
         total = int(hdr[0])
         if total > self._FETCH_ROWS:
             return None
-        return Finished(keys[:total], boxes, scores, stt["h_alive"][:, :, :T].astype(np.int64), bool(hdr[3]),
+        return Finished(keys[:total], boxes, scores, alive_host(stt.final.alive, T), bool(hdr[3]),
                         self._nms_keep(stt, 0, self._FETCH_ROWS, total) if nms else None)
 
     _ORDER_ROWS = 4096               # per image: what wb_det_order_batch_launch orders (more: the caller's other path)
@@ -1025,18 +1070,18 @@ class PyramidEngine:
         form applies to this pyramid (the sort key's bit fields)."""
         import torch
         if self._order is None:
-            od = self._order = dict(fits=self._key_extent()[0])
-            if od["fits"]:
+            od = self._order = OrderBuffers(self._key_extent()[0])
+            if od.fits:
                 P, B = self._ORDER_ROWS, self.batch
                 blk = FinishBlock(P)
-                od["scratch"] = torch.empty(B * (256 + 16 * P), dtype=torch.uint8, device=self.dev)
-                od["out"] = torch.empty(16 + B * blk.nbytes, dtype=torch.uint8, device=self.dev)
-                od["h_out"] = torch.empty(16 + B * blk.nbytes, dtype=torch.uint8).pin_memory()
-                od["ev"] = torch.cuda.Event()
-                h = od["h_out"].numpy()
-                od["info"] = h[:16].view(np.int32)
-                od["views"] = [blk.views(h, 16 + b * blk.nbytes) for b in range(B)]
-        return self._order["fits"]
+                od.scratch = torch.empty(B * (256 + 16 * P), dtype=torch.uint8, device=self.dev)
+                od.out = torch.empty(16 + B * blk.nbytes, dtype=torch.uint8, device=self.dev)
+                od.h_out = torch.empty(16 + B * blk.nbytes, dtype=torch.uint8).pin_memory()
+                od.ev = torch.cuda.Event()
+                h = od.h_out.numpy()
+                od.info = h[:16].view(np.int32)
+                od.views = [blk.views(h, 16 + b * blk.nbytes) for b in range(B)]
+        return self._order.fits
 
     def order_batch_enqueue(self, dm, stt, nms=None):
         """wb_det_order_batch_launch on the last scan's detections + the read-back copies (ordered results, alive[B, L, T])
@@ -1048,14 +1093,14 @@ class PyramidEngine:
         od, p = self._order, self.plan
         nat.check(self.lib.wb_det_order_batch_launch(nat.stream_ptr(), nat.ptr(self.detb.recs), nat.ptr(self.detb.counts),
                                                      self.detb.cap, self.batch, nat.ptr(self._inv_scales_d), p.n_levels,
-                                                     self._key_dims[1], self._key_dims[2], dm.m, dm.n, nat.ptr(od["scratch"]),
-                                                     od["scratch"].numel(), nat.ptr(od["out"]), self._ORDER_ROWS),
+                                                     self._key_dims[1], self._key_dims[2], dm.m, dm.n, nat.ptr(od.scratch),
+                                                     od.scratch.numel(), nat.ptr(od.out), self._ORDER_ROWS),
                   "wb_det_order_batch_launch")
-        od["h_out"].copy_(od["out"], non_blocking=True)
+        od.h_out.copy_(od.out, non_blocking=True)
         self._alive_enqueue(stt)
         if nms is not None:                                   # (every image's block suppressed in the same three launches)
-            self._nms_enqueue(od, od["out"].data_ptr() + 16, self._ORDER_ROWS, self.batch, nms)
-        od["ev"].record()
+            self._nms_enqueue(od, od.out.data_ptr() + 16, self._ORDER_ROWS, self.batch, nms)
+        od.ev.record()
         return True
 
     def fetch_ordered_batch(self, dm, stt, enqueued=False, nms=None):
@@ -1073,19 +1118,19 @@ class PyramidEngine:
                 return None
             enqueued = False
             od = self._order
-            od["ev"].synchronize()
-            worst = int(od["info"][1])
+            od.ev.synchronize()
+            worst = int(od.info[1])
             if worst <= self.detb.cap:
                 break
             stt = self._grow_and_rescan(dm, stt, worst)
         out = []
-        for hdr, keys, boxes, scores in od["views"]:
+        for hdr, keys, boxes, scores in od.views:
             n_b = int(hdr[0])
             if int(hdr[1]) > self._ORDER_ROWS or int(hdr[3]) != 1:
                 return None
             out.append(ImageResult(keys[:n_b], boxes[:n_b], scores[:n_b],
                                    self._nms_keep(od, len(out), self._ORDER_ROWS, n_b) if nms is not None else None))
-        return out, self._h_alive.numpy()[:, :, :dm.n_stages].astype(np.int64)
+        return out, alive_host(self._h_alive, dm.n_stages)
 
     def live_check(self, dm):
         """A cascade whose specialised kernel has just been built, on the image(s) resident in this engine: the whole step
@@ -1094,22 +1139,20 @@ class PyramidEngine:
         switched off for this cascade for good (a warning says so) -- the step's buffers hold the generic kernel's results
         either way.  Runs _LIVE_CHECKS times per cascade and tile kind, outside captures; costs one extra step each."""
         import torch
-        dtype = dm.rank_dtype if self.ranks_for(dm) else self.spec.wb_dtype
+        dtype = self.scan_dtype(dm)
         if dm.live_checks_left(dtype) <= 0 or dtype not in dm.specialized() or torch.cuda.is_current_stream_capturing():
             return
-        left = dm.__dict__["_live_left"]
-        while left.get(dtype, 0) > 0:
-            left[dtype] -= 1
+        while dm.take_live_check(dtype):
             stt = self.run(dm)                                       # specialised kernel
             if int(self.detb.counts.max().item()) > self.detb.cap:
                 return                                                # (overflowing buffer: the caller grows it; check another time)
-            spec = (sort_records(self.detb.compact()).clone(), stt["alive"].clone())
+            spec = (sort_records(self.detb.compact()).clone(), stt.alive.clone())
             dm.use_specialized(False)
-            self.run_cascade(dm, ranks=stt["ranks"])                  # generic kernel, same channels
-            gen = (sort_records(self.detb.compact()), stt["alive"])
+            self.run_cascade(dm, ranks=stt.ranks)                     # generic kernel, same channels
+            gen = (sort_records(self.detb.compact()), stt.alive)
             same = spec[0].shape == gen[0].shape and bool(torch.equal(spec[0], gen[0])) and bool(torch.equal(spec[1], gen[1]))
             if not same:
-                left[dtype] = 0
+                dm.take_live_check(dtype, all_left=True)
                 _log.warning("cascade of %d stages, depth %d: its model-specialised kernel disagrees with the generic kernel on "
                              "this image (%d against %d detections); the specialised kernel is switched off for this cascade",
                              dm.n_stages, dm.depth, int(spec[0].shape[0]), int(gen[0].shape[0]))
@@ -1134,11 +1177,11 @@ class PyramidEngine:
         if not self._final_ready():
             self.run(dm)
             return None
-        g = stt.get("graph")
-        if g is None and stt.get("detect_calls", 0) >= 1 and not _NO_DETECT_GRAPH:
+        g = stt.graph
+        if g is None and stt.detect_calls >= 1 and not _NO_DETECT_GRAPH:
             # (the first call ran eagerly: every lazily allocated buffer exists, the kernels are loaded)
             # a cascade that is scanned again is worth its specialised kernel -- built now, so that the graph holds it
-            dm.note_scan(dm.rank_dtype if self.ranks_for(dm) else self.spec.wb_dtype, force=True)
+            dm.note_scan(self.scan_dtype(dm), force=True)
             self.live_check(dm)               # (a kernel built just now meets its first real image: cross-checked before the capture)
             g = torch.cuda.CUDAGraph()
             self.ensure_clean_keys()          # (the captured step holds no memset: see run)
@@ -1146,8 +1189,8 @@ class PyramidEngine:
             with capturing(g):
                 self.run(dm)
                 self._final_enqueue(dm, stt)
-            stt["graph"] = g
-        stt["detect_calls"] = stt.get("detect_calls", 0) + 1
+            stt.graph = g
+        stt.detect_calls += 1
         if g is None:
             self.run(dm)
             self._final_enqueue(dm, stt)
@@ -1155,22 +1198,20 @@ class PyramidEngine:
             self.ensure_clean_keys()
             g.replay()
         if nms is not None:
-            self._nms_enqueue(stt, stt["final"].data_ptr(), self._FETCH_ROWS, 1, nms)
+            self._nms_enqueue(stt, stt.final.dev.data_ptr(), self._FETCH_ROWS, 1, nms)
         return stt
 
     def batch_enqueue(self, dm):
         """The step -- octaves, channels, cascade -- over the resident batch, without a wait: eager on an engine's first
-        call, a replayed hipGraph afterwards (captured again when the engine re-allocated a buffer the graph addresses).
+        call, a replayed hipGraph afterwards (captured again after _buffers_moved has dropped it).
         Returns the scan state fetch() takes."""
         stt = self._casc_state(dm)
-        step = stt.get("step")
-        if step is not None and step.generation != self.generation:
-            step = None
-        if step is None and stt.get("batch_calls", 0) >= 1 and not _NO_DETECT_GRAPH:
-            dm.note_scan(dm.rank_dtype if self.ranks_for(dm) else self.spec.wb_dtype, force=True)
+        step = stt.step
+        if step is None and stt.batch_calls >= 1 and not _NO_DETECT_GRAPH:
+            dm.note_scan(self.scan_dtype(dm), force=True)
             self.live_check(dm)
-            step = stt["step"] = self.capture(dm)
-        stt["batch_calls"] = stt.get("batch_calls", 0) + 1
+            step = stt.step = self.capture(dm)
+        stt.batch_calls += 1
         if step is None:
             self.run(dm)
         else:
@@ -1190,16 +1231,16 @@ class PyramidEngine:
         if not self._final_ready() or not 0 < len(dms) <= 4 or len({id(d) for d in dms}) != len(dms):
             return None
         key = tuple(id(d) for d in dms) + (bool(ranks),)
-        stts = [self._casc_state(d) for d in dms]            # (may grow the control block: before the generation is read)
+        stts = [self._casc_state(d) for d in dms]            # (may grow the control block, which drops the sequences)
         if any(self._casc.get(id(d)) is not t for d, t in zip(dms, stts)):
             return None
         st = self._multi.get(key)
-        if st is None or st["generation"] != self.generation or any(a is not b for a, b in zip(st["stts"], stts)):
+        if st is None or any(a is not b for a, b in zip(st.stts, stts)):
             if len(self._multi) >= 2:
                 self._multi.pop(next(iter(self._multi)))
-            st = self._multi[key] = dict(generation=self.generation, stts=stts, dms=list(dms), calls=0, graph=None, skip=0, fails=0)
-        if st["skip"] > 0:                                    # (its results did not fit lately: do not scan twice per call)
-            st["skip"] -= 1
+            st = self._multi[key] = MultiState(stts, list(dms))
+        if st.skip > 0:                                       # (its results did not fit lately: do not scan twice per call)
+            st.skip -= 1
             return None
 
         def enqueue():
@@ -1207,7 +1248,7 @@ class PyramidEngine:
             for d in dms:
                 self._final_enqueue(d, self.run_cascade(d, ranks=ranks))
 
-        if st["graph"] is None and st["calls"] >= 1 and st["fails"] == 0 and not _NO_DETECT_GRAPH:
+        if st.graph is None and st.calls >= 1 and st.fails == 0 and not _NO_DETECT_GRAPH:
             # (captured after an eager call whose results fitted: a sequence that keeps missing is not worth a capture)
             for d in dms:
                 d.note_scan(d.rank_dtype if ranks else self.spec.wb_dtype, force=True)
@@ -1215,13 +1256,13 @@ class PyramidEngine:
             torch.cuda.synchronize()
             with capturing(g):
                 enqueue()
-            st["graph"] = g
-        st["calls"] += 1
-        if st["graph"] is None:
+            st.graph = g
+        st.calls += 1
+        if st.graph is None:
             enqueue()
         else:
             self._mm_clean = False                            # (the replay's octave launch leaves its keys behind)
-            st["graph"].replay()
+            st.graph.replay()
             self.rank_owner = dms[0].rank_key if ranks else None
         self._fetch_ev.record()
         self._fetch_ev.synchronize()
@@ -1230,15 +1271,15 @@ class PyramidEngine:
             # a cascade whose results did not fit (a shard overflowed, or more detections than one read-back holds): None
             # in its place -- the caller scans THAT cascade again on the pyramid this call left resident
             # (Model.scan_engine: run_cascade + fetch, which grows the buffer); the others keep what they have
-            out.append(None if int(stt["h_final_views"][0][1]) > self.detb.cap else self._finished(stt, d.n_stages))
+            out.append(None if int(stt.final.views[0][1]) > self.detb.cap else self._finished(stt, d.n_stages))
         if any(f is None for f in out):
-            st["fails"] += 1                                  # (the whole sequence is tried again after 16, 32, 64 ... calls)
-            st["skip"] = min(8 << st["fails"], 4096)
+            st.fails += 1                                     # (the whole sequence is tried again after 16, 32, 64 ... calls)
+            st.skip = min(8 << st.fails, 4096)
             # (the re-scans may reuse read-back buffers before the caller has collected the fitted results: hand out copies)
             out = [None if f is None else f._replace(keys=f.keys.copy(), boxes=np.array(f.boxes[:f.keys.size]),
                                                      scores=np.array(f.scores[:f.keys.size])) for f in out]
         else:
-            st["fails"] = 0
+            st.fails = 0
         return out
 
     def detect_collect(self, dm, token, stream=None, nms=None):
@@ -1274,27 +1315,25 @@ class PyramidEngine:
             self._inv_scales = np.array([np.float32(1.0 / s) for s in self.plan.scales], np.float32)
         return self._inv_scales
 
-    def level_tensor(self, b, l):
-        """Channels of level l of image b as a device view [u,v,C] into the pyramid buffer."""
-        lv = self.plan.levels[l]
-        off = int(self.level_np[l]["chn_off"])
-        u, v, C = lv["u"], lv["v"], self.spec.n_channels
-        return self.chn[b, off:off + u * v * C].view(u, v, C)
-
-    def read_rank_level(self, b, l):
-        """Ranks of level l of image b as a uint8 ndarray [u,v,4] (after launch_channels(rank_dm=...))."""
+    def _level_slice(self, buf, b, l, C):
+        """Level l of image b in a channel or rank buffer, as a device view [u,v,C]."""
         lv = self.plan.levels[l]
         off = int(self.level_np[l]["chn_off"])
         u, v = lv["u"], lv["v"]
-        r = self.rank[b, off:off + u * v * 4].reshape(u, v, 4).cpu().numpy()
+        return buf[b, off:off + u * v * C].view(u, v, C)
+
+    def level_tensor(self, b, l):
+        """Channels of level l of image b as a device view [u,v,C] into the pyramid buffer."""
+        return self._level_slice(self.chn, b, l, self.spec.n_channels)
+
+    def read_rank_level(self, b, l):
+        """Ranks of level l of image b as a uint8 ndarray [u,v,4] (after launch_channels(rank_dm=...))."""
+        r = self._level_slice(self.rank, b, l, 4).cpu().numpy()
         return r.view(np.uint16) if r.dtype == np.int16 else r
 
     def read_level(self, b, l):
         """Channels of level l of image b as a fresh HWC ndarray [u,v,C] of the channel function's dtype."""
-        lv = self.plan.levels[l]
-        off = int(self.level_np[l]["chn_off"])
-        u, v, C = lv["u"], lv["v"], self.spec.n_channels
-        return self.chn[b, off:off + u * v * C].reshape(u, v, C).cpu().numpy()
+        return self.level_tensor(b, l).cpu().numpy()
 
 
 def nat_f32_key(f):

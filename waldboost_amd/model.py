@@ -262,9 +262,9 @@ class Model:
         got = fin if fin is not None else eng.fetch(dm, stt)      # (likewise: packed records + statistics)
         # (dm: the cascade that was scanned -- detect_stream collects late)
         res = dict(alive=got.alive[0].reshape(eng.plan.n_levels, dm.n_stages), scales=list(eng.plan.scales))
-        if "n_loc" not in stt:
-            stt["n_loc"] = eng.plan.n_loc(m, n)
-        self.n_loc += stt["n_loc"]
+        if stt.n_loc is None:
+            stt.n_loc = eng.plan.n_loc(m, n)
+        self.n_loc += stt.n_loc
         self.n_weak += int(res["alive"].sum())
         keep = None
         if fin is not None:
@@ -502,7 +502,7 @@ class Model:
         eng.ensure_capacity(dm)
         det = eng.sorted_detections()
         boxes, scores = eng.boxes(det, dm)
-        alive = stt["alive"][:, :, :T].cpu().numpy().astype(np.int64).reshape(B, L, T)
+        alive = _engine.alive_host(stt.alive, T).reshape(B, L, T)
         self.n_loc += B * eng.plan.n_loc(m, n)
         self.n_weak += int(alive.sum())
         d = det.cpu().numpy().view(nat.DET_DTYPE).reshape(-1)
