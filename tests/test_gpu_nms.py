@@ -12,6 +12,7 @@ import waldboost_amd as wb
 from waldboost_amd import _native as nat
 from waldboost_amd.boxes import Boxes, nms_keep_mask
 from waldboost_amd.synth import synth_image
+from nms_designs import finish_block
 from nms_reference import detector_like_boxes, hand_cases, nms_boxes, nms_keep
 from util import GOLDEN
 
@@ -295,16 +296,6 @@ def test_the_threshold_does_not_leak_into_the_plain_call(case):
         want = nms_boxes(fresh, 0.2)
         check_not_vacuous(fresh, want)
         assert same_boxes(full, fresh) and same_boxes(kept, want)
-
-
-def finish_block(P, keys, boxes, scores, header):
-    blk = np.zeros(16 + 28 * P, np.uint8)
-    blk[:16].view(np.int32)[:] = header
-    n = len(keys)
-    blk[16:16 + 8 * P].view(np.uint64)[:n] = keys
-    blk[16 + 8 * P:16 + 24 * P].view(np.float32).reshape(P, 4)[:n] = boxes
-    blk[16 + 24 * P:].view(np.float32)[:n] = scores
-    return blk
 
 
 def test_nms_on_hand_built_finish_blocks():
