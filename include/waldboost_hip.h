@@ -504,6 +504,28 @@ int wb_nms_finish_launch(void *stream, const void *fin, uint32_t out_capacity, i
                          int use_score_threshold, float score_threshold, void *scratch, size_t scratch_bytes,
                          void *result);
 
+/* Box matching: for every detection the best IoU over the ground-truth boxes of its image and the box that gives it (reference
+ * testing.py:53-58, the iou.argmax / iou.max of Evaluator.evaluate; samples.py:133 for the miner).
+ * New symbol of ABI 8 (the version number did not change: nothing that existed did).
+ *   dt        dev float64 [n_dt][4] XYXY, 8-byte aligned;  dt_image dev int32 [n_dt]: the image each detection belongs to
+ *   gt        dev float64 [n_gt][4] XYXY, 8-byte aligned (NULL allowed when n_gt == 0);  gt_off dev int32 [n_images + 1]: the
+ *             candidates of image b are gt[gt_off[b] .. gt_off[b + 1])
+ *   best      dev float64 [n_dt], 8-byte aligned;  owner dev int32 [n_dt]
+ *   * iou in float64: iw = max(min(ax2, bx2) - max(ax1, bx1), 0), ih alike, inter = iw * ih, areas (x2 - x1) * (y2 - y1),
+ *     union = area_a + area_b - inter, inter / union, 0 where union <= 0 -- every operation rounded on its own, the divide
+ *     correctly rounded (waldboost_amd.boxes.iou, operation by operation);
+ *   * best[i] = the largest iou over the candidates of detection i; owner[i] = the FIRST candidate that reaches it, as an index
+ *     inside the image's own list (np.argmax: a detection that overlaps nothing is owned by candidate 0);
+ *   * an image without candidates: best 0, owner -1.
+ * Every entry of best and owner is written.  dt_image is clamped to [0, n_images) and both ends of a candidate range to
+ * [0, n_gt] (an end in front of its start: no candidates), so bad offsets read nothing outside the buffers.
+ * n_dt == 0 launches nothing (WB_OK, pointers not looked at); n_dt > 2^26 is WB_ERR_UNSUPPORTED; null pointers, negative
+ * sizes, n_images == 0 with detections and misaligned pointers are WB_ERR_INVALID.  One launch, no scratch, no host
+ * synchronisation. */
+int wb_match_launch(void *stream, const double *dt /* [n_dt][4] */, const int32_t *dt_image /* [n_dt] */,
+                    const double *gt /* [n_gt][4] */, const int32_t *gt_off /* [n_images + 1] */,
+                    int64_t n_dt, int64_t n_gt, int n_images, double *best /* [n_dt] */, int32_t *owner /* [n_dt] */);
+
 /* Split search of the FPGA flavour's tree learner (reference fpga/training.py:15-57), one tree level per call.
  * New symbols of ABI 8 (the version number did not change: nothing that existed did).
  *   xt       dev uint8 [n_features][n_samples]: the samples, FEATURE-major

@@ -39,6 +39,12 @@ class Boxes:
     def normalized(self, scale=1.0):
         return Boxes((self._c * np.float32(scale)).astype(self._c.dtype), **self._fields)
 
+    def area(self):
+        """(x2 - x1) * (y2 - y1) per box, float64 (stand-in for ``bbx.Boxes.area``, reference testing.py:42; bbx is absent here
+        and this boundary is unpinned upstream)."""
+        c = np.asarray(self._c, np.float64)
+        return (c[:, 2] - c[:, 0]) * (c[:, 3] - c[:, 1])
+
     def __len__(self):
         return self._c.shape[0]
 
@@ -74,6 +80,99 @@ def iou(a, b):
     area_b = ((B[:, 2] - B[:, 0]) * (B[:, 3] - B[:, 1]))[None, :]
     union = area_a + area_b - inter
     return np.where(union > 0, inter / np.where(union > 0, union, 1), 0.0)
+
+
+def boxes_in_window(boxes, window, min_overlap=1):
+    """bool [N]: the part of each box inside the single box `window` is at least `min_overlap` of the box's own area --
+    ``inter >= min_overlap * area``, inter the clipped intersection, float64 host arithmetic (so a box that exactly fills the
+    window passes at 1, and so does a box of no area).  Stand-in for ``bbx.boxes_in_window`` (reference testing.py:43); bbx is
+    absent here and this boundary is unpinned upstream."""
+    w = np.asarray(window.get() if isinstance(window, Boxes) else window, np.float64).reshape(-1)
+    if w.size != 4:
+        raise ValueError("boxes_in_window takes ONE window box")
+    c = np.asarray(boxes.get(), np.float64).reshape(-1, 4)
+    iw = np.clip(np.minimum(c[:, 2], w[2]) - np.maximum(c[:, 0], w[0]), 0, None)
+    ih = np.clip(np.minimum(c[:, 3], w[3]) - np.maximum(c[:, 1], w[1]), 0, None)
+    return iw * ih >= min_overlap * boxes.area()
+
+
+def set_aspect_ratio(boxes, ar):
+    """Boxes of the same centres and areas whose width / height is `ar`: ``w' = sqrt(area * ar)``, ``h' = sqrt(area / ar)``,
+    float64 host arithmetic; every field is carried over.  Stand-in for ``bbx.set_aspect_ratio`` (reference testing.py:50-51);
+    bbx is absent here and this boundary is unpinned upstream."""
+    ar = float(ar)
+    if not ar > 0 or not np.isfinite(ar):
+        raise ValueError("aspect ratio must be a positive number")
+    c = np.asarray(boxes.get(), np.float64).reshape(-1, 4)
+    cx, cy = (c[:, 0] + c[:, 2]) / 2, (c[:, 1] + c[:, 3]) / 2
+    area = boxes.area()
+    w, h = np.sqrt(area * ar), np.sqrt(area / ar)
+    return Boxes(np.stack([cx - w / 2, cy - h / 2, cx + w / 2, cy + h / 2], 1), **{k: boxes.get_field(k) for k in boxes.fields()})
+
+
+_MATCH_COORD_MAX = 2.0 ** 500   # coordinates below it: no difference, product or sum of match_boxes' arithmetic overflows
+
+
+def _match_coords(b, what):
+    c = np.ascontiguousarray(np.asarray(b.get(), np.float64).reshape(-1, 4))
+    if not (np.abs(c) < _MATCH_COORD_MAX).all():               # (a NaN fails the comparison too)
+        raise ValueError(f"match_boxes: {what} coordinates must be finite and below 2**500 in magnitude")
+    return c
+
+
+def match_boxes(dt_boxes, gt_boxes_per_image, dt_image=None):
+    """(best float64 [N], owner int32 [N]): for every detection the largest ``iou`` over the ground-truth boxes of its image
+    and the index, inside that image's list, of the FIRST box that reaches it (``np.argmax``: a detection that overlaps nothing
+    is owned by box 0); an image without ground truth gives best 0, owner -1.
+
+    dt_boxes, gt_boxes_per_image: one pair of Boxes -- or the detections of a whole data set in one Boxes, ``dt_image`` the
+    image ordinal of each, and a list with every image's ground-truth Boxes.  Coordinates are converted to float64 as `iou`
+    does (ground truth need not hold float32 values); all of them must be finite and below 2**500 in magnitude, so that no
+    product can overflow into a NaN (ValueError).
+
+    Runs on the GPU (wb_match_launch): one upload, one launch, one read-back; like everything in this package it has no CPU
+    fallback and raises NativeError without a GPU.  No detections: empty arrays, without touching the device."""
+    if isinstance(gt_boxes_per_image, Boxes):
+        if dt_image is not None:
+            raise ValueError("match_boxes: dt_image goes with a LIST of ground-truth Boxes")
+        gts = [gt_boxes_per_image]
+        image = np.zeros(len(dt_boxes), np.int32)
+    else:
+        gts = list(gt_boxes_per_image)
+        if dt_image is None:
+            raise ValueError("match_boxes: a list of ground-truth Boxes needs dt_image")
+        image = np.asarray(dt_image).reshape(-1)
+        if image.size != len(dt_boxes):
+            raise ValueError(f"match_boxes: {image.size} dt_image entries, {len(dt_boxes)} detections")
+        if image.size and (image.dtype.kind not in "iu" or image.min() < 0 or image.max() >= len(gts)):
+            raise ValueError(f"match_boxes: dt_image must hold integers in [0, {len(gts)})")
+        image = image.astype(np.int32)
+    dt = _match_coords(dt_boxes, "detection")
+    gt = [_match_coords(g, "ground-truth") for g in gts]
+    n = dt.shape[0]
+    if n == 0:
+        return np.zeros(0, np.float64), np.zeros(0, np.int32)
+    off = np.zeros(len(gt) + 1, np.int64)
+    np.cumsum([g.shape[0] for g in gt], out=off[1:])
+    n_gt = int(off[-1])
+    if n_gt >= 1 << 31:
+        raise ValueError("match_boxes: at most 2**31 - 1 ground-truth boxes")
+    import ctypes as C
+    import torch
+    from . import _native as nat
+    lib = nat.load()
+    dev = nat.require_gpu()
+    # one upload: detections | ground truth | dt_image | gt_off (the doubles first: everything stays aligned)
+    parts = [dt.reshape(-1).view(np.uint8)] + [g.reshape(-1).view(np.uint8) for g in gt]
+    parts += [image.view(np.uint8), off.astype(np.int32).view(np.uint8)]
+    d_in = torch.from_numpy(np.concatenate(parts)).to(dev)
+    d_out = torch.empty(12 * n, dtype=torch.uint8, device=dev)         # best | owner: one read-back
+    at = lambda t, o: C.c_void_p(t.data_ptr() + o)
+    o_gt, o_img = 32 * n, 32 * (n + n_gt)
+    nat.check(lib.wb_match_launch(nat.stream_ptr(), at(d_in, 0), at(d_in, o_img), at(d_in, o_gt), at(d_in, o_img + 4 * n), n, n_gt,
+                                  len(gt), at(d_out, 0), at(d_out, 8 * n)), "wb_match_launch")
+    h = d_out.cpu().numpy()
+    return h[:8 * n].view(np.float64).copy(), h[8 * n:].view(np.int32).copy()
 
 
 _NMS_RANK_MAX = 1 << 16      # most boxes wb_nms_launch orders itself (a quadratic pass); above: torch.sort + wb_nms_ordered_launch

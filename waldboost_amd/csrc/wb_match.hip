@@ -1,0 +1,130 @@
+// Box matching on the device (wb_match_launch): for every detection its best IoU over the ground-truth boxes of its image
+// and the box that gives it -- the step of the reference's Evaluator.evaluate between NMS and the precision / recall curve
+// (reference testing.py:53-58 iou.argmax / iou.max), and the miner's samples._match_ground_truth.
+//
+// Semantics (tests/match_designs.py proves the expected answers in exact arithmetic):
+//   * detection i belongs to image b = dt_image[i]; its candidates are gt[gt_off[b] .. gt_off[b + 1]);
+//   * iou is boxes.iou's float64 arithmetic, operation by operation (this file is built with -ffp-contract=off: no fused
+//     multiply-add; the float64 divide is the correctly rounded one);
+//   * best[i] is the largest iou, owner[i] the FIRST candidate that reaches it, counted inside the image's own list
+//     (np.argmax): a detection that overlaps nothing is owned by candidate 0;  no candidates: best 0, owner -1.
+//
+// One kernel, one thread per detection, 256 per workgroup.  A workgroup whose detections all belong to one image stages
+// that image's candidates through LDS, WB_MATCH_CHUNK = 64 boxes at a time: 64 boxes are 256 doubles, ONE coalesced 8-byte
+// load per thread, and every thread then reads the same box at the same time, which the LDS serves as a broadcast (no bank
+// conflict whatever the chunk size).  2 KiB per workgroup is never what limits the workgroups of a CU (160 KiB of LDS
+// against at most 8 workgroups of 256), so a larger chunk would only save barriers: an image seldom has more than 64
+// ground-truth boxes, which makes it one load, two barriers.  A workgroup that straddles images reads its candidates from
+// global memory, every thread its own range (neighbouring threads mostly the same addresses).
+//
+// Whatever dt_image and gt_off hold, nothing outside the buffers is read: the image is clamped to [0, n_images), both ends
+// of a range to [0, n_gt], and an end in front of its start gives an empty range.  Every loop is bounded by n_gt.
+#include "wb_common.h"
+
+#define WB_MATCH_MAX (1 << 26)      // most detections of one call (what one detect call can return)
+#define WB_MATCH_CHUNK 64           // candidates staged in LDS at a time: 4 * 64 doubles = one per thread
+
+namespace {
+
+struct MatchRange {
+    int64_t lo, hi;
+};
+
+__device__ inline MatchRange match_range(const int32_t *gt_off, int32_t b, int64_t n_gt) {
+    int64_t lo = gt_off[b], hi = gt_off[b + 1];
+    lo = lo < 0 ? 0 : (lo > n_gt ? n_gt : lo);
+    hi = hi < 0 ? 0 : (hi > n_gt ? n_gt : hi);
+    if (hi < lo) hi = lo;
+    return {lo, hi};
+}
+
+// boxes.iou, operation by operation
+__device__ inline double match_iou(double ax1, double ay1, double ax2, double ay2, double area_a, double bx1, double by1,
+                                   double bx2, double by2) {
+    double iw = (ax2 < bx2 ? ax2 : bx2) - (ax1 > bx1 ? ax1 : bx1);
+    double ih = (ay2 < by2 ? ay2 : by2) - (ay1 > by1 ? ay1 : by1);
+    iw = iw < 0.0 ? 0.0 : iw;
+    ih = ih < 0.0 ? 0.0 : ih;
+    const double inter = iw * ih;
+    const double area_b = (bx2 - bx1) * (by2 - by1);
+    const double uni = area_a + area_b - inter;
+    return uni > 0.0 ? inter / uni : 0.0;
+}
+
+__global__ __launch_bounds__(256) void match_kernel(const double *dt, const int32_t *dt_image, const double *gt,
+                                                    const int32_t *gt_off, int64_t n_dt, int64_t n_gt, int n_images,
+                                                    double *best, int32_t *owner) {
+    __shared__ double sg[4 * WB_MATCH_CHUNK];
+    __shared__ int32_t s_first, s_mixed;
+    const uint32_t tid = threadIdx.x;
+    const int64_t i = (int64_t)blockIdx.x * 256 + tid;
+    const bool live = i < n_dt;
+    const int64_t ii = live ? i : n_dt - 1;                    // (threads behind the last detection walk with it)
+    int32_t b = dt_image[ii];
+    b = b < 0 ? 0 : (b >= n_images ? n_images - 1 : b);
+    if (tid == 0) {
+        s_first = b;
+        s_mixed = 0;
+    }
+    __syncthreads();
+    if (b != s_first) s_mixed = 1;                             // (every writer writes the same value)
+    __syncthreads();
+    const bool one_image = s_mixed == 0;                       // (workgroup-uniform)
+    const MatchRange r = match_range(gt_off, b, n_gt);
+    const double ax1 = dt[4 * ii], ay1 = dt[4 * ii + 1], ax2 = dt[4 * ii + 2], ay2 = dt[4 * ii + 3];
+    const double area_a = (ax2 - ax1) * (ay2 - ay1);
+    double bestv = -1.0;                                       // (an iou is never negative and never NaN: the first candidate takes it)
+    int32_t own = -1;
+    if (one_image) {
+        for (int64_t c0 = r.lo; c0 < r.hi; c0 += WB_MATCH_CHUNK) {     // (r is the same in every thread)
+            const uint32_t m = r.hi - c0 < WB_MATCH_CHUNK ? (uint32_t)(r.hi - c0) : (uint32_t)WB_MATCH_CHUNK;
+            __syncthreads();                                   // the last chunk has been read by everyone
+            if (tid < 4u * m) sg[tid] = gt[4 * c0 + tid];
+            __syncthreads();
+            for (uint32_t k = 0; k < m; ++k) {
+                const double v = match_iou(ax1, ay1, ax2, ay2, area_a, sg[4 * k], sg[4 * k + 1], sg[4 * k + 2], sg[4 * k + 3]);
+                if (v > bestv) {
+                    bestv = v;
+                    own = (int32_t)(c0 - r.lo) + (int32_t)k;
+                }
+            }
+        }
+    } else {
+        for (int64_t c = r.lo; c < r.hi; ++c) {
+            const double v = match_iou(ax1, ay1, ax2, ay2, area_a, gt[4 * c], gt[4 * c + 1], gt[4 * c + 2], gt[4 * c + 3]);
+            if (v > bestv) {
+                bestv = v;
+                own = (int32_t)(c - r.lo);
+            }
+        }
+    }
+    if (live) {
+        best[i] = own < 0 ? 0.0 : bestv;
+        owner[i] = own;
+    }
+}
+
+}  // namespace
+
+extern "C" int wb_match_launch(void *stream, const double *dt, const int32_t *dt_image, const double *gt, const int32_t *gt_off,
+                               int64_t n_dt, int64_t n_gt, int n_images, double *best, int32_t *owner) {
+    WB_REQUIRE(n_dt >= 0 && n_gt >= 0 && n_images >= 0, "wb_match_launch: n_dt = %lld, n_gt = %lld, n_images = %d: negative",
+               (long long)n_dt, (long long)n_gt, n_images);
+    if (n_dt == 0) return WB_OK;
+    WB_REQUIRE(dt && dt_image && gt_off && best && owner && (gt || n_gt == 0), "wb_match_launch: null pointer");
+    WB_REQUIRE(n_images >= 1, "wb_match_launch: %lld detections of no image", (long long)n_dt);
+    WB_REQUIRE(reinterpret_cast<uintptr_t>(dt) % 8 == 0 && reinterpret_cast<uintptr_t>(gt) % 8 == 0 &&
+                   reinterpret_cast<uintptr_t>(best) % 8 == 0,
+               "wb_match_launch: dt, gt and best must be 8-byte aligned");
+    WB_REQUIRE(reinterpret_cast<uintptr_t>(dt_image) % 4 == 0 && reinterpret_cast<uintptr_t>(gt_off) % 4 == 0 &&
+                   reinterpret_cast<uintptr_t>(owner) % 4 == 0,
+               "wb_match_launch: dt_image, gt_off and owner must be 4-byte aligned");
+    if (n_dt > WB_MATCH_MAX) {
+        wb_set_error("wb_match_launch: %lld detections (at most %d in one call)", (long long)n_dt, WB_MATCH_MAX);
+        return WB_ERR_UNSUPPORTED;
+    }
+    hipLaunchKernelGGL(match_kernel, dim3((uint32_t)((n_dt + 255) / 256)), dim3(256), 0, (hipStream_t)stream, dt, dt_image, gt,
+                       gt_off, n_dt, n_gt, n_images, best, owner);
+    WB_HIP_CHECK(hipGetLastError());
+    return WB_OK;
+}
