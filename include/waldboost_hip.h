@@ -608,6 +608,37 @@ int wb_cart_level_launch(void *stream, const float *xt, int64_t n_samples, int64
                          const int32_t *begin, const int32_t *end, const uint64_t *t0, const uint64_t *t1, double scale,
                          int min_samples_leaf, int child_base, void *scratch, size_t scratch_bytes, WbCartSplit *splits);
 
+/* CNN re-scoring of detection windows: out[i] = cnn(X[i]) + scores_in[i], the forward pass of the reference's
+ * verification.model_cnn (reference verification.py:28-56) for a window shape (m, n, C).  New symbols of ABI 8 (the version
+ * number did not change: nothing that existed did).  The arithmetic contract is stated at the head of csrc/wb_verify.hip:
+ * every pre-activation one float32 fmaf chain in a fixed order, so a window's result depends on nothing but the window.
+ *
+ * Supported: 2 <= m, n <= 32, 1 <= C <= 16 (WB_ERR_UNSUPPORTED otherwise, from all three entry points).
+ * m2 = m / 2, n2 = n / 2, F = m2 * n2 * 16.
+ *
+ * The packed float32 weight buffer (wb_verify_weights_floats gives its length), batch normalisation already folded in
+ * (W' = float32(W * s[o]), b' = float32((b - mean) * s + beta), s = gamma / sqrt(variance + epsilon), in float64):
+ *   conv1  W' [3][3][C][8]   then b' [8]
+ *   conv2  W' [3][3][8][8]   then b' [8]
+ *   conv3  W' [3][3][8][16]  then b' [16]
+ *   conv4  W' [3][3][16][16] then b' [16]
+ *   dense0 kernel [F][128] (row = flat (row, column, channel) index of the pooled 16-channel map) then bias [128]
+ *   dense1 kernel [128] then bias [1]
+ * The convolution kernels keep Keras's (ky, kx, input channel, output channel) order; every value must be finite.
+ *
+ *   X          dev [n_windows][m][n][C], x_dtype WB_DTYPE_F32 (4-byte aligned) or WB_DTYPE_U8 (widened exactly)
+ *   weights    dev float32, 16-byte aligned, the packed buffer
+ *   scores_in  dev float32 [n_windows];  out dev float32 [n_windows]: every entry written, nothing behind them
+ *   scratch    dev, 16-byte aligned, wb_verify_scratch_bytes(m, n, C, n_windows) bytes: the features [n_windows][F].
+ *              Nothing in it needs clearing between calls.
+ * n_windows == 0 launches nothing (WB_OK, pointers not looked at); more than 2^26 windows or another x_dtype is
+ * WB_ERR_UNSUPPORTED; null pointers, misaligned pointers, a negative count and a short scratch are WB_ERR_INVALID.  Two
+ * launches, no host synchronisation. */
+int wb_verify_weights_floats(int m, int n, int C, int64_t *count);
+int wb_verify_scratch_bytes(int m, int n, int C, int64_t n_windows, size_t *bytes);
+int wb_verify_launch(void *stream, const void *X, int x_dtype, int64_t n_windows, int m, int n, int C, const float *weights,
+                     const float *scores_in, void *scratch, size_t scratch_bytes, float *out);
+
 /* Device self-test: the uint8 fast path of the orientation projection (fp32 arithmetic that is
  * proven equal to the reference's fp64 formula for integer gradients) is compared with the fp64
  * formula for every (gx, gy) in [-1020, 1020]^2; *mismatches (dev uint32, zeroed by the caller)

@@ -112,6 +112,9 @@ SYMBOLS = {
     "wb_cart_scratch_bytes": (C.c_int, [C.c_int64, C.c_int, C.POINTER(C.c_size_t)]),
     "wb_cart_level_launch": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, C.c_double,
                                        C.c_int, C.c_int, _P, C.c_size_t, _P]),
+    "wb_verify_weights_floats": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
+    "wb_verify_scratch_bytes": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int64, C.POINTER(C.c_size_t)]),
+    "wb_verify_launch": (C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_size_t, _P]),
 }
 
 _lib = None

@@ -1,0 +1,284 @@
+"""CNN verification -- drop-in for the inference side of ``waldboost.verification``: a small CNN re-scores the
+windows a cascade lets through, ``p(X, H) = sigmoid(cnn(X) + H)`` (reference verification.py:1-16).
+
+What runs where:
+
+* the forward pass of ``model_cnn`` (reference verification.py:28-56) is two HIP kernels behind ``wb_verify_launch``
+  (csrc/wb_verify.hip), on crops that are already on the GPU;
+* ``Verifier`` holds the network's 28 arrays as Keras orders them (``model_cnn(...).get_weights()`` of the reference),
+  folds batch normalisation into the convolutions once, on the host, in float64, and uploads the packed result once
+  per device;
+* ``detect_and_verify`` (reference verification.py:85-105, with ``get_boxes`` for its ``get_bbs`` slip) scans the image
+  like ``samples.get_samples_from_image`` does and gathers the crops of every detection on the device: they never travel
+  to the host;
+* ``train`` is not here: the backward pass is out of scope.  Train with the reference and import the result with
+  ``Verifier.from_keras_weights(input_shape, M.get_weights())``.
+
+The arithmetic is fixed to the bit: every pre-activation is one float32 fused-multiply-add chain in a
+stated order, so a window's result depends neither on the batch it sits in nor on the run.  It differs from Keras's own
+float32 evaluation (batch normalisation applied after the convolution, accumulation order of its backend) by rounding.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _native as nat
+
+HIDDEN = 128
+_CONV_OUT = (8, 8, 16, 16)
+_SCRATCH_BYTES = 256 << 20          # predict's chunks keep the feature scratch at or below this
+
+
+def _conv_in(C_in):
+    return (int(C_in), 8, 8, 16)
+
+
+def _flat_features(input_shape):
+    m, n, _ = input_shape
+    return (m // 2) * (n // 2) * 16
+
+
+def _expected_shapes(input_shape):
+    """Shapes of the 28 arrays of model_cnn(input_shape).get_weights(), in Keras's order."""
+    shapes = []
+    for cin, cout in zip(_conv_in(input_shape[2]), _CONV_OUT):
+        shapes += [(3, 3, cin, cout)] + [(cout,)] * 5      # kernel, bias, gamma, beta, moving_mean, moving_variance
+    F = _flat_features(input_shape)
+    return shapes + [(F, HIDDEN), (HIDDEN,), (HIDDEN, 1), (1,)]
+
+
+def fold_batchnorm(kernel, bias, gamma, beta, mean, variance, epsilon):
+    """(W', b') float32 of one convolution block: s = gamma / sqrt(variance + epsilon), W' = W * s[o],
+    b' = (b - mean) * s + beta, in float64, rounded to float32 once."""
+    f8 = lambda a: np.asarray(a, np.float64)
+    with np.errstate(all="ignore"):
+        s = f8(gamma) / np.sqrt(f8(variance) + float(epsilon))
+        return (f8(kernel) * s).astype(np.float32), ((f8(bias) - f8(mean)) * s + f8(beta)).astype(np.float32)
+
+
+class Verifier:
+    """The verification CNN for windows of `input_shape` = (m, n, C).  `arrays`: the 28 float arrays of the reference's
+    model_cnn(input_shape).get_weights(); they are copied and kept unfolded (get_weights, save)."""
+
+    def __init__(self, input_shape, arrays, epsilon=1e-3):
+        shape = tuple(int(x) for x in input_shape)
+        if len(shape) != 3 or min(shape) < 1:
+            raise ValueError(f"input_shape must be (m, n, C), got {input_shape!r}")
+        arrays = list(arrays)
+        want = _expected_shapes(shape)
+        if len(arrays) != len(want):
+            raise ValueError(f"expected the {len(want)} arrays of model_cnn(...).get_weights(), got {len(arrays)}")
+        kept = []
+        for k, (a, w) in enumerate(zip(arrays, want)):
+            a = np.array(a, dtype=np.float32)
+            if a.shape != w:
+                raise ValueError(f"array {k} has shape {a.shape}, expected {w} for input_shape {shape}")
+            if not np.isfinite(a).all():
+                raise ValueError(f"array {k} holds non-finite values")
+            a.setflags(write=False)
+            kept.append(a)
+        self.input_shape = shape
+        self.epsilon = float(epsilon)
+        self.arrays = kept
+        self._packed = self._fold()
+        self._device = {}           # device index -> packed weights
+        self._scratch = {}          # device index -> feature scratch
+
+    # ---- construction, files
+    @staticmethod
+    def from_keras_weights(input_shape, arrays, epsilon=1e-3):
+        """From model_cnn(input_shape).get_weights() of the reference: per convolution block kernel (3, 3, Cin, Cout), bias,
+        gamma, beta, moving_mean, moving_variance; then the dense kernel (F, 128), its bias, the dense kernel (128, 1), its bias."""
+        return Verifier(input_shape, arrays, epsilon)
+
+    def get_weights(self):
+        return [a.copy() for a in self.arrays]
+
+    def save(self, filename):
+        """.npz, no pickle."""
+        np.savez(filename, input_shape=np.array(self.input_shape, np.int64), epsilon=np.float64(self.epsilon),
+                 **{f"w{k:02d}": a for k, a in enumerate(self.arrays)})
+
+    @staticmethod
+    def load(filename):
+        with np.load(filename, allow_pickle=False) as z:
+            keys = sorted(k for k in z.files if k.startswith("w"))
+            return Verifier(tuple(int(x) for x in z["input_shape"]), [z[k] for k in keys], float(z["epsilon"]))
+
+    # ---- weights
+    def _fold(self):
+        """The packed float32 buffer wb_verify_launch reads (include/waldboost_hip.h has the layout)."""
+        parts = []
+        for k in range(4):
+            w, b = fold_batchnorm(*self.arrays[6 * k:6 * k + 6], self.epsilon)
+            parts += [w.reshape(-1), b]
+        parts += [self.arrays[24].reshape(-1), self.arrays[25], self.arrays[26].reshape(-1), self.arrays[27]]
+        packed = np.ascontiguousarray(np.concatenate(parts), np.float32)
+        if not np.isfinite(packed).all():
+            raise ValueError("folding batch normalisation gives non-finite weights (moving_variance + epsilon must be positive)")
+        return packed
+
+    def folded(self):
+        """[(W', b') of the four convolutions] + [dense0 kernel, bias, dense1 kernel, bias], float32 copies."""
+        out, at = [], 0
+        for cin, cout in zip(_conv_in(self.input_shape[2]), _CONV_OUT):
+            out.append((self._packed[at:at + 9 * cin * cout].reshape(3, 3, cin, cout).copy(),
+                        self._packed[at + 9 * cin * cout:at + 9 * cin * cout + cout].copy()))
+            at += 9 * cin * cout + cout
+        return out + [a.copy() for a in self.arrays[24:]]
+
+    def _weights_on(self, dev):
+        import torch
+        key = dev.index
+        if key not in self._device:
+            m, n, Cc = self.input_shape
+            count = C.c_int64()
+            nat.check(nat.load().wb_verify_weights_floats(m, n, Cc, C.byref(count)), "wb_verify_weights_floats")
+            assert count.value == self._packed.size, (count.value, self._packed.size)
+            self._device[key] = torch.from_numpy(self._packed).to(dev)
+        return self._device[key]
+
+    def _scratch_on(self, dev, nbytes):
+        import torch
+        have = self._scratch.get(dev.index)
+        if have is None or have.numel() < nbytes:
+            have = self._scratch[dev.index] = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+        return have
+
+    # ---- inference
+    def _checked(self, inputs):
+        import torch
+        try:
+            samples, scores = inputs
+        except (TypeError, ValueError):
+            raise ValueError("predict takes [samples, scores]") from None
+        on_device = isinstance(samples, torch.Tensor)
+        if not on_device:
+            samples = np.asarray(samples)
+        if not isinstance(scores, torch.Tensor):
+            scores = np.asarray(scores)
+        if len(samples.shape) != 4 or tuple(samples.shape[1:]) != self.input_shape:
+            raise ValueError(f"samples of shape {tuple(samples.shape)}, expected (N,) + {self.input_shape}")
+        dt = np.dtype(str(samples.dtype).replace("torch.", "")) if on_device else np.asarray(samples).dtype
+        if dt not in (np.float32, np.uint8):
+            raise NotImplementedError(f"samples must be float32 or uint8, got {dt}")
+        if not on_device:
+            samples = np.ascontiguousarray(samples)
+            if dt == np.float32 and not np.isfinite(samples).all():
+                raise ValueError("samples hold non-finite values")
+        N = int(samples.shape[0])
+        if tuple(scores.shape) not in ((N,), (N, 1)):
+            raise ValueError(f"scores of shape {tuple(scores.shape)}, expected ({N},) or ({N}, 1)")
+        return samples, scores, N, dt
+
+    def predict_device(self, inputs, batch_size=None):
+        """predict with the result left on the device: a float32 tensor (N, 1).  No host synchronisation when samples and
+        scores are device tensors."""
+        import torch
+        samples, scores, N, dt = self._checked(inputs)
+        if batch_size is not None and int(batch_size) < 1:
+            raise ValueError("batch_size must be positive")
+        lib = nat.load()
+        dev = nat.require_gpu()
+        m, n, Cc = self.input_shape
+        weights = self._weights_on(dev)                     # (refuses a window shape the kernels do not take)
+        tdt, wdt = (torch.uint8, nat.WB_DTYPE_U8) if dt == np.uint8 else (torch.float32, nat.WB_DTYPE_F32)
+        X = (samples if isinstance(samples, torch.Tensor) else torch.from_numpy(samples)).to(dev, tdt).contiguous()
+        H = scores if isinstance(scores, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(scores, np.float32))
+        H = H.to(dev, torch.float32).reshape(-1).contiguous()
+        out = torch.empty((N, 1), dtype=torch.float32, device=dev)
+        if N == 0:
+            return out
+        F = _flat_features(self.input_shape)
+        chunk = int(batch_size) if batch_size is not None else max(64, _SCRATCH_BYTES // (4 * F) // 64 * 64)
+        chunk = min(chunk, N)
+        need = C.c_size_t()
+        nat.check(lib.wb_verify_scratch_bytes(m, n, Cc, chunk, C.byref(need)), "wb_verify_scratch_bytes")
+        scratch = self._scratch_on(dev, need.value)
+        flat = out.reshape(-1)
+        for at in range(0, N, chunk):
+            k = min(chunk, N - at)
+            nat.check(lib.wb_verify_launch(nat.stream_ptr(), nat.ptr(X[at:]), wdt, k, m, n, Cc, nat.ptr(weights), nat.ptr(H[at:]),
+                                           nat.ptr(scratch), scratch.numel(), nat.ptr(flat[at:])), "wb_verify_launch")
+        return out
+
+    def predict(self, inputs, batch_size=None):
+        """cnn(samples) + scores as float32 (N, 1), the shape Keras's predict returns.  inputs = [samples, scores]: samples
+        (N, m, n, C) float32 or uint8, ndarray or device tensor; scores (N,) or (N, 1).  batch_size: windows per launch
+        (None: as many as keep the scratch bounded); the result does not depend on it."""
+        return self.predict_device(inputs, batch_size).cpu().numpy()
+
+
+def model_cnn(input_shape, seed=None):
+    """A Verifier with Keras's default initialisers (reference verification.py:28-56): glorot-uniform kernels, zero biases,
+    batch normalisation gamma 1, beta 0, moving_mean 0, moving_variance 1.  The generator is NumPy's (`seed`)."""
+    rng = np.random.default_rng(seed)
+
+    def glorot(shape, fan_in, fan_out):
+        limit = np.sqrt(6.0 / (fan_in + fan_out))
+        return rng.uniform(-limit, limit, shape).astype(np.float32)
+
+    arrays = []
+    for cin, cout in zip(_conv_in(input_shape[2]), _CONV_OUT):
+        arrays += [glorot((3, 3, cin, cout), 9 * cin, 9 * cout), np.zeros(cout, "f"), np.ones(cout, "f"), np.zeros(cout, "f"),
+                   np.zeros(cout, "f"), np.ones(cout, "f")]
+    F = _flat_features(input_shape)
+    arrays += [glorot((F, HIDDEN), F, HIDDEN), np.zeros(HIDDEN, "f"), glorot((HIDDEN, 1), HIDDEN, 1), np.zeros(1, "f")]
+    return Verifier(input_shape, arrays)
+
+
+def exploss(y_true, y_pred):
+    """The reference's training loss (verification.py:59-60), in NumPy."""
+    return np.maximum(np.minimum(np.exp(-np.asarray(y_true) * np.asarray(y_pred)), 1e3), 1e-6)
+
+
+def train(*args, **kwargs):
+    raise NotImplementedError(
+        "waldboost_amd.verification has the forward pass only: train the verifier with the reference "
+        "(waldboost.verification.train) and import the result with Verifier.from_keras_weights(input_shape, M.get_weights())")
+
+
+def detect_and_verify(image, model, verifier):
+    """Detections of `model` on `image`, re-scored by `verifier` (reference verification.py:85-105): (bbs, scores), a
+    float32 (N, 4) array and a float32 (N,) array in Model.detect's order (levels in pyramid order, row-major inside a
+    level); ([], []) when nothing is detected.  The scan is samples.get_samples_from_image's route (float channels, not
+    rank bytes); the crops are gathered from the resident pyramid and stay on the device.  One upload (the window origins
+    and scores) and two host waits: the scan's read-back and the scores.  n_loc / n_weak advance as in a scan."""
+    import torch
+    from . import channels as _channels
+    from . import engine as _engine
+    if tuple(int(x) for x in model.shape) != verifier.input_shape:
+        raise ValueError(f"the model's window shape {tuple(model.shape)} is not the verifier's input_shape {verifier.input_shape}")
+    _channels._validate_image(image)
+    shrink, n_per_oct, smooth, spec = _channels.read_opts(model.channel_opts)
+    if spec.dtype == np.uint8:
+        _channels._require_u8(image, spec.key)
+    eng = _engine.get_engine(image.shape[0], image.shape[1], image.dtype, shrink, n_per_oct, smooth, 1, channels=spec)
+    if eng.plan.n_levels == 0:
+        return [], []
+    eng.load_images(image)
+    eng.run_channels()
+    found = model.scan_engine(eng)                          # wait 1: detections, in (level, r, c) order
+    N = int(found["scores"].size)
+    if N == 0:
+        return [], []
+    lib = nat.load()
+    dev = nat.require_gpu()
+    m, n, Cc = verifier.input_shape
+    tdt, wdt = (torch.uint8, nat.WB_DTYPE_U8) if spec.dtype == np.uint8 else (torch.float32, nat.WB_DTYPE_F32)
+    # rows, columns and score bits in one upload
+    host = np.stack([found["r"].astype(np.int32), found["c"].astype(np.int32),
+                     np.ascontiguousarray(found["scores"], np.float32).view(np.int32)])
+    sent = torch.from_numpy(host).to(dev)
+    crops = torch.empty((N, m, n, Cc), dtype=tdt, device=dev)
+    level = found["level"]
+    cuts = np.flatnonzero(np.diff(level, prepend=-1, append=-1))      # starts of the runs of one level, then N
+    for a, b in zip(cuts[:-1], cuts[1:]):
+        chns = eng.level_tensor(0, int(level[a]))
+        assert chns.is_contiguous() and chns.dtype == tdt
+        u, v, _ = (int(x) for x in chns.shape)
+        nat.check(lib.wb_gather_samples_launch(nat.stream_ptr(), nat.ptr(chns), wdt, u, v, Cc, nat.ptr(sent[0, a:]),
+                                               nat.ptr(sent[1, a:]), int(b - a), m, n, nat.ptr(crops[a:])),
+                  "wb_gather_samples_launch")
+    scores = verifier.predict_device([crops, sent[2].view(torch.float32)])
+    return found["boxes"], scores.cpu().numpy().reshape(-1)              # wait 2
