@@ -48,14 +48,16 @@ Counts the host test measures (its assertions are the inequalities; these are th
   held_quads 37 x 50     no wrap: int8 284, int16 295, uint16 523, int32 287, uint32 527 pixels; floor instead of trunc:
                          int8 256, int16 272, int32 254, int64 271; one float16 rounding 269; float64 row-first 103,
                          pairwise 147, reversed 212 (batch 1; three times that at batch 3)
-  key faults             cases (of the 198 `extremes` and `tail_bait` ones) with a changed key: wave 0 / 1 / 2 / 3 dropped
-                         178 / 96 / 106 / 56 (wave 0 owns the background's first pixel too), lane 0 only 175, image 1 or 2
-                         written to image 0's words 52 each, padding admitted 103, odd tails admitted 28; a dropped octave
-                         slot shows in every case that has the octave (slot 8: the 2048 x 2064 ones)
+  key faults             cases (of the 214 `extremes` and `tail_bait` ones) with a changed key: wave 0 / 1 / 2 / 3 dropped
+                         214 / 109 / 115 / 65 (wave 0 owns the background's first pixel too), lane 0 only 208, image 1 or 2
+                         written to image 0's words 52 each, padding admitted 126, odd tails admitted 30; a dropped octave
+                         slot shows in every case that has the octave (slot 8: the 2048 x 2064 and 2048 x 8208 ones)
+  tail waves             TAIL_WAVE_SHAPES, 8 cases each (of the 254 in all): the tail octave is 8 x 32, wave w owns rows 2 w and
+                         2 w + 1; a tail kernel that drops wave w's partial changes that octave's key on the 4 cases with
+                         an extreme in wave w, for every w (every other tail octave of the cases holds 64 pixels, wave 0's)
 
-Not exposed by any design: none of KEY_FAULTS / PIXEL_FAULTS.  Outside that list, and not designed for: a tail kernel whose
-waves 1 .. 3 lose their partial (the tail octaves of the cases hold 64 pixels, one wave's), and the 48 KiB dynamic-LDS
-branch of the tail launch (it needs a float32 image of 160 MB: 1024 x 39424; left out).
+Not exposed by any design: none of KEY_FAULTS / PIXEL_FAULTS.  Outside that list, and not designed for: the 48 KiB
+dynamic-LDS branch of the tail launch (it needs a float32 image of 160 MB: 1024 x 39424; left out).
 """
 import functools
 
@@ -64,6 +66,9 @@ import numpy as np
 from oracle import wb_oracle as orc
 
 BLOCK = {"uint8": (128, 7), "float32": (64, 6)}          # block side at octave 0, octaves derived inside the block
+# the smallest shapes whose tail octave (float32: 7, uint8: 8) is 8 x 32 = 256 pixels: one per thread of octaves_tail_kernel,
+# 64 per wave (a tail octave of 64 pixels is wave 0's alone)
+TAIL_WAVE_SHAPES = (("float32", 1024, 4112), ("uint8", 2048, 8208))
 HELD = ("int8", "int16", "uint16", "int32", "uint32", "int64", "bool", "float16", "float64")
 PIXEL_FAULTS = ("nowrap", "lane_carry", "rowfirst", "pairwise", "reversed", "floor", "single_f16")
 KEY_FAULTS = ([("wave", w) for w in range(4)] + [("slot", j) for j in range(9)] + [("lane0",), ("image", 1), ("image", 2),
@@ -269,10 +274,11 @@ def true_keys(octs):
     return [(o.min(), o.max()) for o in octs]
 
 
-def emulated_keys(dtype, images, paths, fault):
+def emulated_keys(dtype, images, paths, fault, only=None):
     """[image][octave] -> (min, max) or None (the words stay zero), as a kernel with `fault` (KEY_FAULTS) in its reduction
     would report them: a wave's partial dropped, an octave's slot dropped, only lane 0's value kept, image b's keys
-    written to image 0's words, padded pixels or the odd tails admitted."""
+    written to image 0's words, padded pixels or the odd tails admitted.  `only`: the octaves the fault acts in (the
+    others keep their true keys)."""
     dtype = str(dtype)
     B, H, W = images.shape
     out = []
@@ -281,7 +287,9 @@ def emulated_keys(dtype, images, paths, fault):
         keys = []
         for k, o in enumerate(stored):
             vals = o
-            if fault[0] == "wave" or fault[0] == "lane0":
+            if only is not None and k not in only:
+                pass
+            elif fault[0] == "wave" or fault[0] == "lane0":
                 own = owner_map(dtype, H, W, k, paths[b])
                 vals = o[own["wave"] != fault[1]] if fault[0] == "wave" else o[own["lane"] == 0]
             elif fault[0] == "padding":
@@ -559,7 +567,7 @@ def _case(design, dtype, H, W, B, **args):
 def _extreme_cases():
     """The ownership sweep.  Per (dtype, shape, k): extremes in wave w of the first workgroup and wave w + 1 of the last, and
     the other way round, for every wave the two workgroups have at that octave; the wave-0 walk and tail octaves with one
-    extreme in the first and one in the last workgroup; batches of 3 with the maximum alone in image b and the minimum
+    extreme in the first and one in the last workgroup; waves w and w + 1 of the tail kernel; batches of 3 with the maximum alone in image b and the minimum
     alone in image b + 1."""
     out = []
 
@@ -592,6 +600,12 @@ def _extreme_cases():
                 continue                                      # (1024 x 1040 holds the walk)
             add(dtype, H, W, 1, k, ("first", None), ("last", None))
             add(dtype, H, W, 1, k, ("last", None), ("first", None))
+    # the tail kernel's four waves: extremes in wave w and wave w + 1 of its one workgroup, both ways round
+    for dtype, H, W in TAIL_WAVE_SHAPES:
+        k = tail_octaves(dtype, len(octave_dims(H, W)))[-1]
+        for w in range(4):
+            add(dtype, H, W, 1, k, ("any", w), ("any", (w + 1) % 4))
+            add(dtype, H, W, 1, k, ("any", (w + 1) % 4), ("any", w))
     # batches of 3: 200 x 208 and 72 x 80 / 73 x 80 (image 1 leaves the regs path), float32, and two held dtypes
     for dtype, H, W, ks in (("uint8", 200, 208, (0, 1, 4)), ("uint8", 72, 80, (0, 1, 3)), ("uint8", 73, 80, (1,)), ("float32", 100, 108, (0, 1, 3)),
                             ("int16", 40, 76, (0, 1, 2)), ("float64", 40, 76, (0, 1, 2))):

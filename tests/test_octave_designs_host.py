@@ -25,7 +25,8 @@ def test_closed_form_equals_the_oracle(case):
     imgs, ref = od.images(case), od.reference(case)
     dtype, H, W, B = case["dtype"], case["H"], case["W"], case["B"]
     dims = od.octave_dims(H, W)
-    assert imgs.shape == (B, H, W) and imgs.dtype == np.dtype(dtype) and imgs.nbytes <= 5 << 20
+    # (the tail-wave shapes are the smallest with a 256-pixel tail octave: 16.1 MiB; every other image stays within 5 MiB)
+    assert imgs.shape == (B, H, W) and imgs.dtype == np.dtype(dtype) and imgs.nbytes <= (17 if (dtype, H, W) in od.TAIL_WAVE_SHAPES else 5) << 20
     for b in range(B):
         assert [o.shape for o in ref[b]] == dims
         # the pooling restated: block by block with zero padding, then the tail's floor chain
@@ -294,6 +295,28 @@ def test_each_wrong_reduction_changes_a_key(fault):
         # a dropped wave shows in the block kernel for bytes on every path and for floats, and in the held dtypes' kernels
         assert any("-uint8-200x208x1" in h for h in hit) and any("-uint8-201x213x1" in h for h in hit)
         assert any("-float32-" in h for h in hit) and any("-int16-" in h or "-float64-" in h for h in hit)
+
+
+@pytest.mark.parametrize("shape", od.TAIL_WAVE_SHAPES, ids=lambda s: "-".join(map(str, s)))
+def test_tail_wave_sweep_exposes_each_wave_of_the_tail_kernel(shape):
+    """A tail kernel that drops wave w's partial reports another key for the tail octave on at least one case of the
+    sweep, for every w: the octave holds one pixel per thread, 64 per wave, and the extremes sit in single pixels."""
+    dtype, H, W = shape
+    cases = [c for c in od.CASES if c["design"] == "extremes" and (c["dtype"], c["H"], c["W"]) == shape]
+    k = od.tail_octaves(dtype, len(od.octave_dims(H, W)))[-1]
+    own = od.owner_map(dtype, H, W, k)
+    assert own["kernel"] == "tail" and own["wave"].shape == (8, 32) and all(int((own["wave"] == w).sum()) == 64 for w in range(4))
+    assert len(cases) == 8 and all(c["args"]["k"] == k and c["B"] == 1 for c in cases)
+    waves = [tuple(int(own["wave"][c["args"][e][1:]]) for e in ("hi", "lo")) for c in cases]
+    assert set(waves) == {(w, (w + 1) % 4) for w in range(4)} | {((w + 1) % 4, w) for w in range(4)}
+
+    def changed(c, w):
+        wrong = od.emulated_keys(dtype, od.images(c), ["scalar"], ("wave", w), only=(k,))
+        true = od.true_keys(od.reference(c)[0])
+        assert wrong[0][:k] == true[:k]
+        return wrong[0][k] != true[k]
+    for w in range(4):
+        assert any(changed(c, w) for c in cases), (shape, w)
 
 
 def test_a_right_reduction_changes_nothing():

@@ -11,6 +11,10 @@
 // minmax encoding: mm[0] = max over ~key(pixel)  (so min key = ~mm[0]),  mm[1] = max over key;
 // both are plain atomicMax on a word the CALLER has zeroed (like the cascade's counters: one memset of one
 // control block per step can then serve every kernel of the step).
+//
+// The pieces, each written once: KeyRange (the running key range and its wave reduction), commit_key_ranges (a
+// workgroup's ranges -> atomics), pool_step (one octave from the one before), the loaders of octave 0
+// (load_block_regs, load_block_lds) and zero_by_first_workgroup.
 #include "wb_common.h"
 
 namespace {
@@ -40,30 +44,178 @@ template <> __device__ inline float pool4<float>(float a, float b, float c, floa
     return (((a + b) + c) + d) * 0.25f;
 }
 
-// workgroup reduction of (lo-as-~key max, hi max) -> two atomics by thread 0 (one pair per wave was
-// measured 2x slower at batch 1: hundreds of atomics queue up on each octave's two words)
-__device__ inline void block_minmax_commit(uint32_t nlo, uint32_t hi, uint32_t *red, uint32_t *mm) {
+// The key range of a set of pixels in the minmax encoding: nlo = max over ~key, hi = max over key, both 0 for the empty
+// set (so an empty range merges and commits as nothing).  K: uint32_t keys, or the held dtypes' unsigned long long ones.
+template <typename K> struct KeyRange {
+    K nlo = 0, hi = 0;
+    __device__ void add(K key) {
+        const K nk = ~key;
+        nlo = nk > nlo ? nk : nlo;
+        hi = key > hi ? key : hi;
+    }
+    __device__ void merge(const KeyRange &o) {
+        nlo = o.nlo > nlo ? o.nlo : nlo;
+        hi = o.hi > hi ? o.hi : hi;
+    }
+    // every lane of the (full) wave ends with the wave's range
+    __device__ void wave_reduce() {
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        uint32_t l2 = __shfl_xor(nlo, o), h2 = __shfl_xor(hi, o);
-        nlo = l2 > nlo ? l2 : nlo;
-        hi = h2 > hi ? h2 : hi;
-    }
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        red[2 * wave] = nlo;
-        red[2 * wave + 1] = hi;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < (int)(blockDim.x >> 6); ++w) {
-            nlo = red[2 * w] > nlo ? red[2 * w] : nlo;
-            hi = red[2 * w + 1] > hi ? red[2 * w + 1] : hi;
+        for (int o = 32; o > 0; o >>= 1) {
+            KeyRange other;
+            other.nlo = __shfl_xor(nlo, o);
+            other.hi = __shfl_xor(hi, o);
+            merge(other);
         }
-        atomicMax(mm + 0, nlo);
-        atomicMax(mm + 1, hi);
+    }
+};
+__device__ inline void add_bytes(KeyRange<uint32_t> &kr, uint32_t dword) {
+#pragma unroll
+    for (int bb = 0; bb < 4; ++bb) kr.add((dword >> (8 * bb)) & 255u);
+}
+
+// A workgroup's (256 threads) partial ranges of n consecutive octaves leave for mm ([octave][2]): wave reduction,
+// exchange through LDS (red: 4 * 2 * N words), then thread j commits word j -- ONE reduction and one atomic per value per
+// workgroup (one pair per wave was measured 2x slower at batch 1: hundreds of atomics queue up on each octave's two
+// words).  A zero is the empty range's and changes nothing: it is not sent.  One barrier inside; whoever calls again
+// keeps a barrier between this call's reads of `red` and the next one's writes.
+template <int N>
+__device__ inline void commit_key_ranges(KeyRange<uint32_t> (&part)[N], int n, uint32_t *red, uint32_t *mm) {
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+        part[j].wave_reduce();
+        if ((tid & 63) == 0) {
+            red[(tid >> 6) * 2 * N + 2 * j] = part[j].nlo;
+            red[(tid >> 6) * 2 * N + 2 * j + 1] = part[j].hi;
+        }
     }
     __syncthreads();
+    if (tid < 2 * n) {
+        uint32_t v = red[tid];
+#pragma unroll
+        for (int w = 1; w < 4; ++w) v = red[w * 2 * N + tid] > v ? red[w * 2 * N + tid] : v;
+        if (v) atomicMax(mm + tid, v);
+    }
+}
+
+// words a LATER kernel of the step accumulates into (the cascade's counters and statistics): nobody touches them while
+// the octave kernel runs, so its first workgroup resets them -- a step then needs no memset launch of its own
+__device__ inline void zero_by_first_workgroup(uint32_t *zero, int zero_words) {
+    if (blockIdx.x == 0 && blockIdx.y == 0)
+        for (int i = threadIdx.x; i < zero_words; i += 256) zero[i] = 0u;
+}
+
+// One octave from the one before: the 2x2 quads of `cur` (rows of `pitch` elements) pooled into the rows x cols pixels
+// of `nxt` and, where pixel (oy0 + r, ox0 + c) lies inside the oh x ow octave at `dst`, into HBM.  Returns the key range
+// of what went to HBM.  Thread t of the 256 takes pixels t, t + 256, ...  No synchronisation in here: the caller puts the
+// barrier it needs between this step's writes of `nxt` and the next step's reads.
+template <typename T>
+__device__ inline KeyRange<uint32_t> pool_step(const T *cur, int pitch, T *nxt, int rows, int cols, T *dst, int oh, int ow,
+                                               int oy0, int ox0) {
+    KeyRange<uint32_t> kr;
+    for (int i = threadIdx.x; i < rows * cols; i += 256) {
+        const int r = i / cols, c = i - r * cols;
+        const T *p0 = cur + (2 * r) * pitch + 2 * c;
+        const T v = pool4<T>(p0[0], p0[pitch], p0[1], p0[pitch + 1]);
+        nxt[i] = v;
+        const int y = oy0 + r, x = ox0 + c;
+        if (y < oh && x < ow) {
+            dst[(int64_t)y * ow + x] = v;
+            kr.add(PixKey<T>::key(v));
+        }
+    }
+    return kr;
+}
+
+// ---- octave 0 of a block, with its key range (all pixels, odd tails included).  Loads are unconditional (clamped
+//      addresses) and issued 8 at a time.
+
+// Bytes, rows 16-byte aligned (the usual image): a thread takes 16 pixels of TWO rows (two 16-byte loads, all of a
+// block's loads in flight at once), pools them into 8 pixels of octave 1 in registers -- two byte lanes per dword at a
+// time -- and stores those as two dwords: octave 0 never goes through LDS, octave 1 leaves with 8-byte instead of
+// 1-byte stores (at batch 1 the kernel is one round of workgroups whose serial depth is the image's octave chain).
+// lds1: octave 1 of the block, [OB/2][OB/2] bytes; dst1: the oh x ow octave 1 in HBM; k0, k1: the key ranges of both.
+__device__ inline void load_block_regs(const uint8_t *src, int H, int W, int y0, int x0, uint32_t *lds1, uint8_t *dst1,
+                                       int oh, int ow, KeyRange<uint32_t> &k0, KeyRange<uint32_t> &k1) {
+    constexpr int OB = Blk<uint8_t>::OB, NG = OB / 16, NITEM = (OB / 2) * NG, PER = NITEM / 256;
+    static_assert(NITEM % 256 == 0, "whole items per thread");
+    uint4 va[PER], vb[PER];
+    bool ok0[PER], ok1[PER];
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+        const int it = threadIdx.x + k * 256;
+        const int rp = it / NG, g = it - rp * NG;
+        const int ya = y0 + 2 * rp, yb = ya + 1, x = x0 + 16 * g;
+        ok0[k] = ya < H && x < W;
+        ok1[k] = yb < H && x < W;
+        const int yac = ya < H ? ya : H - 1, ybc = yb < H ? yb : H - 1, xc = x < W ? x : W - 16;
+        va[k] = *reinterpret_cast<const uint4 *>(src + (int64_t)yac * W + xc);
+        vb[k] = *reinterpret_cast<const uint4 *>(src + (int64_t)ybc * W + xc);
+    }
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+        const uint32_t a[4] = {va[k].x, va[k].y, va[k].z, va[k].w}, b[4] = {vb[k].x, vb[k].y, vb[k].z, vb[k].w};
+        uint32_t o[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (ok0[k]) add_bytes(k0, a[j]);
+            if (ok1[k]) add_bytes(k0, b[j]);
+            // two pooled pixels per dword: the byte pairs summed in 16-bit lanes ((a+b+c+d) & 255) >> 2
+            const uint32_t sum = (a[j] & 0x00ff00ffu) + ((a[j] >> 8) & 0x00ff00ffu) + (b[j] & 0x00ff00ffu) + ((b[j] >> 8) & 0x00ff00ffu);
+            o[j] = ((sum >> 2) & 0x3fu) | (((sum >> 18) & 0x3fu) << 8);
+        }
+        const uint32_t out0 = o[0] | (o[1] << 16), out1 = o[2] | (o[3] << 16);
+        const int it = threadIdx.x + k * 256;
+        const int rp = it / NG, g = it - rp * NG;
+        lds1[(rp * (OB / 2) + 8 * g) / 4] = out0;
+        lds1[(rp * (OB / 2) + 8 * g) / 4 + 1] = out1;
+        const int oy = (y0 >> 1) + rp, ox = (x0 >> 1) + 8 * g;
+        if (oy < oh && ox < ow) {                                  // (ow % 4 == 0 and ox % 8 == 0: whole dwords in or out)
+            uint32_t *gp = reinterpret_cast<uint32_t *>(dst1 + (int64_t)oy * ow + ox);
+            gp[0] = out0;
+            add_bytes(k1, out0);
+            if (ox + 4 < ow) {
+                gp[1] = out1;
+                add_bytes(k1, out1);
+            }
+        }
+    }
+}
+
+// Through LDS, in words V of a row: uint32_t (four bytes at once, for bytes whose rows are 4-byte aligned) or T itself.
+// Hv x Wv: the image in words, (y0, xv0): the block's origin in words; pixels outside the image are stored as zeros and
+// stay out of the range.
+template <typename T, typename V>
+__device__ inline KeyRange<uint32_t> load_block_lds(const V *src, int H, int Wv, int y0, int xv0, V *lds) {
+    constexpr int U = 8, OB = Blk<T>::OB, OBV = OB * (int)sizeof(T) / (int)sizeof(V);          // OBV: words per block row
+    KeyRange<uint32_t> kr;
+    for (int i0 = threadIdx.x; i0 < OB * OBV; i0 += 256 * U) {
+        V v[U];
+        bool ok[U];
+#pragma unroll
+        for (int k = 0; k < U; ++k) {
+            int i = i0 + k * 256;
+            i = i < OB * OBV ? i : OB * OBV - 1;
+            const int r = i / OBV, c = i - r * OBV;
+            int y = y0 + r, x = xv0 + c;
+            ok[k] = (y < H) && (x < Wv);
+            y = y < H ? y : H - 1;
+            x = x < Wv ? x : Wv - 1;
+            v[k] = src[(int64_t)y * Wv + x];
+        }
+#pragma unroll
+        for (int k = 0; k < U; ++k) {
+            const int i = i0 + k * 256;
+            if (i < OB * OBV) {
+                lds[i] = ok[k] ? v[k] : V(0);
+                if (ok[k]) {
+                    if constexpr (sizeof(V) == sizeof(T)) kr.add(PixKey<T>::key(v[k]));
+                    else add_bytes(kr, v[k]);
+                }
+            }
+        }
+    }
+    return kr;
 }
 
 struct OctDims {
@@ -76,270 +228,70 @@ template <typename T>
 __global__ __launch_bounds__(256) void octaves_block_kernel(const T *img, int64_t img_stride, T *oct, int64_t oct_stride,
                                                             OctDims d, int n_oct, int blocks_x, uint32_t *minmax,
                                                             uint32_t *zero, int zero_words) {
-    // words a LATER kernel of the step accumulates into (the cascade's counters and statistics): nobody touches them while
-    // this kernel runs, so its first workgroup resets them -- a step then needs no memset launch of its own
-    if (blockIdx.x == 0 && blockIdx.y == 0)
-        for (int i = threadIdx.x; i < zero_words; i += 256) zero[i] = 0u;
+    zero_by_first_workgroup(zero, zero_words);
     constexpr int OB = Blk<T>::OB, OB_LEVELS = Blk<T>::LEVELS;
     __shared__ __attribute__((aligned(16))) T bufA[OB * OB];
     __shared__ T bufB[(OB / 2) * (OB / 2)];
-    __shared__ uint32_t red[4][2 * (OB_LEVELS + 1)];      // per wave: (max ~key, max key) of octaves 0..OB_LEVELS
+    __shared__ uint32_t red[4 * 2 * (OB_LEVELS + 1)];     // per wave: (max ~key, max key) of octaves 0..OB_LEVELS
 
     const int b = blockIdx.y;
     const int by = blockIdx.x / blocks_x, bx = blockIdx.x - by * blocks_x;
     const int tid = threadIdx.x;
     const T *src = img + (int64_t)b * img_stride;
     T *obase = oct + (int64_t)b * oct_stride;
-    uint32_t *mm = minmax + (int64_t)b * n_oct * 2;
-
-    // ---- octave 0 block -> LDS, with its min/max (all pixels, odd tails included).  Loads are
-    //      unconditional (clamped addresses) and issued 8 at a time; bytes travel as dwords when the
-    //      rows are 4-byte aligned.
     const int H = d.h[0], W = d.w[0];
     const int y0 = by * OB, x0 = bx * OB;
-    uint32_t nlo = 0u, hi = 0u;
-    constexpr int U = 8;
-    // bytes, rows 16-byte aligned (the usual image): a thread takes 16 pixels of TWO rows (two 16-byte loads, all of a
-    // block's loads in flight at once), pools them into 8 pixels of octave 1 in registers -- two byte lanes per dword at a
-    // time -- and stores those as two dwords: octave 0 never goes through LDS, octave 1 leaves with 8-byte instead of
-    // 1-byte stores (at batch 1 the kernel is one round of workgroups whose serial depth is the image's octave chain)
-    bool from_regs = false;
-    uint32_t nlo1 = 0u, hi1 = 0u;
-    if constexpr (sizeof(T) == 1) {
-        T *dst1 = obase + (n_oct > 1 ? d.off[1] : 0);
-        from_regs = n_oct > 1 && (W & 15) == 0 && (img_stride & 15) == 0 && (reinterpret_cast<uintptr_t>(img) & 15) == 0 &&
-                    (d.w[1] & 3) == 0 && (reinterpret_cast<uintptr_t>(dst1) & 3) == 0;
-        if (from_regs) {
-            constexpr int NG = OB / 16, NITEM = (OB / 2) * NG, PER = NITEM / 256;
-            static_assert(NITEM % 256 == 0, "whole items per thread");
-            const int oh = d.h[1], ow = d.w[1];
-            uint4 va[PER], vb[PER];
-            int item_r[PER], item_g[PER];
-            bool ok0[PER], ok1[PER];
-#pragma unroll
-            for (int k = 0; k < PER; ++k) {
-                const int it = tid + k * 256;
-                const int rp = it / NG, g = it - rp * NG;
-                item_r[k] = rp;
-                item_g[k] = g;
-                const int ya = y0 + 2 * rp, yb = ya + 1, x = x0 + 16 * g;
-                ok0[k] = ya < H && x < W;
-                ok1[k] = yb < H && x < W;
-                const int yac = ya < H ? ya : H - 1, ybc = yb < H ? yb : H - 1, xc = x < W ? x : W - 16;
-                va[k] = *reinterpret_cast<const uint4 *>(src + (int64_t)yac * W + xc);
-                vb[k] = *reinterpret_cast<const uint4 *>(src + (int64_t)ybc * W + xc);
-            }
-            uint32_t *lds1 = reinterpret_cast<uint32_t *>(bufB);          // octave 1 of the block: [OB/2][OB/2] bytes
-#pragma unroll
-            for (int k = 0; k < PER; ++k) {
-                const uint32_t a[4] = {va[k].x, va[k].y, va[k].z, va[k].w}, b[4] = {vb[k].x, vb[k].y, vb[k].z, vb[k].w};
-                uint32_t o[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-#pragma unroll
-                    for (int bb = 0; bb < 4; ++bb) {
-                        const uint32_t pa = (a[j] >> (8 * bb)) & 255u, pb = (b[j] >> (8 * bb)) & 255u;
-                        if (ok0[k]) { nlo = (~pa) > nlo ? (~pa) : nlo; hi = pa > hi ? pa : hi; }
-                        if (ok1[k]) { nlo = (~pb) > nlo ? (~pb) : nlo; hi = pb > hi ? pb : hi; }
-                    }
-                    // two pooled pixels per dword: the byte pairs summed in 16-bit lanes ((a+b+c+d) & 255) >> 2
-                    const uint32_t sum = (a[j] & 0x00ff00ffu) + ((a[j] >> 8) & 0x00ff00ffu) + (b[j] & 0x00ff00ffu) + ((b[j] >> 8) & 0x00ff00ffu);
-                    o[j] = ((sum >> 2) & 0x3fu) | (((sum >> 18) & 0x3fu) << 8);
-                }
-                const uint32_t out0 = o[0] | (o[1] << 16), out1 = o[2] | (o[3] << 16);
-                const int rp = item_r[k], g = item_g[k];
-                lds1[(rp * (OB / 2) + 8 * g) / 4] = out0;
-                lds1[(rp * (OB / 2) + 8 * g) / 4 + 1] = out1;
-                const int oy = (y0 >> 1) + rp, ox = (x0 >> 1) + 8 * g;
-                if (oy < oh && ox < ow) {                                  // (ow % 4 == 0 and ox % 8 == 0: whole dwords in or out)
-                    uint32_t *gp = reinterpret_cast<uint32_t *>(dst1 + (int64_t)oy * ow + ox);
-                    gp[0] = out0;
-                    if (ox + 4 < ow) gp[1] = out1;
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) {
-                        const uint32_t pv = ((q < 4 ? out0 : out1) >> (8 * (q & 3))) & 255u;
-                        if (ox + q < ow) { nlo1 = (~pv) > nlo1 ? (~pv) : nlo1; hi1 = pv > hi1 ? pv : hi1; }
-                    }
-                }
-            }
-        }
-    }
-    if (from_regs) {
-    } else if (sizeof(T) == 1 && (W & 3) == 0 && (img_stride & 3) == 0 && (reinterpret_cast<uintptr_t>(img) & 3) == 0) {
-        constexpr int DW = OB / 4;                                   // dwords per block row
-        const uint32_t *src32 = reinterpret_cast<const uint32_t *>(src);
-        uint32_t *lds32 = reinterpret_cast<uint32_t *>(bufA);
-        const int wdw = W >> 2;
-        for (int i0 = tid; i0 < OB * DW; i0 += 256 * U) {
-            uint32_t v[U];
-            bool ok[U];
-#pragma unroll
-            for (int k = 0; k < U; ++k) {
-                int i = i0 + k * 256;
-                i = i < OB * DW ? i : OB * DW - 1;
-                int r = i / DW, c = i - r * DW;
-                int y = y0 + r, xd = (x0 >> 2) + c;
-                ok[k] = (y < H) && (xd < wdw);
-                y = y < H ? y : H - 1;
-                xd = xd < wdw ? xd : wdw - 1;
-                v[k] = src32[(int64_t)y * wdw + xd];
-            }
-#pragma unroll
-            for (int k = 0; k < U; ++k) {
-                int i = i0 + k * 256;
-                if (i < OB * DW) {
-                    uint32_t w = ok[k] ? v[k] : 0u;
-                    lds32[i] = w;
-                    if (ok[k]) {
-#pragma unroll
-                        for (int bb = 0; bb < 4; ++bb) {
-                            uint32_t kk = (w >> (8 * bb)) & 255u;
-                            nlo = (~kk) > nlo ? (~kk) : nlo;
-                            hi = kk > hi ? kk : hi;
-                        }
-                    }
-                }
-            }
-        }
-    } else {
-        for (int i0 = tid; i0 < OB * OB; i0 += 256 * U) {
-            T v[U];
-            bool ok[U];
-#pragma unroll
-            for (int k = 0; k < U; ++k) {
-                int i = i0 + k * 256;
-                i = i < OB * OB ? i : OB * OB - 1;
-                int r = i / OB, c = i - r * OB;
-                int y = y0 + r, x = x0 + c;
-                ok[k] = (y < H) && (x < W);
-                y = y < H ? y : H - 1;
-                x = x < W ? x : W - 1;
-                v[k] = src[(int64_t)y * W + x];
-            }
-#pragma unroll
-            for (int k = 0; k < U; ++k) {
-                int i = i0 + k * 256;
-                if (i < OB * OB) {
-                    bufA[i] = ok[k] ? v[k] : T(0);
-                    if (ok[k]) {
-                        uint32_t kk = PixKey<T>::key(v[k]);
-                        nlo = (~kk) > nlo ? (~kk) : nlo;
-                        hi = kk > hi ? kk : hi;
-                    }
-                }
-            }
-        }
-    }
-    __syncthreads();
-    // per-thread partial (max ~key, max key) of every octave this block touches; ONE workgroup reduction
-    // and one atomic per value at the very end (a reduction + two atomics per octave cost two barriers each)
-    uint32_t pmm[2 * (OB_LEVELS + 1)];
-#pragma unroll
-    for (int j = 0; j < 2 * (OB_LEVELS + 1); ++j) pmm[j] = 0u;
-    pmm[0] = nlo;
-    pmm[1] = hi;
-    pmm[2] = nlo1;                       // (octave 1 straight from registers: see above)
-    pmm[3] = hi1;
 
-    // ---- octaves 1..7: pool LDS -> LDS (+ global), ping-pong between bufA and bufB
+    // the load path of octave 0, bytes only: 16-byte rows and a 4-byte aligned octave 1 -> registers, 4-byte rows -> dwords
+    // through LDS, else (and every float32 image) element by element
+    T *dst1 = obase + (n_oct > 1 ? d.off[1] : 0);
+    auto rows_aligned = [&](int a) { return ((W | img_stride | reinterpret_cast<uintptr_t>(img)) & (a - 1)) == 0; };
+    const bool from_regs = sizeof(T) == 1 && n_oct > 1 && rows_aligned(16) && (d.w[1] & 3) == 0 && (reinterpret_cast<uintptr_t>(dst1) & 3) == 0;
+    const bool by_dwords = sizeof(T) == 1 && !from_regs && rows_aligned(4);
+
+    // per-thread partial key range of every octave this block touches; ONE workgroup reduction and one atomic per value at
+    // the very end (a reduction + two atomics per octave cost two barriers each)
+    KeyRange<uint32_t> part[OB_LEVELS + 1];
+    if constexpr (sizeof(T) == 1) {
+        if (from_regs)
+            load_block_regs(src, H, W, y0, x0, reinterpret_cast<uint32_t *>(bufB), dst1, d.h[1], d.w[1], part[0], part[1]);
+        else if (by_dwords)
+            part[0] = load_block_lds<T>(reinterpret_cast<const uint32_t *>(src), H, W >> 2, y0, x0 >> 2, reinterpret_cast<uint32_t *>(bufA));
+    }
+    if (!from_regs && !by_dwords) part[0] = load_block_lds<T>(src, H, W, y0, x0, bufA);
+    __syncthreads();
+
+    // ---- octaves 1..7: pool LDS -> LDS (+ global), ping-pong between bufA and bufB (the regs path left octave 1 in bufB)
     T *cur = from_regs ? bufB : bufA;
     T *nxt = from_regs ? bufA : bufB;
     int side = from_regs ? OB / 2 : OB;  // side of `cur`
     const int kmax = n_oct - 1 < OB_LEVELS ? n_oct - 1 : OB_LEVELS;
-    int k = from_regs ? 2 : 1;
-    for (; k <= kmax; ++k) {
-        if ((side >> 1) * (side >> 1) <= 64) break;       // the small octaves: one wave, no barriers (below)
+    for (int k = from_regs ? 2 : 1; k <= kmax; ++k) {
+        // the octaves of at most 64 pixels per block (the last four of a 128 x 128 block): wave 0 alone walks them, lane =
+        // pixel -- LDS serves a wave's accesses in order, so a level's reads see the previous level's writes without a
+        // workgroup barrier; the other waves go straight to the final reduction (at batch 1 the kernel is ONE round of
+        // workgroups whose length is this serial chain: four barriers and four sweeps of 256 threads over a handful of
+        // pixels less)
         const int ns = side >> 1;
-        const int oh = d.h[k], ow = d.w[k];
-        const int oy0 = y0 >> k, ox0 = x0 >> k;
-        T *dst = obase + d.off[k];
-        nlo = 0u;
-        hi = 0u;
-        for (int i = tid; i < ns * ns; i += 256) {
-            int r = i / ns, c = i - r * ns;
-            const T *p0 = cur + (2 * r) * side + 2 * c;
-            T v = pool4<T>(p0[0], p0[side], p0[1], p0[side + 1]);
-            nxt[r * ns + c] = v;
-            int y = oy0 + r, x = ox0 + c;
-            if (y < oh && x < ow) {
-                dst[(int64_t)y * ow + x] = v;
-                uint32_t key = PixKey<T>::key(v);
-                nlo = (~key) > nlo ? (~key) : nlo;
-                hi = key > hi ? key : hi;
-            }
+        const bool wave0_walk = ns * ns <= 64;
+        if (wave0_walk && tid >= 64) break;
+        const KeyRange<uint32_t> kr = pool_step<T>(cur, side, nxt, ns, ns, obase + d.off[k], d.h[k], d.w[k], y0 >> k, x0 >> k);
+        if (wave0_walk) {
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        } else {
+            __syncthreads();
         }
-        __syncthreads();
 #pragma unroll
-        for (int j = 1; j <= OB_LEVELS; ++j)          // (static indexing keeps pmm in registers)
-            if (j == k) {
-                pmm[2 * j] = nlo;
-                pmm[2 * j + 1] = hi;
-            }
+        for (int j = 1; j <= OB_LEVELS; ++j)          // (static indexing keeps `part` in registers)
+            if (j == k) part[j] = kr;
         T *t = cur;
         cur = nxt;
         nxt = t;
         side = ns;
     }
-    // ---- the octaves of at most 64 pixels per block (the last four of a 128 x 128 block): wave 0 alone walks them, lane =
-    //      pixel -- LDS serves a wave's accesses in order, so a level's reads see the previous level's writes without a
-    //      workgroup barrier; the other waves go straight to the final reduction (at batch 1 the kernel is ONE round of
-    //      workgroups whose length is this serial chain: four barriers and four sweeps of 256 threads over a handful of
-    //      pixels less)
-    if (tid < 64) {
-        for (; k <= kmax; ++k) {
-            const int ns = side >> 1;
-            const int oh = d.h[k], ow = d.w[k];
-            const int oy0 = y0 >> k, ox0 = x0 >> k;
-            T *dst = obase + d.off[k];
-            nlo = 0u;
-            hi = 0u;
-            if (tid < ns * ns) {
-                const int r = tid / ns, c = tid - r * ns;
-                const T *p0 = cur + (2 * r) * side + 2 * c;
-                const T v = pool4<T>(p0[0], p0[side], p0[1], p0[side + 1]);
-                nxt[r * ns + c] = v;
-                const int y = oy0 + r, x = ox0 + c;
-                if (y < oh && x < ow) {
-                    dst[(int64_t)y * ow + x] = v;
-                    const uint32_t key = PixKey<T>::key(v);
-                    nlo = ~key;
-                    hi = key;
-                }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#pragma unroll
-            for (int j = 1; j <= OB_LEVELS; ++j)
-                if (j == k) {
-                    pmm[2 * j] = nlo;
-                    pmm[2 * j + 1] = hi;
-                }
-            T *t = cur;
-            cur = nxt;
-            nxt = t;
-            side = ns;
-        }
-    }
-    // ---- min/max of all octaves: wave reduction, exchange through LDS, then lane j commits value j
-    const int nval = 2 * (kmax + 1);
-#pragma unroll
-    for (int j = 0; j < 2 * (OB_LEVELS + 1); ++j) {
-        uint32_t v = pmm[j];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            uint32_t w = __shfl_xor(v, o);
-            v = w > v ? w : v;
-        }
-        if ((tid & 63) == 0) red[tid >> 6][j] = v;
-    }
-    __syncthreads();
-    if (tid < nval) {
-        uint32_t v = red[0][tid];
-#pragma unroll
-        for (int w = 1; w < 4; ++w) v = red[w][tid] > v ? red[w][tid] : v;
-        if (v) atomicMax(mm + tid, v);                 // mm is [octave][2]: index 2*k + {0: ~min key, 1: max key}
-    }
+    commit_key_ranges(part, kmax + 1, red, minmax + (int64_t)b * n_oct * 2);
 }
 
 // octaves beyond the block's reach (bytes: images of 2048+ px on the short side): one workgroup per image walks
@@ -349,35 +301,24 @@ __global__ __launch_bounds__(256) void octaves_tail_kernel(T *oct, int64_t oct_s
                                                            uint32_t *minmax) {
     constexpr int OB_LEVELS = Blk<T>::LEVELS;
     extern __shared__ __attribute__((aligned(16))) unsigned char tail_smem[];
-    __shared__ uint32_t red[8];
+    __shared__ uint32_t red[4 * 2];
     T *cur = reinterpret_cast<T *>(tail_smem);
     const int b = blockIdx.x, tid = threadIdx.x;
     T *obase = oct + (int64_t)b * oct_stride;
     uint32_t *mm = minmax + (int64_t)b * n_oct * 2;
-    int sh = d.h[OB_LEVELS], sw = d.w[OB_LEVELS];
-    T *nxt = cur + sh * sw;
-    for (int i = tid; i < sh * sw; i += 256) cur[i] = obase[d.off[OB_LEVELS] + i];
+    int sw = d.w[OB_LEVELS];
+    const int n0 = d.h[OB_LEVELS] * sw;
+    T *nxt = cur + n0;
+    for (int i = tid; i < n0; i += 256) cur[i] = obase[d.off[OB_LEVELS] + i];
     __syncthreads();
     for (int k = OB_LEVELS + 1; k < n_oct; ++k) {
         const int oh = d.h[k], ow = d.w[k];
-        T *dst = obase + d.off[k];
-        uint32_t nlo = 0u, hi = 0u;
-        for (int i = tid; i < oh * ow; i += 256) {
-            int r = i / ow, c = i - r * ow;
-            const T *p0 = cur + (2 * r) * sw + 2 * c;
-            T v = pool4<T>(p0[0], p0[sw], p0[1], p0[sw + 1]);
-            nxt[i] = v;
-            dst[i] = v;
-            uint32_t key = PixKey<T>::key(v);
-            nlo = (~key) > nlo ? (~key) : nlo;
-            hi = key > hi ? key : hi;
-        }
-        __syncthreads();
-        block_minmax_commit(nlo, hi, red, mm + 2 * k);
+        KeyRange<uint32_t> part[1] = {pool_step<T>(cur, sw, nxt, oh, ow, obase + d.off[k], oh, ow, 0, 0)};
+        __syncthreads();                                  // (also: the last commit's reads of `red` before this one's writes)
+        commit_key_ranges(part, 1, red, mm + 2 * k);
         T *t = cur;
         cur = nxt;
         nxt = t;
-        sh = oh;
         sw = ow;
     }
 }
@@ -389,21 +330,19 @@ __global__ __launch_bounds__(256) void octaves_tail_kernel(T *oct, int64_t oct_s
 // ((a+b)+c)+d and divides exactly.  min/max are 64-bit order-preserving keys (word 0: max of ~key, word 1:
 // max of key, atomicMax on zeroed words, like the 32-bit ones).  One plain launch per octave: these are the
 // rare dtypes, correct rather than tuned.
+using KeyRange64 = KeyRange<unsigned long long>;
+
 __device__ inline unsigned long long f64_key(double v) {
     const unsigned long long b = (unsigned long long)__double_as_longlong(v);
     return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
 }
 
-__device__ inline void wave_minmax64_commit(unsigned long long nlo, unsigned long long hi, unsigned long long *mm) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long l2 = __shfl_xor(nlo, o), h2 = __shfl_xor(hi, o);
-        nlo = l2 > nlo ? l2 : nlo;
-        hi = h2 > hi ? h2 : hi;
-    }
+// one pair of atomics per wave (zeros are not sent, as in commit_key_ranges)
+__device__ inline void wave_commit64(KeyRange64 kr, unsigned long long *mm) {
+    kr.wave_reduce();
     if ((threadIdx.x & 63) == 0) {
-        if (nlo) atomicMax(mm + 0, nlo);
-        if (hi) atomicMax(mm + 1, hi);
+        if (kr.nlo) atomicMax(mm + 0, kr.nlo);
+        if (kr.hi) atomicMax(mm + 1, kr.hi);
     }
 }
 
@@ -417,65 +356,59 @@ __device__ inline double wrap_int(double s, int bits, int sgn) {
 
 __global__ __launch_bounds__(256) void minmax_f64_kernel(const double *img, int64_t img_stride, int64_t n, int n_oct,
                                                          unsigned long long *minmax, uint32_t *zero, int zero_words) {
-    if (blockIdx.x == 0 && blockIdx.y == 0)
-        for (int i = threadIdx.x; i < zero_words; i += 256) zero[i] = 0u;          // (see octaves_block_kernel)
+    zero_by_first_workgroup(zero, zero_words);
     const double *src = img + (int64_t)blockIdx.y * img_stride;
-    unsigned long long nlo = 0, hi = 0;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const unsigned long long k = f64_key(src[i]);
-        nlo = ~k > nlo ? ~k : nlo;
-        hi = k > hi ? k : hi;
-    }
-    wave_minmax64_commit(nlo, hi, minmax + (int64_t)blockIdx.y * n_oct * 2);
+    KeyRange64 kr;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) kr.add(f64_key(src[i]));
+    wave_commit64(kr, minmax + (int64_t)blockIdx.y * n_oct * 2);
 }
 
-// octave k from octave k - 1 (src: sh x sw, dst: oh x ow = floor(sh/2) x floor(sw/2))
+// octave k from octave k - 1 (src: sh x sw, dst: oh x ow = floor(sh/2) x floor(sw/2)); cast: WB_CAST_* of the image's
+// dtype, (bits, sgn): the integer type whose adds wrap, bits = 0 where none does
 __global__ __launch_bounds__(256) void pool_f64_kernel(const double *src_base, int64_t src_stride, int sw, double *dst_base,
-                                                       int64_t dst_stride, int oh, int ow, int bits, int sgn, int k, int n_oct,
-                                                       unsigned long long *minmax) {
+                                                       int64_t dst_stride, int oh, int ow, int cast, int bits, int sgn, int k,
+                                                       int n_oct, unsigned long long *minmax) {
     const double *src = src_base + (int64_t)blockIdx.y * src_stride;
     double *dst = dst_base + (int64_t)blockIdx.y * dst_stride;
-    unsigned long long nlo = 0, hi = 0;
+    KeyRange64 kr;
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i < (int64_t)oh * ow) {
         const int r = (int)(i / ow), c = (int)(i - (int64_t)r * ow);
         const double *p0 = src + (int64_t)(2 * r) * sw + 2 * c;
         const double a = p0[0], b = p0[sw], cc = p0[1], d = p0[sw + 1];      // [2r,2c], [2r+1,2c], [2r,2c+1], [2r+1,2c+1]
+        const double s = ((a + b) + cc) + d;
         double v;
-        if (bits > 0) {
-            // each add wraps in the array's dtype; wrapping once at the end is the same residue
-            // (+ 0.0: a sum of -1 .. -3 truncates to -0.0, and an integer has one zero -- the pixel and its key are +0.0's)
-            v = trunc(wrap_int(((a + b) + cc) + d, bits, sgn) / 4.0) + 0.0;
-        } else if (bits == -WB_CAST_TRUNC) {
-            v = trunc((((a + b) + cc) + d) / 4.0) + 0.0;    // int64 / uint64 values exact in float64: no rounding, no wrap
-        } else if (bits == -WB_CAST_BOOL) {
-            v = (a != 0.0 || b != 0.0 || cc != 0.0 || d != 0.0) ? 1.0 : 0.0;    // bool + bool is logical or; x / 4 != 0
-        } else if (bits == -WB_CAST_F16) {
-            v = wb_round_f16(wb_round_f16(wb_round_f16(wb_round_f16(a + b) + cc) + d) / 4.0);   // every float16 add rounds
-        } else {
-            v = (((a + b) + cc) + d) / 4.0;
+        switch (cast) {
+            case WB_CAST_TRUNC:
+                // each add wraps in the array's dtype; wrapping once at the end is the same residue (int64 / uint64 values
+                // are exact in float64: no rounding, no wrap)
+                // (+ 0.0: a sum of -1 .. -3 truncates to -0.0, and an integer has one zero -- the pixel and its key are +0.0's)
+                v = trunc((bits ? wrap_int(s, bits, sgn) : s) / 4.0) + 0.0;
+                break;
+            case WB_CAST_BOOL:
+                v = (a != 0.0 || b != 0.0 || cc != 0.0 || d != 0.0) ? 1.0 : 0.0;    // bool + bool is logical or; x / 4 != 0
+                break;
+            case WB_CAST_F16:
+                v = wb_round_f16(wb_round_f16(wb_round_f16(wb_round_f16(a + b) + cc) + d) / 4.0);   // every float16 add rounds
+                break;
+            default:
+                v = s / 4.0;
         }
         dst[i] = v;
-        const unsigned long long key = f64_key(v);
-        nlo = ~key;
-        hi = key;
+        kr.add(f64_key(v));
     }
-    wave_minmax64_commit(nlo, hi, minmax + ((int64_t)blockIdx.y * n_oct + k) * 2);
+    wave_commit64(kr, minmax + ((int64_t)blockIdx.y * n_oct + k) * 2);
 }
 
 int launch_octaves_f64(hipStream_t st, const double *img, int dtype, int batch, int H, int W, int64_t img_stride, double *oct,
                        int64_t oct_stride, const int64_t *oct_off, int n_oct, unsigned long long *minmax, uint32_t *zero, int zero_words) {
-    int bits = 0, sgn = 0;
+    int bits = 0, sgn = 0;                              // the integer types narrower than float64's 53 bits: their adds wrap
     switch (dtype) {
-        case WB_DTYPE_F64: break;
         case WB_DTYPE_I8: bits = 8; sgn = 1; break;
         case WB_DTYPE_I16: bits = 16; sgn = 1; break;
         case WB_DTYPE_U16: bits = 16; break;
         case WB_DTYPE_I32: bits = 32; sgn = 1; break;
         case WB_DTYPE_U32: bits = 32; break;
-        case WB_DTYPE_I64: case WB_DTYPE_U64: bits = -WB_CAST_TRUNC; break;     // (negative: no wrap, see pool_f64_kernel)
-        case WB_DTYPE_BOOL: bits = -WB_CAST_BOOL; break;
-        case WB_DTYPE_F16: bits = -WB_CAST_F16; break;
     }
     const int64_t n0 = (int64_t)H * W;
     int blocks = (int)((n0 + 255) / 256);
@@ -487,7 +420,7 @@ int launch_octaves_f64(hipStream_t st, const double *img, int dtype, int batch, 
         const double *src = k == 1 ? img : oct + oct_off[k - 1];
         const int64_t sstride = k == 1 ? img_stride : oct_stride;
         hipLaunchKernelGGL(pool_f64_kernel, dim3((unsigned)(((int64_t)oh * ow + 255) / 256), batch), dim3(256), 0, st, src, sstride,
-                           sw, oct + oct_off[k], oct_stride, oh, ow, bits, sgn, k, n_oct, minmax);
+                           sw, oct + oct_off[k], oct_stride, oh, ow, wb_cast_mode(dtype), bits, sgn, k, n_oct, minmax);
         sh = oh;
         sw = ow;
     }
