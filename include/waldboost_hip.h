@@ -639,6 +639,52 @@ int wb_verify_scratch_bytes(int m, int n, int C, int64_t n_windows, size_t *byte
 int wb_verify_launch(void *stream, const void *X, int x_dtype, int64_t n_windows, int m, int n, int C, const float *weights,
                      const float *scores_in, void *scratch, size_t scratch_bytes, float *out);
 
+/* Training of the verification CNN: one step of Keras's train_on_batch for model_cnn under the reference's exploss and
+ * Adam (reference verification.py:59-81).  New symbols of ABI 8 (additive: the version number did not change).  The
+ * step's contract -- batch statistics, loss, backward rules, the dropout generator, Adam, the fixed summation orders --
+ * is stated at the head of csrc/wb_verify_train.hip and in tests/verify_train_reference.py.
+ *
+ * Supported: wb_verify_launch's window shapes, and an even batch of 2 .. 1024 windows (WB_ERR_UNSUPPORTED otherwise,
+ * before any launch).
+ *
+ * The training layout (wb_verify_train_param_floats gives its length): the 28 arrays of model_cnn(...).get_weights()
+ * in Keras's order, unfolded, float32, one after the other -- per convolution block kernel [3][3][Cin][Cout], bias,
+ * gamma, beta, moving_mean, moving_variance; then the dense kernel [F][128], its bias, the dense kernel [128], its bias.
+ * params, adam_m, adam_v and grads_out all have this layout.  Of adam_m / adam_v the slots of the convolution biases and
+ * of the moving statistics are never touched.
+ *
+ *   X, H, Y    the resident sample pool: dev [n_pool][m][n][C] crops of x_dtype (WB_DTYPE_F32 / WB_DTYPE_U8, widened
+ *              exactly), dev float32 [n_pool] detector scores and targets (-1 / +1)
+ *   idx        dev int32 [batch]: the step's windows, as indices into the pool; duplicates are allowed and each counts.
+ *              The caller keeps them inside 0 .. n_pool - 1 (the kernels clamp, so nothing outside the pool is read).
+ *   params, adam_m, adam_v    dev float32, 16-byte aligned, updated in place
+ *   t          dev int32 [2]: t[0] the number of steps done (0 before the first; the dropout masks and Adam's bias
+ *              correction follow it), advanced by the update kernel; t[1] is the update kernel's workgroup counter: zero
+ *              before the first step, and left zero by every step
+ *   hyper      host: the step's constants (Keras's defaults: lr 1e-4, beta1 0.9, beta2 0.999, adam_epsilon 1e-7,
+ *              momentum 0.99, bn_epsilon 1e-3; dropout 0.2).  An element is kept iff its 32 bits of the generator are
+ *              >= round(dropout * 2^32); kept values are multiplied by float32(1 / (1 - dropout)).
+ *   scratch    dev, 16-byte aligned, wb_verify_train_scratch_bytes(m, n, C, batch) bytes; nothing in it needs clearing
+ *   loss_out   dev float32 [1]: the step's loss (before the update)
+ *   grads_out  null, or dev float32 in the training layout: the step's gradients; the convolution biases' slots receive
+ *              0 (their gradient is zero by contract), the moving_mean / moving_variance slots the step's batch mean and
+ *              unbiased batch variance
+ * Null or misaligned pointers, n_pool < 1, a short scratch and constants out of range are WB_ERR_INVALID.  A chain of
+ * launches on `stream`, no host synchronisation; the same inputs give the same bits. */
+typedef struct {
+    double lr, beta1, beta2, adam_epsilon;
+    double momentum, bn_epsilon;    /* batch normalisation: moving-average momentum, variance epsilon */
+    double dropout;                 /* rate, 0 <= dropout < 1 */
+    uint32_t seed;                  /* of the dropout generator */
+    uint32_t reserved;              /* 0 */
+} WbVerifyTrainHyper;               /* 64 bytes */
+int wb_verify_train_param_floats(int m, int n, int C, int64_t *count);
+int wb_verify_train_scratch_bytes(int m, int n, int C, int64_t batch, size_t *bytes);
+int wb_verify_train_step(void *stream, const void *X, int x_dtype, const float *H, const float *Y, int64_t n_pool,
+                         const int32_t *idx, int64_t batch, int m, int n, int C, float *params, float *adam_m, float *adam_v,
+                         int32_t *t, const WbVerifyTrainHyper *hyper, void *scratch, size_t scratch_bytes, float *loss_out,
+                         float *grads_out);
+
 /* Device self-test: the uint8 fast path of the orientation projection (fp32 arithmetic that is
  * proven equal to the reference's fp64 formula for integer gradients) is compared with the fp64
  * formula for every (gx, gy) in [-1020, 1020]^2; *mismatches (dev uint32, zeroed by the caller)

@@ -49,6 +49,14 @@ class WbModelInfo(C.Structure):
                 ("rank_ok", C.c_int32), ("specialized", C.c_int32), ("rank16_ok", C.c_int32)]
 
 
+class WbVerifyTrainHyper(C.Structure):
+    _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("adam_epsilon", C.c_double),
+                ("momentum", C.c_double), ("bn_epsilon", C.c_double), ("dropout", C.c_double), ("seed", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+assert C.sizeof(WbVerifyTrainHyper) == 64
+
 # every symbol include/waldboost_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -115,6 +123,10 @@ SYMBOLS = {
     "wb_verify_weights_floats": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
     "wb_verify_scratch_bytes": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int64, C.POINTER(C.c_size_t)]),
     "wb_verify_launch": (C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_size_t, _P]),
+    "wb_verify_train_param_floats": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
+    "wb_verify_train_scratch_bytes": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int64, C.POINTER(C.c_size_t)]),
+    "wb_verify_train_step": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int64, _P, C.c_int64, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P,
+                                       _P, _P, C.c_size_t, _P, _P]),
 }
 
 _lib = None

@@ -1,4 +1,4 @@
-"""CNN verification -- drop-in for the inference side of ``waldboost.verification``: a small CNN re-scores the
+"""CNN verification -- drop-in for ``waldboost.verification``, inference and training: a small CNN re-scores the
 windows a cascade lets through, ``p(X, H) = sigmoid(cnn(X) + H)`` (reference verification.py:1-16).
 
 What runs where:
@@ -11,10 +11,15 @@ What runs where:
 * ``detect_and_verify`` (reference verification.py:85-105, with ``get_boxes`` for its ``get_bbs`` slip) scans the image
   like ``samples.get_samples_from_image`` does and gathers the crops of every detection on the device: they never travel
   to the host;
-* ``train`` is not here: the backward pass is out of scope.  Train with the reference and import the result with
-  ``Verifier.from_keras_weights(input_shape, M.get_weights())``.
+* ``train`` (reference verification.py:63-81) and ``Trainer`` run Keras's ``train_on_batch`` for this network on the GPU:
+  the forward pass in training mode (batch statistics, dropout), exploss, the backward pass and Adam are HIP kernels
+  behind ``wb_verify_train_step`` (csrc/wb_verify_train.hip), over a sample pool that is uploaded
+  once; no autograd, no torch.nn.  Training is deterministic to the bit for a seed; it is held to a float64 statement
+  within a measured margin, not to bits.  The convolution biases never move (their gradient is zero under batch
+  statistics), a deliberate difference from Keras with no effect on the trained function.  A Keras model itself is still
+  trained with the reference and imported with ``Verifier.from_keras_weights(input_shape, M.get_weights())``.
 
-The arithmetic is fixed to the bit: every pre-activation is one float32 fused-multiply-add chain in a
+The inference arithmetic is fixed to the bit: every pre-activation is one float32 fused-multiply-add chain in a
 stated order, so a window's result depends neither on the batch it sits in nor on the run.  It differs from Keras's own
 float32 evaluation (batch normalisation applied after the convolution, accumulation order of its backend) by rounding.
 """
@@ -64,6 +69,15 @@ class Verifier:
         shape = tuple(int(x) for x in input_shape)
         if len(shape) != 3 or min(shape) < 1:
             raise ValueError(f"input_shape must be (m, n, C), got {input_shape!r}")
+        self.input_shape = shape
+        self.epsilon = float(epsilon)
+        self._scratch = {}          # device index -> feature scratch
+        self.set_weights(arrays)
+
+    def set_weights(self, arrays):
+        """Replace the 28 arrays (the constructor's checks), fold again and drop the weights cached on the devices: predict
+        uses the new ones from the next call on.  Nothing changes when the arrays are refused."""
+        shape = self.input_shape
         arrays = list(arrays)
         want = _expected_shapes(shape)
         if len(arrays) != len(want):
@@ -77,12 +91,14 @@ class Verifier:
                 raise ValueError(f"array {k} holds non-finite values")
             a.setflags(write=False)
             kept.append(a)
-        self.input_shape = shape
-        self.epsilon = float(epsilon)
+        before = getattr(self, "arrays", None)
         self.arrays = kept
-        self._packed = self._fold()
+        try:
+            self._packed = self._fold()
+        except ValueError:
+            self.arrays = before
+            raise
         self._device = {}           # device index -> packed weights
-        self._scratch = {}          # device index -> feature scratch
 
     # ---- construction, files
     @staticmethod
@@ -232,10 +248,208 @@ def exploss(y_true, y_pred):
     return np.maximum(np.minimum(np.exp(-np.asarray(y_true) * np.asarray(y_pred)), 1e3), 1e-6)
 
 
-def train(*args, **kwargs):
-    raise NotImplementedError(
-        "waldboost_amd.verification has the forward pass only: train the verifier with the reference "
-        "(waldboost.verification.train) and import the result with Verifier.from_keras_weights(input_shape, M.get_weights())")
+class Trainer:
+    """Training state of a Verifier on the GPU: the 28 arrays in the training layout (include/waldboost_hip.h), Adam's m
+    and v, and the step count t, all resident.  A step is wb_verify_train_step: Keras's train_on_batch for model_cnn under
+    exploss and Adam(lr).  `seed` feeds the dropout generator (None: drawn from the system)."""
+
+    def __init__(self, verifier, lr=1e-4, seed=None, dropout=0.2, momentum=0.99):
+        import torch
+        if not isinstance(verifier, Verifier):
+            raise TypeError(f"Trainer takes a Verifier, got {type(verifier).__name__}")
+        if not (np.isfinite(lr) and lr >= 0):
+            raise ValueError(f"lr must be finite and not negative, got {lr!r}")
+        if not 0 <= dropout < 1:
+            raise ValueError(f"dropout must lie in [0, 1), got {dropout!r}")
+        if not 0 <= momentum <= 1:
+            raise ValueError(f"momentum must lie in [0, 1], got {momentum!r}")
+        self.verifier = verifier
+        self.seed = int(np.random.SeedSequence(seed).generate_state(1)[0]) if seed is None else int(seed) & 0xFFFFFFFF
+        self.hyper = nat.WbVerifyTrainHyper(lr=float(lr), beta1=0.9, beta2=0.999, adam_epsilon=1e-7, momentum=float(momentum),
+                                            bn_epsilon=verifier.epsilon, dropout=float(dropout), seed=self.seed, reserved=0)
+        lib = nat.load()
+        m, n, Cc = verifier.input_shape
+        count = C.c_int64()
+        nat.check(lib.wb_verify_train_param_floats(m, n, Cc, C.byref(count)), "wb_verify_train_param_floats")
+        flat = np.concatenate([a.reshape(-1) for a in verifier.arrays]).astype(np.float32)
+        assert flat.size == count.value, (flat.size, count.value)
+        dev = nat.require_gpu()
+        self.device = dev
+        self.params = torch.from_numpy(flat).to(dev)
+        self.adam_m = torch.zeros_like(self.params)
+        self.adam_v = torch.zeros_like(self.params)
+        self.t = torch.zeros(2, dtype=torch.int32, device=dev)
+        self._scratch = None
+        self._scratch_batch = 0
+
+    # ---- the pool
+    def _pool(self, X, H, Y):
+        """(X, x_dtype code, H, Y, N) on the device, checked."""
+        import torch
+        on_device = isinstance(X, torch.Tensor)
+        if not on_device:
+            X = np.asarray(X)
+        if len(X.shape) != 4 or tuple(X.shape[1:]) != self.verifier.input_shape or X.shape[0] < 1:
+            raise ValueError(f"samples of shape {tuple(X.shape)}, expected (N,) + {self.verifier.input_shape} with N >= 1")
+        dt = np.dtype(str(X.dtype).replace("torch.", ""))
+        if dt not in (np.float32, np.uint8):
+            raise NotImplementedError(f"samples must be float32 or uint8, got {dt}")
+        if not on_device and dt == np.float32 and not np.isfinite(X).all():
+            raise ValueError("samples hold non-finite values")
+        N = int(X.shape[0])
+        tdt, wdt = (torch.uint8, nat.WB_DTYPE_U8) if dt == np.uint8 else (torch.float32, nat.WB_DTYPE_F32)
+        Xd = (X if on_device else torch.from_numpy(np.ascontiguousarray(X))).to(self.device, tdt).contiguous()
+        vecs = []
+        for name, v in (("scores", H), ("targets", Y)):
+            if not isinstance(v, torch.Tensor):
+                v = np.ascontiguousarray(v, np.float32)
+                if not np.isfinite(v).all():
+                    raise ValueError(f"{name} hold non-finite values")
+                v = torch.from_numpy(v)
+            if tuple(v.shape) not in ((N,), (N, 1)):
+                raise ValueError(f"{name} of shape {tuple(v.shape)}, expected ({N},) or ({N}, 1)")
+            vecs.append(v.to(self.device, torch.float32).reshape(-1).contiguous())
+        return Xd, wdt, vecs[0], vecs[1], N
+
+    def _scratch_for(self, B):
+        import torch
+        if self._scratch is None or self._scratch_batch != B:
+            m, n, Cc = self.verifier.input_shape
+            need = C.c_size_t()
+            nat.check(nat.load().wb_verify_train_scratch_bytes(m, n, Cc, B, C.byref(need)), "wb_verify_train_scratch_bytes")
+            self._scratch = torch.empty(need.value, dtype=torch.uint8, device=self.device)
+            self._scratch_batch = B
+        return self._scratch
+
+    def _steps(self, pool, idx, grads=None):
+        """idx (steps, B) int32 on the device -> the device losses (steps,).  No host wait."""
+        import torch
+        Xd, wdt, Hd, Yd, N = pool
+        steps, B = (int(x) for x in idx.shape)
+        m, n, Cc = self.verifier.input_shape
+        losses = torch.empty(steps, dtype=torch.float32, device=self.device)
+        lib = nat.load()
+        scratch = self._scratch_for(B) if steps else None
+        for s in range(steps):
+            nat.check(lib.wb_verify_train_step(nat.stream_ptr(), nat.ptr(Xd), wdt, nat.ptr(Hd), nat.ptr(Yd), N, nat.ptr(idx[s]), B,
+                                               m, n, Cc, nat.ptr(self.params), nat.ptr(self.adam_m), nat.ptr(self.adam_v),
+                                               nat.ptr(self.t), C.byref(self.hyper), nat.ptr(scratch), scratch.numel(),
+                                               nat.ptr(losses[s:]), nat.ptr(grads)), "wb_verify_train_step")
+        return losses
+
+    def upload(self, X, H, Y):
+        """A resident pool for run: samples (N, m, n, C) float32 or uint8, scores and targets (N,), ndarray or device tensor."""
+        return self._pool(X, H, Y)
+
+    def _indices(self, idx, N):
+        import torch
+        if isinstance(idx, torch.Tensor):
+            host = idx.detach().cpu().numpy()
+        else:
+            host = np.asarray(idx)
+        if host.ndim != 2 or host.dtype.kind not in "iu":
+            raise ValueError("idx must be an integer array of shape (steps, B)")
+        if host.size and (host.min() < 0 or host.max() >= N):
+            raise ValueError(f"idx must lie in 0 .. {N - 1}")
+        B = host.shape[1]
+        if B < 2 or B > 1024 or B % 2:
+            raise NotImplementedError(f"a batch of {B} windows: supported are even sizes 2 .. 1024")
+        return torch.from_numpy(np.ascontiguousarray(host, np.int32)).to(self.device)
+
+    # ---- steps
+    def run(self, X, H, Y, idx, pool=None):
+        """idx.shape[0] steps over the resident pool (X, H, Y) -- or a pool from upload(): step s trains on the windows
+        idx[s] (B indices into the pool, duplicates count).  Returns the steps' losses as a device tensor; no wait."""
+        pool = pool if pool is not None else self._pool(X, H, Y)
+        return self._steps(pool, self._indices(idx, pool[4]))
+
+    def train_on_batch(self, X, H, Y):
+        """One step on the batch (X, H, Y) as it stands; returns its loss (a host wait)."""
+        pool = self._pool(X, H, Y)
+        idx = np.arange(pool[4], dtype=np.int32)[None]
+        return float(self._steps(pool, self._indices(idx, pool[4])).cpu().numpy()[0])
+
+    @property
+    def steps_done(self):
+        return int(self.t.cpu().numpy()[0])
+
+    def get_weights(self):
+        """The 28 arrays as they stand on the device."""
+        flat = self.params.cpu().numpy()
+        out, at = [], 0
+        for a in self.verifier.arrays:
+            out.append(flat[at:at + a.size].reshape(a.shape).copy())
+            at += a.size
+        return out
+
+    def commit(self):
+        """Write the parameters back into the verifier (set_weights: re-fold, caches dropped)."""
+        self.verifier.set_weights(self.get_weights())
+        return self.verifier
+
+
+def _draw_epoch(rng, N0, N1, steps, b):
+    """An epoch's pool indices (steps, 2 b): b negatives (0 .. N0 - 1), then b positives (N0 .. N0 + N1 - 1), with replacement."""
+    return np.concatenate([rng.integers(0, N0, (steps, b)), N0 + rng.integers(0, N1, (steps, b))], axis=1)
+
+
+_TRAIN_REFUSAL = ("waldboost_amd.verification trains its own Verifier only: train a Keras model with the reference "
+                  "(waldboost.verification.train) and import the result with Verifier.from_keras_weights(input_shape, M.get_weights())")
+
+
+def train(M, X0, H0, X1, H1, epochs=10, batch_size=64, steps=1000, *, lr=1e-4, seed=None, trainer=None,
+          verbose=True):
+    """The reference's train (verification.py:63-81) on the GPU: `epochs` times `steps` steps of Adam(lr) under exploss on
+    batches of batch_size // 2 negatives (X0, H0; target -1) and as many positives (X1, H1; target +1), drawn with
+    replacement.  M, a Verifier, is updated in place; the epochs' mean losses are returned (and printed when `verbose`,
+    as the reference does).  X0 / X1: (N, m, n, C) float32 or uint8, ndarray or device tensor.  The pool is uploaded once;
+    per epoch the indices are drawn on the host (numpy's generator from `seed`), uploaded once, and one wait fetches the
+    mean.  `trainer`: a Trainer of M to continue with (Adam state, step count, dropout seed).  Anything but a Verifier is
+    refused: a Keras model is trained with the reference and imported with from_keras_weights."""
+    import torch
+    if not isinstance(M, Verifier):
+        raise NotImplementedError(_TRAIN_REFUSAL)
+    epochs, steps, b = int(epochs), int(steps), int(batch_size) // 2
+    if epochs < 0 or steps < 1:
+        raise ValueError("epochs must not be negative and steps must be positive")
+    if b < 1 or 2 * b > 1024:
+        raise NotImplementedError(f"batch_size {batch_size}: supported are 2 .. 1025")
+    if trainer is None:
+        trainer = Trainer(M, lr=lr, seed=seed)
+    elif trainer.verifier is not M:
+        raise ValueError("the trainer belongs to another verifier")
+    N0, N1 = int(X0.shape[0]), int(X1.shape[0])
+    if N0 < 1 or N1 < 1:
+        raise ValueError("both classes need samples")
+    both = [X0, X1]
+    if any(isinstance(x, torch.Tensor) for x in both):
+        both = [x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x)) for x in both]
+        if both[0].dtype != both[1].dtype:
+            raise ValueError("X0 and X1 must have one dtype")
+        X = torch.cat([x.to(trainer.device) for x in both])
+    else:
+        both = [np.asarray(x) for x in both]
+        if both[0].dtype != both[1].dtype:
+            raise ValueError("X0 and X1 must have one dtype")
+        X = np.concatenate(both)
+    host = lambda v: v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+    H = np.concatenate([host(H0).reshape(-1), host(H1).reshape(-1)]).astype(np.float32)
+    Y = np.concatenate([-np.ones(N0, np.float32), np.ones(N1, np.float32)])
+    pool = trainer.upload(X, H, Y)
+    rng = np.random.default_rng(seed)
+    means = []
+    for e in range(1, epochs + 1):
+        if verbose:
+            print(f"Epoch {e}/{epochs}")
+        idx = _draw_epoch(rng, N0, N1, steps, b)
+        losses = trainer.run(None, None, None, idx, pool=pool)
+        means.append(float(losses.cpu().numpy().astype(np.float64).mean()))           # the epoch's one wait
+        if verbose:
+            print(means[-1])
+    trainer.commit()
+    if verbose:
+        print("Done")
+    return means
 
 
 def detect_and_verify(image, model, verifier):
