@@ -48,6 +48,9 @@
  *        gini criterion, best splitter, on float32 samples): the sort of every feature column and the split search,
  *        routing and re-partitioning of one tree level
  *        -> wb_cart_sort_launch, wb_cart_level_launch
+ *   reference waldboost/samples.py:46-216 (label_boxes, select_candidates, get_samples_from_image: hard-negative mining),
+ *        for a scanned batch and with a stated selection rule in place of np.random.choice
+ *        -> wb_mine_select_launch, wb_mine_gather_launch
  */
 #ifndef WALDBOOST_HIP_H
 #define WALDBOOST_HIP_H
@@ -525,6 +528,49 @@ int wb_nms_finish_launch(void *stream, const void *fin, uint32_t out_capacity, i
 int wb_match_launch(void *stream, const double *dt /* [n_dt][4] */, const int32_t *dt_image /* [n_dt] */,
                     const double *gt /* [n_gt][4] */, const int32_t *gt_off /* [n_images + 1] */,
                     int64_t n_dt, int64_t n_gt, int n_images, double *best /* [n_dt] */, int32_t *owner /* [n_dt] */);
+
+/* Hard-negative mining of a scanned batch: label, choose and crop on the device (reference samples.py:46-216 label_boxes,
+ * select_candidates, gather_samples; DESIGN.md 4.12 has the rule, tests/mine_reference.py states it in NumPy).
+ * New symbols of ABI 8 (the version number did not change: nothing that existed did).
+ * wb_mine_select_launch:
+ *   det        dev WbDet [n_det], 16-byte aligned, ANY order (e.g. wb_det_pack_launch's records); image and level are clamped
+ *              into [0, n_images) and [0, n_levels); (image, level, r, c) must be unique (a scan's records are)
+ *   inv_scale  dev float [n_levels] as for wb_boxes_launch: the box of a record is float32 [c, r, c+n, r+m] * inv_scale[level]
+ *   gt, gt_off as for wb_match_launch (both ends of a range clamped to [0, n_gt]);  gt_ignore dev uint8 [n_gt];
+ *   serial     dev uint32 [n_images]: the caller's number of each image (what its keys depend on instead of its batch slot)
+ *   * best / owner of a record: wb_match_launch's, on the float32 box;
+ *   * FP hit: best < max_fp_iou, or an image without candidates;  TP hit: candidates, best > min_tp_iou (both strict, float64)
+ *     and gt_ignore[owner] == 0;  want_tp / want_fp == 0: that class has no hits;
+ *   * key = fmix32(((r << 16) | c) ^ g), g = fmix32(fmix32(seed ^ fmix32(serial[image] + 0x9E3779B9)) ^ (level * 0x9E3779B1)),
+ *     fmix32(x): x ^= x >> 16, x *= 0x85EBCA6B, x ^= x >> 13, x *= 0xC2B2AE35, x ^= x >> 16 (uint32);
+ *   * per (image, level) and class, of H hits the min(H, max_tp) / min(H, max_fp) with the smallest keys are chosen;
+ *     label 1 (TP) or -1 (FP); a record chosen for both is FP.
+ *   rows       dev, 16-byte aligned: the chosen records as 32-byte rows {WbDet det; double best; int32 owner; int32 label},
+ *              in NO particular order (the caller orders them by (image, level, r, c)); n_rows dev uint32 [1]: their number.
+ *              out_capacity rows of room: at least min(n_det, n_images * n_levels * (max_tp + max_fp)) (caps of classes
+ *              that are not wanted count as 0), which the rule cannot exceed -- less is WB_ERR_INVALID
+ *   scratch    dev, 16-byte aligned, wb_mine_scratch_bytes(n_det, n_images, n_levels) bytes (6 per record, 2 KiB + 32 per
+ *              group); its content on entry does not matter
+ * n_det == 0 launches nothing (WB_OK, n_rows untouched).  Null or misaligned pointers, a short scratch, negative sizes or caps,
+ * records of no image or level: WB_ERR_INVALID.  More than 2^26 records, 1024 images, 256 levels or 16384 (image, level)
+ * groups: WB_ERR_UNSUPPORTED.  One memset and nine launches (an 8-bit digit select: no sort, no host synchronisation).
+ * wb_mine_gather_launch: out[i][m][n][C] = the window of rows[i] in the pyramid buffer `buf` (dtype WB_DTYPE_F32 / WB_DTYPE_U8):
+ *   level l of image b is HWC [u][v][C] at buf + b * img_stride + levels[l].chn_off (elements).  A row whose image or level is
+ *   out of range, whose window leaves its level (r + m > u or c + n > v) or whose level leaves the image's stride is written
+ *   as zeros and sets err[0] = 1 (err dev uint32 [1], 0 otherwise): nothing outside n_images * img_stride elements is read.
+ *   One memset and one launch, no host synchronisation. */
+typedef struct WbMineLevel {
+    int64_t chn_off;
+    int32_t u, v;
+} WbMineLevel; /* 16 bytes */
+int wb_mine_scratch_bytes(int64_t n_det, int n_images, int n_levels, size_t *bytes);
+int wb_mine_select_launch(void *stream, const WbDet *det, int64_t n_det, const float *inv_scale, int n_levels, int m, int n,
+                          const double *gt, const int32_t *gt_off, const uint8_t *gt_ignore, int64_t n_gt, const uint32_t *serial,
+                          int n_images, double min_tp_iou, double max_fp_iou, int64_t max_tp, int64_t max_fp, int want_tp,
+                          int want_fp, uint32_t seed, void *scratch, size_t scratch_bytes, void *rows, int64_t out_capacity,
+                          uint32_t *n_rows);
+int wb_mine_gather_launch(void *stream, const void *buf, int dtype, int64_t img_stride, int n_images, const WbMineLevel *levels,
+                          int n_levels, int C, const void *rows, int64_t n_rows, int m, int n, void *out, uint32_t *err);
 
 /* Split search of the FPGA flavour's tree learner (reference fpga/training.py:15-57), one tree level per call.
  * New symbols of ABI 8 (the version number did not change: nothing that existed did).

@@ -36,6 +36,10 @@ assert PATCH_DTYPE.itemsize == 16
 FIT_SPLIT_DTYPE = np.dtype([("feature", "<i4"), ("threshold", "<i4"), ("metric", "<f8"), ("t0", "<f8"), ("t1", "<f8")], align=True)   # WbFitSplit
 assert FIT_SPLIT_DTYPE.itemsize == 32
 WB_FIT_MAX_OPEN = 8
+MINE_ROW_DTYPE = np.dtype([("image", "<i4"), ("level", "<i4"), ("r", "<u2"), ("c", "<u2"), ("score", "<f4"), ("best", "<f8"),
+                           ("owner", "<i4"), ("label", "<i4")], align=True)   # wb_mine_select_launch's rows
+MINE_LEVEL_DTYPE = np.dtype([("chn_off", "<i8"), ("u", "<i4"), ("v", "<i4")], align=True)   # WbMineLevel
+assert MINE_ROW_DTYPE.itemsize == 32 and MINE_LEVEL_DTYPE.itemsize == 16
 CART_SPLIT_DTYPE = np.dtype([("feature", "<i4"), ("n_left", "<i4"), ("lo", "<f4"), ("hi", "<f4"), ("proxy", "<f8"), ("t0", "<f8"),
                              ("t1", "<f8")], align=True)   # WbCartSplit
 assert CART_SPLIT_DTYPE.itemsize == 40
@@ -112,6 +116,10 @@ SYMBOLS = {
     "wb_nms_finish_scratch_bytes": (C.c_int, [C.c_uint32, C.c_int, C.POINTER(C.c_size_t)]),
     "wb_nms_finish_launch": (C.c_int, [_P, _P, C.c_uint32, C.c_int, C.c_double, C.c_int, C.c_float, _P, C.c_size_t, _P]),
     "wb_match_launch": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int, _P, _P]),
+    "wb_mine_scratch_bytes": (C.c_int, [C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "wb_mine_select_launch": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_int64, _P, C.c_int, C.c_double,
+                                        C.c_double, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_uint32, _P, C.c_size_t, _P, C.c_int64, _P]),
+    "wb_mine_gather_launch": (C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int, _P, C.c_int, C.c_int, _P, C.c_int64, C.c_int, C.c_int, _P, _P]),
     "wb_fit_scratch_bytes": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
     "wb_fit_level_launch": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, _P, C.c_int, C.c_int, _P, C.c_int, _P, C.c_int, _P,
                                       C.c_size_t, _P]),

@@ -20,36 +20,12 @@
 // Whatever dt_image and gt_off hold, nothing outside the buffers is read: the image is clamped to [0, n_images), both ends
 // of a range to [0, n_gt], and an end in front of its start gives an empty range.  Every loop is bounded by n_gt.
 #include "wb_common.h"
+#include "wb_match_iou.h"   // match_range, match_iou: shared with the miner (wb_mine.hip)
 
 #define WB_MATCH_MAX (1 << 26)      // most detections of one call (what one detect call can return)
 #define WB_MATCH_CHUNK 64           // candidates staged in LDS at a time: 4 * 64 doubles = one per thread
 
 namespace {
-
-struct MatchRange {
-    int64_t lo, hi;
-};
-
-__device__ inline MatchRange match_range(const int32_t *gt_off, int32_t b, int64_t n_gt) {
-    int64_t lo = gt_off[b], hi = gt_off[b + 1];
-    lo = lo < 0 ? 0 : (lo > n_gt ? n_gt : lo);
-    hi = hi < 0 ? 0 : (hi > n_gt ? n_gt : hi);
-    if (hi < lo) hi = lo;
-    return {lo, hi};
-}
-
-// boxes.iou, operation by operation
-__device__ inline double match_iou(double ax1, double ay1, double ax2, double ay2, double area_a, double bx1, double by1,
-                                   double bx2, double by2) {
-    double iw = (ax2 < bx2 ? ax2 : bx2) - (ax1 > bx1 ? ax1 : bx1);
-    double ih = (ay2 < by2 ? ay2 : by2) - (ay1 > by1 ? ay1 : by1);
-    iw = iw < 0.0 ? 0.0 : iw;
-    ih = ih < 0.0 ? 0.0 : ih;
-    const double inter = iw * ih;
-    const double area_b = (bx2 - bx1) * (by2 - by1);
-    const double uni = area_a + area_b - inter;
-    return uni > 0.0 ? inter / uni : 0.0;
-}
 
 __global__ __launch_bounds__(256) void match_kernel(const double *dt, const int32_t *dt_image, const double *gt,
                                                     const int32_t *gt_off, int64_t n_dt, int64_t n_gt, int n_images,

@@ -11,7 +11,10 @@ What runs where:
   host steps with the reference's semantics (TP: best IoU above ``min_tp_iou`` on a non-ignored box; FP:
   best IoU below ``max_fp_iou``; at most ``max_*_candidates`` of each per call, drawn with
   ``np.random.choice``), ``bbx.iou`` replaced by ``boxes.iou``;
-* ``SamplePool`` (reference samples.py:219-338) re-scores its samples with ``Model.predict`` on the GPU.
+* ``SamplePool`` (reference samples.py:219-338) re-scores its samples with ``Model.predict`` on the GPU;
+* ``mine_batch`` / ``DeviceSamplePool`` are the batched, device-resident form of the same step: several images per
+  scan, labelling, choice and crops in two native calls (``wb_mine_select_launch``, ``wb_mine_gather_launch``), the
+  pool's samples in GPU memory.  They state their own selection rule (``mine_batch`` has it).
 """
 import logging
 
@@ -215,3 +218,315 @@ class SamplePool(object):
 
     def get_false_positives(self):
         return self.get_samples(SampleLabel.FALSE_POSITIVE)
+
+
+# --------------------------------------------------------------------------------------- mining on the device
+class MinedSamples:
+    """Chosen windows of a mined batch (mine_batch) or of a DeviceSamplePool, as device tensors of N rows in
+    (image, level, row, col) order: samples (N, m, n, C) in the channels' dtype, scores float32, tp_label int32
+    (SampleLabel), instance_id int32 (index of the best ground-truth box inside its image's list, -1 without ground
+    truth), image / level / row / col int32, boxes float32 (N, 4), best float64 (the best IoU)."""
+    FIELDS = ("samples", "scores", "tp_label", "instance_id", "image", "level", "row", "col", "boxes", "best")
+
+    def __init__(self, **fields):
+        assert set(fields) == set(self.FIELDS)
+        for k, v in fields.items():
+            setattr(self, k, v)
+
+    def __len__(self):
+        return int(self.scores.shape[0])
+
+    def take(self, idx):
+        """The rows `idx` (a device index tensor), copied."""
+        return MinedSamples(**{k: getattr(self, k)[idx] for k in self.FIELDS})
+
+    @staticmethod
+    def cat(parts):
+        import torch
+        return MinedSamples(**{k: torch.cat([getattr(p, k) for p in parts]) for k in MinedSamples.FIELDS})
+
+    def to_boxes(self, where=True):
+        """A host Boxes with the fields get_samples_from_image yields ('scores', 'row', 'col', 'instance_id', 'tp_label',
+        'samples') and, with `where`, 'image' and 'level'."""
+        host = lambda k: getattr(self, k).cpu().numpy()
+        out = Boxes(host("boxes"), scores=host("scores"), row=host("row").astype(np.int64), col=host("col").astype(np.int64),
+                    instance_id=host("instance_id"), tp_label=host("tp_label"), samples=host("samples"))
+        if where:
+            out.set_field("image", host("image"))
+            out.set_field("level", host("level"))
+        return out
+
+
+def _ground_truth_arrays(gts):
+    """(gt float64 [n_gt, 4], gt_off int32 [B + 1], ignore uint8 [n_gt]) of a list of Boxes / None, validated."""
+    from .boxes import _match_coords
+    coords, flags = [], []
+    for g in gts:
+        if g is None or len(g) == 0:
+            coords.append(np.zeros((0, 4), np.float64))
+            flags.append(np.zeros(0, np.uint8))
+            continue
+        f = np.asarray(g.get_field("ignore")) if g.has_field("ignore") else np.zeros(len(g))
+        if f.ndim != 1:
+            raise ValueError("'ignore' field must be single dimension")
+        coords.append(_match_coords(g, "ground-truth"))
+        flags.append((f != 0).astype(np.uint8))
+    off = np.zeros(len(gts) + 1, np.int64)
+    np.cumsum([c.shape[0] for c in coords], out=off[1:])
+    if off[-1] >= 1 << 31:
+        raise ValueError("mine_batch: at most 2**31 - 1 ground-truth boxes")
+    return np.concatenate(coords).reshape(-1, 4), off.astype(np.int32), np.concatenate(flags)
+
+
+def _empty_mined(shape, chn_dtype, dev):
+    import torch
+    z = lambda dt, *s: torch.empty((0,) + s, dtype=dt, device=dev)
+    i32 = torch.int32
+    return MinedSamples(samples=z(chn_dtype, *(int(x) for x in shape)), scores=z(torch.float32), tp_label=z(i32), instance_id=z(i32),
+                        image=z(i32), level=z(i32), row=z(i32), col=z(i32), boxes=z(torch.float32, 4), best=z(torch.float64))
+
+
+def order_rows(rows):
+    """wb_mine_select_launch's rows (device int32 [N, 8]) in (image, level, r, c) order."""
+    from . import engine as _engine
+    return _engine.sort_records(rows)
+
+
+def mine_batch(model, images, gt_boxes_per_image, tp=True, fp=True, min_tp_iou=0.7, max_fp_iou=0.3, max_tp_candidates=100,
+               max_fp_candidates=100, seed=0, serial0=0):
+    """get_samples_from_image for a batch, on the device: `images` [B, H, W] (or one [H, W]; what the engine accepts) go
+    through one scan, every surviving window is labelled against its image's ground truth (a list of B Boxes / None;
+    for one image the Boxes itself), at most max_*_candidates per (image, pyramid level) and class are chosen, and the
+    chosen windows are cropped out of the pyramid -- two native calls (wb_mine_select_launch, wb_mine_gather_launch)
+    on the records and the pyramid where they lie.  Returns a MinedSamples; updates model.n_loc / n_weak as a scan does.
+
+    The rule.  Labelling is label_boxes': the box of record (image, level, r, c) is float32 [c, r, c+n, r+m] *
+    float32(1 / scale[level]); IoU is boxes.iou's float64 arithmetic; `best` is the largest IoU over the image's ground
+    truth, the owner its first argmax; no ground truth: best 0, owner -1, every window an FP hit.  FP hit: best <
+    max_fp_iou; TP hit: best > min_tp_iou and the owner's 'ignore' flag is 0.  Choice is per (image, level) and class: of H
+    hits the min(H, max_*_candidates) with the smallest keys, key = fmix32(((r << 16) | c) ^ g), g = fmix32(fmix32(seed ^
+    fmix32(serial + 0x9E3779B9)) ^ (level * 0x9E3779B1)), serial = serial0 + the image's index in the batch (uint32
+    arithmetic; fmix32 is MurmurHash3's 32-bit finaliser, a bijection: keys never tie inside a group).  Labels are written
+    TP first, then FP: a window chosen for both is FP.  With tp=False / fp=False that class is neither chosen nor
+    returned.  The result is in (image, level, r, c) order.
+
+    Deviation from the reference: select_candidates thins with np.random.choice WITH replacement from NumPy's global
+    state (so it can pick fewer than the cap through duplicates, and no two runs agree); this choice is without
+    replacement and depends on (seed, serial, level, r, c) alone -- not on the batch an image sits in, the order of the
+    scan's records or the run.
+
+    Host traffic: one upload (ground truth, offsets, flags, serials, level table), four waits (the scan's counters
+    twice as in every scan, the number of chosen rows with the scan statistics, the gather's error word); neither
+    records, pyramid nor crops leave the device.  Images too small for any level, or no detections: an empty result
+    without a mining launch."""
+    import ctypes as C
+    import torch
+    from . import channels as _channels
+    from . import engine as _engine
+    single = getattr(images, "ndim", None) == 2
+    if single:
+        images = images[None]
+        gts = list(gt_boxes_per_image) if isinstance(gt_boxes_per_image, (list, tuple)) else [gt_boxes_per_image]
+    elif getattr(images, "ndim", None) == 3:
+        gts = list(gt_boxes_per_image)
+    else:
+        raise ValueError("images must have 3 dimensions [B,H,W] (or 2: one image)")
+    B, H, W = (int(x) for x in images.shape)
+    if len(gts) != B:
+        raise ValueError(f"mine_batch: {B} images, ground truth of {len(gts)}")
+    if max_tp_candidates < 0 or max_fp_candidates < 0:
+        raise ValueError("max_tp_candidates and max_fp_candidates must not be negative")
+    gt, gt_off, ignore = _ground_truth_arrays(gts)
+    shrink, n_per_oct, smooth, spec = _channels.read_opts(model.channel_opts)
+    m, n, Cc = (int(x) for x in model.shape)
+    assert Cc == spec.n_channels, f"Invalid number of channels. Expected {Cc} given {spec.n_channels}."
+    dev = nat.require_gpu()
+    eng = _engine.get_engine(H, W, _engine.array_dtype(images), shrink, n_per_oct, smooth, B, channels=spec)
+    chn_dtype = eng.chn.dtype
+    L = eng.plan.n_levels
+    if L == 0:
+        return _empty_mined(model.shape, chn_dtype, dev)
+    lib = eng.lib
+    eng.load_images(images)
+    eng.run_channels()
+    dm = model.device_cascade()
+    stt = eng.run_cascade(dm)                              # float / uint8 channels, not rank bytes
+    total = eng.ensure_capacity(dm)                        # (grows the buffer and scans again when a shard overflowed)
+    T = len(model)
+    model.n_loc += B * eng.plan.n_loc(m, n)
+    if total == 0:
+        model.n_weak += int(_engine.alive_host(stt.alive, T).sum())
+        return _empty_mined(model.shape, chn_dtype, dev)
+    recs = eng.pack()[1:1 + total]                         # the valid records, shard order
+    # one upload: ground truth | level table | offsets | serials | 1 / scale | ignore flags (the doubles first: all aligned)
+    table = np.zeros(L, nat.MINE_LEVEL_DTYPE)
+    for k in ("chn_off", "u", "v"):
+        table[k] = eng.level_np[k]
+    serial = ((int(serial0) + np.arange(B, dtype=np.int64)) & 0xFFFFFFFF).astype(np.uint32)
+    parts = [gt.reshape(-1).view(np.uint8), table.view(np.uint8), gt_off.view(np.uint8), serial.view(np.uint8),
+             eng.inv_scales().view(np.uint8), ignore]
+    offs = np.concatenate([[0], np.cumsum([p.size for p in parts])])
+    blob = torch.from_numpy(np.concatenate(parts)).to(dev)
+    at = lambda k: C.c_void_p(blob.data_ptr() + int(offs[k]))
+    k_tp = min(int(max_tp_candidates), total) if tp else 0
+    k_fp = min(int(max_fp_candidates), total) if fp else 0
+    room = min(total, B * L * (k_tp + k_fp))
+    need = C.c_size_t()
+    nat.check(lib.wb_mine_scratch_bytes(total, B, L, C.byref(need)), "wb_mine_scratch_bytes")
+    scratch = torch.empty(need.value, dtype=torch.uint8, device=dev)
+    rows = torch.empty((max(room, 1), 8), dtype=torch.int32, device=dev)
+    n_rows = torch.zeros(1, dtype=torch.int32, device=dev)
+    nat.check(lib.wb_mine_select_launch(nat.stream_ptr(), nat.ptr(recs), total, at(4), L, m, n, at(0), at(2), at(5), gt.shape[0], at(3),
+                                        B, float(min_tp_iou), float(max_fp_iou), int(max_tp_candidates), int(max_fp_candidates),
+                                        int(bool(tp)), int(bool(fp)), int(seed) & 0xFFFFFFFF, nat.ptr(scratch), scratch.numel(),
+                                        nat.ptr(rows), room, nat.ptr(n_rows)), "wb_mine_select_launch")
+    h = torch.cat([n_rows, stt.alive.reshape(-1)]).cpu().numpy()      # one wait: the chosen rows' number and the statistics
+    N = int(h[0])
+    model.n_weak += int(h[1:].reshape(stt.alive.shape)[:, :, :T].astype(np.int64).sum())
+    if N == 0:
+        return _empty_mined(model.shape, chn_dtype, dev)
+    assert N <= room
+    rows = order_rows(rows[:N])
+    crops = torch.empty((N, m, n, Cc), dtype=chn_dtype, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    nat.check(lib.wb_mine_gather_launch(nat.stream_ptr(), nat.ptr(eng.chn), eng.spec.wb_dtype, eng.chn_stride, B, at(1), L, Cc,
+                                        nat.ptr(rows), N, m, n, nat.ptr(crops), nat.ptr(err)), "wb_mine_gather_launch")
+    det = rows[:, :4].contiguous()
+    boxes = torch.empty((N, 4), dtype=torch.float32, device=dev)
+    scores = torch.empty(N, dtype=torch.float32, device=dev)
+    nat.check(lib.wb_boxes_launch(nat.stream_ptr(), nat.ptr(det), N, at(4), m, n, nat.ptr(boxes), nat.ptr(scores)), "wb_boxes_launch")
+    if int(err.item()):
+        raise RuntimeError("mine_batch: a chosen window lies outside its pyramid level (the records do not belong to this pyramid)")
+    rc = rows[:, 2]
+    return MinedSamples(samples=crops, scores=scores, tp_label=rows[:, 7].clone(), instance_id=rows[:, 6].clone(),
+                        image=rows[:, 0].clone(), level=rows[:, 1].clone(), row=rc & 0xFFFF, col=(rc >> 16) & 0xFFFF, boxes=boxes,
+                        best=rows[:, 4:6].contiguous().view(torch.float64).reshape(-1))
+
+
+class DeviceSamplePool(object):
+    """SamplePool with its samples resident on the GPU: `update` mines `batch` images of equal shape and dtype per scan
+    (mine_batch: its selection rule, not np.random.choice -- see there), the crops never travel to the host, and the
+    re-scoring, the fits and the predictions of a training stage read them where they lie.  Methods and meaning are
+    SamplePool's; get_samples returns X as a device tensor (a copy) and H as a float32 ndarray -- what Learner.fit_stage
+    takes.  seed: of the selection keys; an image's serial is the number of images this pool consumed before it.
+    The pool's order is SamplePool's: old samples first, then the new ones in mining order, (image, level, row, col)."""
+
+    def __init__(self, min_tp=1000, min_fp=1000, logger=None, batch=8, seed=0, **kwargs):
+        self.samples = None                    # MinedSamples ('image' holds the images' serials)
+        self.min_tp, self.min_fp = min_tp, min_fp
+        self.batch = max(int(batch), 1)
+        self.seed = int(seed)
+        self.images_seen = 0
+        self.label_boxes_args = kwargs
+        self.logger = logger or logging.getLogger("DeviceSamplePool")
+
+    def _counts(self, labels):
+        """{TP: n, FP: n} of an int32 label tensor: one read-back."""
+        import torch
+        both = torch.stack([(labels == SampleLabel.TRUE_POSITIVE).sum(), (labels == SampleLabel.FALSE_POSITIVE).sum()]).cpu()
+        return {SampleLabel.TRUE_POSITIVE: int(both[0]), SampleLabel.FALSE_POSITIVE: int(both[1])}
+
+    def pool_stats(self):
+        if self.samples is None:
+            return dict(num_tp=0, num_fp=0)
+        got = self._counts(self.samples.tp_label)
+        return dict(num_tp=got[SampleLabel.TRUE_POSITIVE], num_fp=got[SampleLabel.FALSE_POSITIVE])
+
+    def update_scores(self, model):
+        """Re-evaluate the model on every pooled sample, where it lies ('scores' becomes -inf where it rejects)."""
+        import torch
+        if self.samples is None or len(self.samples) == 0:
+            return
+        X = self.samples.samples
+        assert tuple(X.shape[1:]) == tuple(model.shape), f"Invalid shape of X. Expected {model.shape}, given {tuple(X.shape[1:])}"
+        N = int(X.shape[0])
+        H = torch.empty(N, dtype=torch.float32, device=X.device)
+        mask = torch.empty(N, dtype=torch.uint8, device=X.device)
+        wdt = nat.WB_DTYPE_U8 if X.dtype == torch.uint8 else nat.WB_DTYPE_F32
+        nat.check(nat.load().wb_samples_predict_launch(nat.stream_ptr(), model.device_cascade().handle, nat.ptr(X), wdt, N, nat.ptr(H),
+                                                       nat.ptr(mask)), "wb_samples_predict_launch")
+        self.samples.scores = H
+
+    def remove_low_scoring(self, min_score=-np.inf):
+        import torch
+        if self.samples is None:
+            return
+        alive = self.samples.scores > min_score
+        if self.logger.isEnabledFor(15):
+            self.logger.log(15, f"Removed {int((~alive).sum())}/{alive.numel()} samples (min_score={min_score:.2f})")
+        self.samples = self.samples.take(torch.nonzero(alive).reshape(-1))
+
+    def _mine(self, model, items, missing):
+        """Mine one batch of items; the new samples (or None)."""
+        import torch
+        first = items[0]["image"]
+        stack = np.stack if isinstance(first, np.ndarray) else torch.stack
+        got = mine_batch(model, stack([it["image"] for it in items]), [it["groundtruth_boxes"] for it in items],
+                         tp=missing[SampleLabel.TRUE_POSITIVE] > 0, fp=missing[SampleLabel.FALSE_POSITIVE] > 0, seed=self.seed,
+                         serial0=self.images_seen, **self.label_boxes_args)
+        if len(got):
+            got.image = got.image + (self.images_seen & 0x7FFFFFFF)
+        self.images_seen += len(items)
+        return got if len(got) else None
+
+    def update(self, model, iterable):
+        """Drop what the current model rejects, then mine images from `iterable` (dicts with 'image' and
+        'groundtruth_boxes'), `batch` of equal shape and dtype at a time, until the pool holds min_tp / min_fp samples
+        again: it stops after the first batch that fills both quotas."""
+        self.update_scores(model)
+        self.remove_low_scoring()
+        have = self._counts(self.samples.tp_label) if self.samples is not None else {SampleLabel.TRUE_POSITIVE: 0, SampleLabel.FALSE_POSITIVE: 0}
+        missing = {SampleLabel.TRUE_POSITIVE: max(self.min_tp - have[SampleLabel.TRUE_POSITIVE], 0),
+                   SampleLabel.FALSE_POSITIVE: max(self.min_fp - have[SampleLabel.FALSE_POSITIVE], 0)}
+        self.logger.log(15, f"Pool needs tp: {missing[SampleLabel.TRUE_POSITIVE]}, fp: {missing[SampleLabel.FALSE_POSITIVE]}")
+        if not any(missing.values()):
+            return
+        fresh, group, kind = [], [], None
+
+        def flush():
+            """Mine the waiting group; True once both quotas are filled."""
+            got = self._mine(model, group, missing)
+            group.clear()
+            if got is not None:
+                for lab, cnt in self._counts(got.tp_label).items():
+                    missing[lab] -= cnt
+                fresh.append(got)
+            return all(v <= 0 for v in missing.values())
+
+        done = False
+        for item in iterable:
+            image = item["image"]
+            its = (tuple(image.shape), str(image.dtype))
+            if group and its != kind:                      # a shape change: what waits goes first
+                done = flush()
+                if done:
+                    break
+            kind = its
+            group.append(item)
+            if len(group) == self.batch:
+                done = flush()
+                if done:
+                    break
+        if group and not done:
+            flush()
+        if fresh:
+            self.samples = MinedSamples.cat(([self.samples] if self.samples is not None else []) + fresh)
+
+    def get_samples(self, label):
+        """(X, H): feature maps (N, m, n, C) as a device tensor and scores (N,) as a float32 ndarray of the pooled
+        samples with `label` (copies)."""
+        import torch
+        if self.samples is None:
+            raise RuntimeError("the pool holds no samples")
+        idx = torch.nonzero(self.samples.tp_label == label).reshape(-1)
+        return self.samples.samples[idx], self.samples.scores[idx].cpu().numpy().reshape(-1)
+
+    def get_true_positives(self):
+        return self.get_samples(SampleLabel.TRUE_POSITIVE)
+
+    def get_false_positives(self):
+        return self.get_samples(SampleLabel.FALSE_POSITIVE)
+
+    def to_host(self):
+        """The pool as an ordinary Boxes, as SamplePool.samples holds it (None while empty)."""
+        return None if self.samples is None else self.samples.to_boxes(where=False)
