@@ -18,7 +18,7 @@ import torch
 import verify_reference as ref
 import verify_train_designs as designs
 import verify_train_reference as tr
-from verify_train_designs import random_arrays
+from verify_train_designs import FACTOR, held, pool_for, random_arrays, statement
 from waldboost_amd import _native as nat
 from waldboost_amd import verification as ver
 
@@ -26,8 +26,6 @@ pytestmark = pytest.mark.gpu
 
 GUARD = 64                              # guard words on either side of every buffer the step writes
 SENTINEL = np.float32(-7.25e33)
-FACTOR = 8.0
-FLOOR = 2.0 ** -20
 
 
 def split(flat, shape):
@@ -43,20 +41,22 @@ def split(flat, shape):
 class Device:
     """One training state at the C ABI, every written buffer between guard words."""
 
-    def __init__(self, shape, arrays, X, H, Y, B, dropout=0.2, seed=3, lr=1e-4, scratch_fill=0):
+    def __init__(self, shape, arrays, X, H, Y, B, dropout=0.2, seed=3, lr=1e-4, scratch_fill=0, beta1=0.9, beta2=0.999,
+                 adam_epsilon=1e-7, momentum=0.99, bn_epsilon=1e-3, m=None, v=None, steps_before=0):
         self.lib, self.dev, self.shape, self.B = nat.load(), nat.require_gpu(), shape, B
         flat = tr.flatten(arrays).astype(np.float32)
-        self.params, self.m, self.v = self._guarded(flat), self._guarded(np.zeros_like(flat)), self._guarded(np.zeros_like(flat))
+        state = [np.zeros_like(flat) if part is None else tr.flatten(part).astype(np.float32) for part in (m, v)]
+        self.params, self.m, self.v = self._guarded(flat), self._guarded(state[0]), self._guarded(state[1])
         self.grads, self.loss = self._guarded(np.zeros_like(flat)), self._guarded(np.zeros(1, "f"))
-        self.t = torch.zeros(2, dtype=torch.int32, device=self.dev)
+        self.t = torch.tensor([steps_before, 0], dtype=torch.int32, device=self.dev)
         self.X = torch.from_numpy(np.ascontiguousarray(X)).to(self.dev)
         self.code = nat.WB_DTYPE_U8 if X.dtype == np.uint8 else nat.WB_DTYPE_F32
         self.H, self.Y = (torch.from_numpy(np.ascontiguousarray(v, np.float32)).to(self.dev) for v in (H, Y))
         need = C.c_size_t()
         nat.check(self.lib.wb_verify_train_scratch_bytes(*shape, B, C.byref(need)), "scratch_bytes")
         self.scratch = torch.full((need.value,), scratch_fill, dtype=torch.uint8, device=self.dev)
-        self.hyper = nat.WbVerifyTrainHyper(lr=lr, beta1=0.9, beta2=0.999, adam_epsilon=1e-7, momentum=0.99, bn_epsilon=1e-3,
-                                            dropout=dropout, seed=seed, reserved=0)
+        self.hyper = nat.WbVerifyTrainHyper(lr=lr, beta1=beta1, beta2=beta2, adam_epsilon=adam_epsilon, momentum=momentum,
+                                            bn_epsilon=bn_epsilon, dropout=dropout, seed=seed, reserved=0)
 
     def _guarded(self, values):
         buf = torch.full((values.size + 2 * GUARD,), float(SENTINEL), dtype=torch.float32, device=self.dev)
@@ -88,34 +88,9 @@ class Device:
                 **{k: split(v, self.shape) for k, v in flat.items()}}
 
 
-def pool_for(shape, n_pool, dtype, seed):
-    rng = np.random.default_rng(seed)
-    if dtype == np.uint8:
-        X = rng.integers(0, 256, (n_pool,) + shape).astype(np.uint8)
-    else:
-        X = rng.standard_normal((n_pool,) + shape).astype(np.float32)
-    H = (rng.standard_normal(n_pool) * 0.5).astype(np.float32)
-    Y = rng.choice([-1.0, 1.0], n_pool).astype(np.float32)
-    return X, H, Y
-
-
-def statement(arrays, X, H, Y, idx, dtype, dropout=0.2, seed=3, lr=1e-4, steps_before=0):
-    state = tr.new_state(arrays, dtype)
-    state["t"] = steps_before
-    out = tr.train_step(state, X[idx].astype(np.float32), H[idx], Y[idx], dtype, seed=seed, dropout=dropout, lr=lr)
-    return out, state
-
-
-def held(gpu, s64, s32):
-    """(largest difference, the rule's unit) of one array.  An array that is zero in both statements has the smallest
-    positive unit: the GPU's must be zero too."""
-    s64 = np.asarray(s64, np.float64)
-    unit = max(np.abs(np.asarray(s32, np.float64) - s64).max(), FLOOR * np.abs(s64).max(), np.finfo(np.float64).tiny)
-    return np.abs(np.asarray(gpu, np.float64).reshape(s64.shape) - s64).max(), unit
-
-
 def check_step(got, arrays, o64, st64, o32, st32, label):
-    """The one-step rule on the loss, every gradient, the moving statistics and the parameters after the update."""
+    """The one-step rule on the loss, every gradient, the moving statistics, the parameters after the update and Adam's
+    m and v (on all their elements: they are smooth in g).  `arrays` are the parameters before the step."""
     diff, unit = held(got["loss"], o64["loss"], o32["loss"])
     report = [("loss", diff / unit)]
     assert diff <= FACTOR * unit, (label, "loss", diff, unit)
@@ -128,8 +103,7 @@ def check_step(got, arrays, o64, st64, o32, st32, label):
         diff, unit = held(got["grads"][k], o64["grads"][k], o32["grads"][k])
         report.append((f"g{k}", diff / unit))
         assert diff <= FACTOR * unit, (label, "gradient", k, diff, unit)
-        g64 = np.asarray(o64["grads"][k], np.float64).reshape(arrays[k].shape)
-        compared = np.ones(arrays[k].shape, bool) if tr.is_moving(k) else (np.abs(g64) > FACTOR * unit) | (g64 == 0)
+        compared = designs.compared_mask(k, arrays, o64, o32)
         left_out += compared.size - compared.sum()
         total += compared.size
         if compared.any():
@@ -137,6 +111,13 @@ def check_step(got, arrays, o64, st64, o32, st32, label):
             diff, unit = held(got["params"][k][compared], p64, p32)
             report.append((f"p{k}", diff / unit))
             assert diff <= FACTOR * unit, (label, "parameter", k, diff, unit)
+        if tr.is_moving(k):
+            assert not got["m"][k].any() and not got["v"][k].any()
+            continue
+        for name in ("m", "v"):
+            diff, unit = held(got[name][k], st64[name][k], st32[name][k])
+            report.append((f"{name}{k}", diff / unit))
+            assert diff <= FACTOR * unit, (label, "Adam's " + name, k, diff, unit)
     worst = max(r for _, r in report)
     print(f"{label}: largest ratio {worst:.3f} ({max(report, key=lambda x: x[1])[0]}), {left_out} of {total} parameters left out")
     assert left_out <= 0.05 * total, (label, left_out, total)
@@ -144,24 +125,26 @@ def check_step(got, arrays, o64, st64, o32, st32, label):
     return worst
 
 
-CASES = [((2, 2, 1), 2), ((3, 5, 2), 4), ((5, 6, 3), 6), ((14, 14, 4), 64), ((13, 32, 9), 8), ((32, 32, 16), 4)]
+def run_case(case, label):
+    """One step of a case of verify_train_designs on the device, held to its two statements."""
+    (o64, st64), (o32, st32) = designs.both_statements(case)
+    shape, B = case["X"].shape[1:], len(case["idx"])
+    dev = Device(shape, case["arrays"], case["X"], case["H"], case["Y"], B, m=case.get("m"), v=case.get("v"),
+                 steps_before=case.get("steps_before", 0), **case.get("hyper", {}))
+    got = dev.step(case["idx"])
+    return got, o64, check_step(got, case["arrays"], o64, st64, o32, st32, label)
+
+
+CASES = designs.SHORT_CASES + designs.LONG_CASES
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.uint8], ids=["f32", "u8"])
 @pytest.mark.parametrize("shape,B", CASES, ids=str)
 def test_one_step_against_the_statement(shape, B, dtype):
-    arrays = random_arrays(shape, 20 + shape[0])
-    X, H, Y = pool_for(shape, B + 3, dtype, 30 + shape[1])
-    rng = np.random.default_rng(B)
-    idx = rng.integers(0, B + 3, B)
-    if B > 2:
-        idx[1] = idx[0]                                                 # a duplicate: it counts twice
-    else:
-        idx = rng.permutation(B + 3)[:B]                                # (two copies of one window: no variance, every gradient 0)
-    o64, st64 = statement(arrays, X, H, Y, idx, np.float64)
-    o32, st32 = statement(arrays, X, H, Y, idx, np.float32)
-    got = Device(shape, arrays, X, H, Y, B).step(idx)
-    check_step(got, arrays, o64, st64, o32, st32, f"{shape} B={B} {np.dtype(dtype).name}")
+    """The long batches reach what B <= 66 leaves unused: weight-gradient ranges of several windows and of unequal length,
+    the cap of 128 per-channel partials (rows_per above 256, 128-long combines) for the full-size and the pooled layers,
+    and the head's second to fourth window per thread and its whole loss tree."""
+    run_case(designs.one_step_case(shape, B, dtype), f"{shape} B={B} {np.dtype(dtype).name}")
 
 
 def test_a_saturated_batch_moves_nothing_but_the_moving_statistics():
@@ -253,6 +236,53 @@ def test_one_live_window_at_either_end_of_the_batch(B, slot):
     got = Device(shape, arrays, X, H, Y, B).step(idx)
     assert got["grads"][24].any() and got["grads"][0].any()
     check_step(got, arrays, o64, st64, o32, st32, f"B={B}, live window {live}")
+
+
+@pytest.mark.parametrize("B,live", designs.LIVE_CASES)
+def test_one_live_window_at_the_partition_edges(B, live):
+    """(6,6,1): the live window at slot 0, at slot B - 1, on both sides of the weight-gradient range boundary where the
+    ranges grow by a window, in a slot that is its head thread's second window, and where the loss tree's halves meet.  A
+    kernel that drops or doubles the window at such an edge loses or doubles every weight gradient
+    (test_verify_train_host.py: a dropped live window moves arrays 0, 6, 12, 18 and 24 by thousands of units)."""
+    case = designs.one_live_case(B, live)
+    got, o64, _ = run_case(case, f"{designs.LIVE_SHAPE} B={B}, live window {live}")
+    inside = (o64["losses"] > 1e-6) & (o64["losses"] < 1e3)
+    assert inside[live] and inside.sum() == 1
+    assert got["grads"][24].any() and got["grads"][0].any()
+
+
+@pytest.mark.parametrize("shape", designs.TIE_SHAPES, ids=str)
+def test_pool_ties_at_positive_maxima_go_to_the_first_maximum(shape):
+    """Equal input pixels inside a pool cell give bit-equal maxima of block 2 (blocks 1 and 2 are pointwise by design), in
+    more than half of the (cell, channel) pairs; the pool's choice among them routes the gradient of kernels 0 and 6
+    through different neighbourhoods.  The last maximum, or every maximum, in vt_pool_bwd would move those two gradients
+    by 1e5 units and more (test_verify_train_host.py); (7,6,2) puts the dropped row next to tied cells."""
+    got, _, _ = run_case(designs.pool_tie_case(shape), f"pool ties {shape}")
+    assert got["grads"][0].any() and got["grads"][6].any()
+
+
+def test_steps_two_and_three_from_the_devices_own_state():
+    """Each step's statements start from what the device held before it (parameters, m, v, t), so no error compounds and
+    the one-step rule holds at every step: the recurrences on a non-zero m and v, lr_t at t >= 1 and the masks of step t."""
+    base = designs.later_steps_case()
+    shape, B = designs.LATER_SHAPE, designs.LATER_B
+    dev = Device(shape, base["arrays"], base["X"], base["H"], base["Y"], B)
+    arrays, m, v = base["arrays"], None, None
+    for t, row in enumerate(base["rows"]):
+        case = dict(base, idx=row, arrays=arrays, m=m, v=v, steps_before=t)
+        (o64, st64), (o32, st32) = designs.both_statements(case)
+        got = dev.step(row)
+        check_step(got, arrays, o64, st64, o32, st32, f"step {t + 1} of three")
+        assert got["t"] == t + 1
+        arrays, m, v = got["params"], got["m"], got["v"]
+    assert any(a.any() for a in m) and any(a.any() for a in v)
+
+
+def test_one_step_away_from_every_default_constant():
+    """lr, beta1, beta2, adam_epsilon, momentum, bn_epsilon, dropout and seed all differ from the defaults, from a state
+    with non-zero m and v and t = 2: a constant that is hard-coded or read from the wrong field fails (the host twin shows
+    that each constant alone moves some array by more than the bound)."""
+    run_case(designs.nondefault_case(), "non-default constants")
 
 
 # ---- Trainer and train, end to end on the planted pool

@@ -6,6 +6,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import verify_train_designs as designs
 import verify_train_reference as tr
 from verify_train_designs import random_arrays, random_batch
 from waldboost_amd import _native as nat
@@ -234,6 +235,138 @@ def test_training_entry_points_validate_without_a_gpu():
                                         1024, 1 << 30, 1024, None) == nat.WB_ERR_INVALID
         assert "hyper" in nat.last_error()
     assert nat.WB_ABI_VERSION == 8 and lib.wb_abi_version() == 8
+
+
+# ---- host twins of the GPU cases (tests/verify_train_designs.py): from the float64 and float32 statements alone, the rule
+# leaves out at most 2.5 % of the parameters -- half the GPU tests' cap, because the GPU's unit is the statement's -- and a
+# wrong kernel would move the result by more than the rule allows.
+def moved(k, wrong, o64, o32, key="grads"):
+    """By how many of the rule's units array k of `wrong` differs from the float64 statement."""
+    diff, unit = designs.held(wrong[key][k], o64[key][k], o32[key][k])
+    return diff / unit
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.uint8], ids=["f32", "u8"])
+@pytest.mark.parametrize("shape,B", designs.LONG_CASES, ids=str)
+def test_long_batch_cases_leave_out_little(shape, B, dtype):
+    case = designs.one_step_case(shape, B, dtype)
+    assert len(set(case["idx"])) < B <= len(case["X"]) - 3
+    (o64, _), (o32, _) = designs.both_statements(case)
+    share = designs.left_out_share(case["arrays"], o64, o32)
+    print(f"{shape} B={B} {np.dtype(dtype).name}: {100 * share:.2f} % left out")
+    assert share <= designs.LEFT_OUT_HOST
+    # what the case is there to reach
+    P, P2 = shape[0] * shape[1], (shape[0] // 2) * (shape[1] // 2)
+    lengths = {b1 - b0 for b0, b1 in (designs.wgrad_range(B, g) for g in range(128))}
+    want = {((2, 3, 1), 130): ({1, 2}, 4, 1), ((4, 4, 2), 1022): ({7, 8}, 64, 16), ((6, 6, 1), 1024): ({8}, 128, 36),
+            ((10, 14, 1), 1024): ({8}, 128, 128)}[(shape, B)]
+    assert (lengths, min(128, -(-B * P // 256)), min(128, -(-B * P2 // 256))) == want
+
+
+def test_live_window_slots_sit_on_the_partition_edges():
+    assert designs.live_slots(130) == [0, 62, 63, 64, 65, 129]             # ranges 62: [62, 63), 63: [63, 65), 64: [65, 66)
+    assert [designs.wgrad_range(130, g) for g in (62, 63, 64)] == [(62, 63), (63, 65), (65, 66)]
+    assert designs.live_slots(258) == [0, 125, 126, 256, 257] and designs.wgrad_range(258, 63) == (126, 129)
+    assert designs.live_slots(1022) == [0, 6, 7, 261, 1021] and designs.wgrad_range(1022, 1) == (7, 15)
+    assert designs.live_slots(1024) == [0, 261, 511, 512, 1023]
+    for B in (130, 258, 1022, 1024):
+        assert designs.wgrad_range(B, 0)[0] == 0 and designs.wgrad_range(B, 127)[1] == B
+
+
+@pytest.mark.parametrize("B,live", designs.LIVE_CASES)
+def test_one_live_window_cases_leave_out_little_and_see_the_window(B, live):
+    case = designs.one_live_case(B, live)
+    (o64, _), (o32, _) = designs.both_statements(case)
+    inside = (o64["losses"] > 1e-6) & (o64["losses"] < 1e3)
+    assert inside[live] and inside.sum() == 1
+    assert designs.left_out_share(case["arrays"], o64, o32) <= designs.LEFT_OUT_HOST
+    # a kernel that drops the live window: its dp is 0, which is the statement with that window saturated as well
+    dropped, _ = designs.statement(**designs.one_live_case(B, live, saturate_all=True), dtype=np.float64)
+    assert not ((dropped["losses"] > 1e-6) & (dropped["losses"] < 1e3)).any()
+    for k in (0, 6, 12, 18, 24):
+        assert moved(k, dropped, o64, o32) > designs.FACTOR, k
+
+
+@pytest.fixture
+def block2_outputs(monkeypatch):
+    """Block 2's output as pool2x2_backward sees it, by dtype name."""
+    seen, true_pool = {}, tr.pool2x2_backward
+
+    def spy(a, dpool):
+        seen[a.dtype.name] = a.copy()
+        return true_pool(a, dpool)
+    monkeypatch.setattr(tr, "pool2x2_backward", spy)
+    return seen
+
+
+@pytest.mark.parametrize("shape,ties,first", [((6, 6, 2), 161, [100, 39, 22, 0]), ((7, 6, 2), 156, [98, 39, 19, 0])], ids=str)
+def test_pool_tie_design_has_ties_that_reach_the_weight_gradients(shape, ties, first, block2_outputs, monkeypatch):
+    assert shape in designs.TIE_SHAPES
+    case = designs.pool_tie_case(shape)
+    (o64, _), (o32, _) = designs.both_statements(case)
+    assert designs.left_out_share(case["arrays"], o64, o32) <= designs.LEFT_OUT_HOST
+    tied64, first64 = designs.tie_census(block2_outputs["float64"])
+    tied32, first32 = designs.tie_census(block2_outputs["float32"])
+    # 288 (cell, channel) pairs; a tie's first maximum cannot be the cell's last pixel
+    assert tied64.size == 288 and tied64.sum() == ties and np.bincount(first64[tied64], minlength=4).tolist() == first
+    assert np.array_equal(tied64, tied32) and np.array_equal(first64, first32)
+    for wrong_pool in (designs.pool2x2_backward_last, designs.pool2x2_backward_all):
+        monkeypatch.setattr(tr, "pool2x2_backward", wrong_pool)
+        wrong, _ = designs.statement(**case, dtype=np.float64)
+        ratios = [moved(k, wrong, o64, o32) for k in (0, 6)]
+        print(shape, wrong_pool.__name__, "moves the gradients of kernels 0 and 6 by", ratios, "units")
+        assert min(ratios) > designs.FACTOR
+
+
+def test_the_wrong_pools_are_wrong_only_at_ties():
+    a = np.zeros((1, 2, 4, 1))
+    a[0, :, 0:2, 0] = [[1, 4], [4, 2]]
+    a[0, :, 2:4, 0] = [[0, 3], [1, 2]]
+    d = np.array([5.0, 7.0]).reshape(1, 1, 2, 1)
+    assert np.array_equal(tr.pool2x2_backward(a, d)[0, :, :, 0], [[0, 5, 0, 7], [0, 0, 0, 0]])
+    assert np.array_equal(designs.pool2x2_backward_last(a, d)[0, :, :, 0], [[0, 0, 0, 7], [5, 0, 0, 0]])
+    assert np.array_equal(designs.pool2x2_backward_all(a, d)[0, :, :, 0], [[0, 5, 0, 7], [5, 0, 0, 0]])
+
+
+def test_later_steps_leave_out_little():
+    """The GPU test starts each step's statements from the device's state; here the float32 statement's own state stands
+    in for it."""
+    base = designs.later_steps_case()
+    assert len({tuple(row) for row in base["rows"]}) == 3
+    arrays, m, v = base["arrays"], None, None
+    for t, row in enumerate(base["rows"]):
+        (o64, _), (o32, st32) = designs.both_statements(dict(base, idx=row, arrays=arrays, m=m, v=v, steps_before=t))
+        assert designs.left_out_share(arrays, o64, o32) <= designs.LEFT_OUT_HOST
+        assert st32["t"] == t + 1
+        arrays, m, v = st32["params"], st32["m"], st32["v"]
+
+
+def test_every_non_default_constant_moves_the_step():
+    case = designs.nondefault_case()
+    assert case["steps_before"] == 2 and all(designs.NONDEFAULT[name] != designs.DEFAULTS[name] for name in designs.DEFAULTS)
+    updated = [k for k in range(28) if not tr.is_conv_bias(k)]
+    adam = [k for k in updated if not tr.is_moving(k)]
+    assert all(case["m"][k].any() and case["v"][k].any() for k in adam)
+    (o64, st64), (o32, st32) = designs.both_statements(case)
+    assert designs.left_out_share(case["arrays"], o64, o32) <= designs.LEFT_OUT_HOST
+
+    def distance(hyper):
+        """Per kind of result, the ratios by which the step under `hyper` differs from the step under NONDEFAULT."""
+        (other, st), _ = designs.both_statements(designs.nondefault_case(hyper))
+        return {"params": [moved(k, st, st64, st32, "params") for k in updated], "m": [moved(k, st, st64, st32, "m") for k in adam],
+                "v": [moved(k, st, st64, st32, "v") for k in adam], "grads": [moved(k, other, o64, o32) for k in updated]}
+    # under the defaults every updated array, and Adam's state of each, lands elsewhere
+    far = distance(designs.DEFAULTS)
+    assert min(far["params"]) > designs.FACTOR and min(far["m"]) > designs.FACTOR and min(far["v"]) > designs.FACTOR
+    # and no constant hides behind the others: each one alone, put back to its default, moves what it enters
+    enters = dict(lr=["params"], beta1=["params", "m"], beta2=["params", "v"], adam_epsilon=["params"], momentum=["params"],
+                  bn_epsilon=["grads", "params", "m", "v"], dropout=["grads", "params", "m", "v"], seed=["grads", "params", "m", "v"])
+    for name, kinds in enters.items():
+        near = distance(dict(designs.NONDEFAULT, **{name: designs.DEFAULTS[name]}))
+        for kind in kinds:
+            assert max(near[kind]) > designs.FACTOR, (name, kind)
+        if name == "momentum":
+            assert min(near["params"][k] for k, a in enumerate(updated) if tr.is_moving(a)) > designs.FACTOR
 
 
 def test_the_statement_alone_meets_the_loss_cap():
