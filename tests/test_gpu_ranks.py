@@ -13,6 +13,7 @@ from waldboost_amd import engine as _engine
 from waldboost_amd import _native as nat
 from waldboost_amd.channels import channel_spec, read_opts
 from waldboost_amd.synth import random_tree_arrays, synth_image
+from rank_designs import mirror_tables
 from util import oracle_detect
 
 pytestmark = pytest.mark.gpu
@@ -123,10 +124,14 @@ def test_special_thresholds_and_float_images_that_overflow():
     assert np.array_equal(bits(a["scores"]), bits(b["scores"]))
 
 
+CLUSTERED_K = {0.0: (2, 3), 1e-3: (16, 21), 0.5: (12, 17)}      # spread -> most thresholds in a cell, one- and two-byte grid
+
+
 @pytest.mark.parametrize("spread", [0.0, 1e-3, 0.5])
 def test_clustered_thresholds_share_lookup_cells(spread):
     """Most thresholds within `spread` of a few centres, plus outliers that stretch the grid: several
-    thresholds per cell (refinement steps > 1), or, when too many share one cell, no rank tables at all."""
+    thresholds per cell (refinement steps > 1: the pair fetch at 2, the loop at 12 and at the 16 a cell may hold) -- the
+    forms the model has are those the mirror of the table builder (rank_designs.mirror_tables) gives it."""
     rng = np.random.default_rng(3)
     centres = np.array([7.25, 7.5, 30.0], np.float32)
 
@@ -135,8 +140,11 @@ def test_clustered_thresholds_share_lookup_cells(spread):
         return np.where(rng.random(n) < 0.1, rng.uniform(-1e4, 1e4, n), v)
     M = model_with_thresholds(rng, 48, 2, draw)
     img = synth_image(160, 230, 14)
-    if M.device_cascade().rank_ok:
-        check_ranks(M, img)
+    t8, t16 = (mirror_tables(sorted_thresholds(M), wide) for wide in (False, True))
+    assert (t8["K"], t16["K"]) == CLUSTERED_K[spread]
+    dm = M.device_cascade()
+    assert dm.rank_ok and dm.rank16_ok and dm.rank_dtype == nat.WB_DTYPE_RANK8
+    check_ranks(M, img)
     check_detect(M, img)
 
 

@@ -102,6 +102,22 @@ void dump_stages(const WbModel *M, int n_records, const std::vector<int32_t> *pa
     fclose(f);
 }
 
+// WB_DUMP_RANKS=path (diagnostic): for each rank form built, int32 {wide, K, slots, cells}, float k[4], float b[4], then
+// the lut bytes (float S[4][slots], then base[4][cells]: uint8, wide: uint16); an empty file when none was built
+void dump_ranks(const RankTables *const *rt, const int *wide, int n) {
+    const char *path = getenv("WB_DUMP_RANKS");
+    FILE *f = path ? fopen(path, "wb") : nullptr;
+    if (!f) return;
+    for (int i = 0; i < n; ++i) {
+        const int32_t hdr[4] = {wide[i], rt[i]->K, wide[i] ? WB_BIN16_SLOTS : WB_BIN_SLOTS, wide[i] ? WB_BIN16_CELLS : WB_BIN_CELLS};
+        fwrite(hdr, 4, 4, f);
+        fwrite(rt[i]->k, 4, 4, f);
+        fwrite(rt[i]->b, 4, 4, f);
+        fwrite(rt[i]->lut.data(), 1, rt[i]->lut.size(), f);
+    }
+    fclose(f);
+}
+
 }  // namespace
 
 extern "C" int wb_model_create(int n_stages, const int32_t *node_off, const uint8_t *feature,
@@ -174,6 +190,14 @@ extern "C" int wb_model_create(int n_stages, const int32_t *node_off, const uint
             if (f != WB_FORM_F32) M->form[f].stages_host = host_copy(packs[f].data(), packs[f].size());
         }
         dump_stages(M, n_stages + G, packs);
+        const RankTables *built[2];
+        int wide[2], n_built = 0;
+        for (int w = 0; w < 2; ++w)
+            if (M->form[WB_FORM_RANK8 + w].present) {
+                built[n_built] = &rt[w];
+                wide[n_built++] = w;
+            }
+        dump_ranks(built, wide, n_built);
     }
     // host copy of the trees as the caller gave them (wb_rankgroup_create)
     const int32_t zero = 0;
@@ -329,10 +353,14 @@ extern "C" int wb_rankgroup_create(const WbModel *const *models, int n, WbRankGr
         sets.push_back(&trees[i]);
     }
     RankTables rt;
+    const RankTables *built = &rt;
+    const int narrow = 0;
     if (getenv("WB_NO_RANKS") != nullptr || !build_rank_tables(sets, rt)) {
+        dump_ranks(&built, &narrow, 0);
         wb_set_error("wb_rankgroup_create: the models' thresholds do not fit one rank table (more than %d distinct per channel)", WB_BIN_MAX);
         return WB_ERR_UNSUPPORTED;
     }
+    dump_ranks(&built, &narrow, 1);
     WbRankGroup *g = new WbRankGroup{std::vector<WbModel *>((size_t)n, nullptr), nullptr};
     Upload up;
     up(&g->lut_dev, rt.lut.data(), rt.lut.size());
