@@ -5,8 +5,9 @@ chain on every tile), a batch of two in one launch (the per-workgroup flag must 
 batch-mate), and the rank bytes through a small cascade whose thresholds tell an exact 0 from a residue from an ordinary
 value.  test_gradient_designs_host.py proves what the designs hold and that a wrong kernel would show.
 
-grad_mag, grad_hist_4_u1 and grad_mag_u1 ride along on the same images at their cells: nothing is designed for them (no
-projection, no residues, no flag), the images are simply further inputs with many zero and extreme gradients."""
+grad_mag, grad_hist_4_u1 and grad_mag_u1 ride along on the same images at their cells: these images are not designed for
+them (no projection, no residues, no flag), they are simply further inputs with many zero and extreme gradients.  Their own
+designs are u1_designs.py (test_gpu_u1_designs.py) and gradmag_designs.py (test_gpu_gradmag_designs.py)."""
 import numpy as np
 import pytest
 
