@@ -178,7 +178,7 @@ typedef struct WbModelInfo {
     int32_t n_stages;
     int32_t depth;      /* depth of the canonical complete trees the kernels walk  */
     int32_t m, n, C;    /* window shape (rows, cols, channels)                     */
-    int32_t tile_rows;  /* cascade tile: tile_rows x 64 windows per workgroup      */
+    int32_t tile_rows;  /* cascade tile: tile_rows x 64 windows, the unit of WbTile.ty (wb_model_form_rows) */
     int32_t tile_cols;
     int32_t lds_bytes;  /* dynamic LDS per workgroup of the cascade kernel         */
     int32_t rank_ok;    /* 1 = the model has rank tables (WB_DTYPE_RANK8 channels)  */
@@ -321,6 +321,16 @@ int wb_model_specialize(WbModel *model, int chn_dtype);
  * them off the generic kernel scans.  For callers that cross-check a specialised kernel on their own data before they
  * rely on it (the Python engine does, on the image at hand, right after wb_model_specialize), or retire one. */
 int wb_model_use_specialized(WbModel *model, int enable);
+/* The tile of the kernel that scans channels of chn_dtype: *tile_rows window rows (x tile_cols) per workgroup, and its
+ * dynamic LDS in *lds_bytes (may be NULL).  The rows are wb_model_info's tile_rows -- the float32 form's, and the unit of
+ * WbTile.ty for every form -- or a whole multiple k of it: the one-byte forms (WB_DTYPE_U8, WB_DTYPE_RANK8) scan tiles
+ * of 64 x 64 windows where 40 KB of LDS hold them.  Such a kernel serves the table entries whose ty is a multiple of k,
+ * each for k units of rows, and its workgroups leave at once on the others: a table of every unit is right for every
+ * form, and a table for one form may hold only the entries that start a tile. */
+int wb_model_form_rows(const WbModel *model, int chn_dtype, int *tile_rows, int *lds_bytes);
+/* The same without a handle or a GPU: the tile wb_model_create chooses for a cascade of n_stages trees of `depth` on
+ * (m, n, C) windows, for channels of chn_dtype.  out[4] = {rows per wave, waves, tile_rows, lds_bytes}. */
+int wb_model_geometry(int n_stages, int depth, int m, int n, int C, int chn_dtype, int32_t *out);
 
 /* Several cascades over ONE pyramid of threshold ranks (waldboost.detect(image, *models), reference __init__.py:120-124:
  * the channels are computed once for all models): one rank table per channel from the UNION of the members'
@@ -339,6 +349,8 @@ int wb_rankgroup_destroy(WbRankGroup *group);
 int wb_jit_compile_check(int depth, int n_stages, const char *arch, int64_t *code_bytes);
 /* The same for a tile of elem_bytes-wide elements (1: uint8 channels / WB_DTYPE_RANK8, 2: WB_DTYPE_RANK16). */
 int wb_jit_compile_check2(int depth, int n_stages, int elem_bytes, const char *arch, int64_t *code_bytes);
+/* The same with rpw window rows per wave on eight waves (4: the tile of 32 rows, 8: the one-byte forms' 64). */
+int wb_jit_compile_check3(int depth, int n_stages, int elem_bytes, int rpw, const char *arch, int64_t *code_bytes);
 
 /* Dense sliding-window cascade over all levels of all images.
  *   chn           [u][v][C] per level as written by wb_channels_launch (or caller-provided), of
@@ -347,7 +359,8 @@ int wb_jit_compile_check2(int depth, int n_stages, int elem_bytes, const char *a
  *                 WB_DTYPE_RANK8 (ranks of float32 channels for THIS model); a byte
  *                 buffer must extend 16 bytes past its last element (16-byte group loads)
  *   tiles         dev WbTile[n_tiles]: tiles of tile_rows x tile_cols WINDOWS over the
- *                 (u-m) x (v-n) window grid of each level
+ *                 (u-m) x (v-n) window grid of each level; ty counts wb_model_info's
+ *                 tile_rows for every chn_dtype (wb_model_form_rows: a form with taller tiles)
  *   det           dev WbDet[WB_DET_SHARDS][shard_capacity]; det_count dev uint32[WB_DET_SHARDS]:
  *                 survivors per shard (a count may exceed shard_capacity: the records beyond it
  *                 are dropped, the count stays exact -- grow the buffer and launch again)

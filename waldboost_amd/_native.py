@@ -90,6 +90,9 @@ SYMBOLS = {
     "wb_model_use_specialized": (C.c_int, [_P, C.c_int]),
     "wb_jit_compile_check": (C.c_int, [C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_int64)]),
     "wb_jit_compile_check2": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_int64)]),
+    "wb_jit_compile_check3": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_int64)]),
+    "wb_model_form_rows": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "wb_model_geometry": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
     "wb_rankgroup_create": (C.c_int, [C.POINTER(_P), C.c_int, C.POINTER(_P)]),
     "wb_rankgroup_model": (C.c_int, [_P, C.c_int, C.POINTER(_P)]),
     "wb_rankgroup_destroy": (C.c_int, [_P]),

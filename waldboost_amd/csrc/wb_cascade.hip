@@ -15,14 +15,15 @@
 // The two walks -- a stage of the model's flat arrays, one tree's uint8 / int8 arrays -- stand here once each (flat_stage,
 // tree_leaf).  What reads the detection records the cascade leaves is in wb_det.hip.
 //
-// The tiled cascade: one workgroup owns a tile of TR x 64 windows of one level of one image:
+// The tiled cascade: one workgroup owns a tile of TR x 64 windows of one level of one image (TR per tile form: 32 rows,
+// 64 on the one-byte forms where 40 KB of LDS hold them -- wb_model.hip, choose_geometry):
 //   * the (TR+m-1) x (64+n-1) x C channel block is staged once into LDS, planar, so that a
 //     wavefront's 64 lanes (64 adjacent window columns) gather from 64 adjacent banks;
 //   * wave-synchronous stages: every lane of a wave is at the same stage, so the stage records
 //     come in through the scalar cache (s_load) and cost no vector memory or LDS traffic; stages
 //     are evaluated in groups of G with all 2*G gathers in flight (only the fp32 accumulation
 //     and the rejection tests are sequential);
-//   * phase A runs the first stages with RPW windows per lane; survivors are compacted with
+//   * phase A runs the first stages with RPW windows per lane, four rows at a time; survivors are compacted with
 //     wave ballot + mbcnt into the wave's own LDS queue; phase B re-packs them densely for
 //     geometrically growing stage segments, compacting in place after each segment, and pools
 //     the survivors of the whole workgroup once, at stage 8, so that a few waves hold full
@@ -289,6 +290,15 @@ struct CascEnv {
 
 int wb_cascade_group(int depth) { return depth >= 3 ? 2 : 4; }
 
+bool wb_cascade_has_kernel(int depth, int rpw, int waves) {
+    if (depth < 1 || depth > WB_CASC_MAX_DEPTH) return false;
+#define WB_X(R, W) \
+    if (rpw == R && waves == W) return true;
+    WB_CASC_CONFIGS(WB_X)
+#undef WB_X
+    return false;
+}
+
 // dynamic LDS of the tile kernel in the layout of wb_cascade_tile.h; eb: 0 float32 tile, 1 bytes, 2 16-bit ranks
 int wb_cascade_lds_bytes(int eb, int C, int rows, int pitch, int TR, int waves, int T, int lds_stages, int depth) {
     return (int)(wb_lds_stab_off(eb, C, rows, pitch, TR, T, waves) + (size_t)lds_stages * WB_STAGE_DWORDS(depth) * 4 + WB_LDS_CTL_BYTES);
@@ -342,7 +352,8 @@ extern "C" int wb_cascade_launch_z(void *stream, const WbModel *model, const voi
     a.m = model->m;
     a.n = model->n;
     a.C = model->C;
-    a.lds_rows = model->lds_rows;
+    a.lds_rows = rec.lds_rows;
+    a.tile_unit = model->tile_rows;
     a.lds_pitch = model->lds_pitch;
     a.lds_stages = model->lds_stages;
     a.det = det;
@@ -376,7 +387,7 @@ extern "C" int wb_cascade_launch_z(void *stream, const WbModel *model, const voi
                                            params, nullptr));
         return WB_OK;
     }
-    return casc_dispatch(model->depth, model->rpw, model->waves, [&](auto d, auto r, auto w) {
+    return casc_dispatch(model->depth, rec.rpw, model->waves, [&](auto d, auto r, auto w) {
         constexpr int D = decltype(d)::value, R = decltype(r)::value, W = decltype(w)::value;
         if (a.chn_u8 == 2)
             hipLaunchKernelGGL((cascade_tile_kernel<D, R, W, 2>), grid, dim3(W * 64), lds, st, a, a.stages);

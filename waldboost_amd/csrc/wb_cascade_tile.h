@@ -51,6 +51,9 @@ static __device__ const int32_t kWbStages[] = {WB_JIT_STAGE_WORDS};
 #ifndef WB_JIT_WAVES
 #define WB_JIT_WAVES 8
 #endif
+#ifndef WB_JIT_RPW
+#define WB_JIT_RPW 4
+#endif
 #else
 static __device__ const int32_t kWbStages[1] = {0};
 #define WB_JIT_SEGMENTS(X)
@@ -58,6 +61,7 @@ static __device__ const int32_t kWbStages[1] = {0};
 #define WB_JIT_T 0
 #define WB_JIT_LDS_STAGES 0
 #define WB_JIT_WAVES 8
+#define WB_JIT_RPW 4
 #define WB_JIT_C 0
 #define WB_JIT_ROWS 0
 #define WB_JIT_PITCH 0
@@ -74,8 +78,11 @@ __host__ __device__ constexpr size_t wb_lds_tile_bytes(int eb, int C, int rows, 
 // windows within its first eight stages (431 of 2048 survive them on the benchmark model), and the rare tile that keeps
 // more goes on DENSELY (a lane mask per row, as in phase A) eight stages at a time until its survivors fit.  Under 32 KB
 // of LDS a fifth workgroup fits a CU once waves of the resident four have left (they no longer wait at a final barrier).
+// A tile taller than 32 rows (the one-byte forms' 64 x 64 tile) keeps twice the windows behind phase A -- 860 of 4096 on the
+// benchmark model -- and gets 256 entries more: 1280 with eight waves, which leaves that tile's LDS at 40 KB (four
+// workgroups per CU).
 __host__ __device__ constexpr int wb_casc_qcap(int TR, int WAVES) {
-    return TR * 64 < 64 * WAVES + 512 ? TR * 64 : 64 * WAVES + 512;
+    return TR * 64 < 64 * WAVES + (TR > 32 ? 768 : 512) ? TR * 64 : 64 * WAVES + (TR > 32 ? 768 : 512);
 }
 __host__ __device__ constexpr size_t wb_lds_stab_off(int eb, int C, int rows, int pitch, int TR, int T, int WAVES) {
     return (wb_lds_tile_bytes(eb, C, rows, pitch) + (size_t)wb_casc_qcap(TR, WAVES) * 8 + (size_t)T * 4 + 15) & ~(size_t)15;
@@ -126,6 +133,8 @@ struct CascArgs {
     uint32_t *zero;             // words the NEXT step's first kernel accumulates into (the octaves' min / max keys): reset here
     int zero_words;
     int dbg;                    // diagnostics (WB_CASC_DBG): 1 = skip the tile load, 2 = stop after the load
+    int tile_unit;              // window rows per unit of WbTile.ty (wb_model_info's tile_rows): a kernel whose tile is k units
+                                // tall serves the entries whose ty is a multiple of k and leaves at once on the others
 };
 
 __device__ inline float as_f(int32_t x) { return __int_as_float(x); }
@@ -324,7 +333,7 @@ template <int D, int RPW, int WAVES, int EB, bool BAKED>
 __device__ __forceinline__ void cascade_tile_body(const CascArgs &a, const int32_t *__restrict__ stages) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     static_assert((2 * WAVES + 2) * 4 <= WB_LDS_CTL_BYTES, "control words");
-    static_assert(!BAKED || WAVES == WB_JIT_WAVES, "the prelude's wave count");
+    static_assert(!BAKED || (WAVES == WB_JIT_WAVES && RPW == WB_JIT_RPW), "the prelude's wave count and rows per wave");
     constexpr int NT = WAVES * 64;
     constexpr int TR = RPW * WAVES;
     constexpr int SD = WB_STAGE_DWORDS(D);
@@ -355,7 +364,7 @@ __device__ __forceinline__ void cascade_tile_body(const CascArgs &a, const int32
 
     const int nr = L.u - a.m > 0 ? L.u - a.m : 0;          // window grid
     const int nc = L.v - a.n > 0 ? L.v - a.n : 0;
-    const int r0 = tile_d.ty * TR, c0 = tile_d.tx * WB_CASC_TC;
+    const int r0 = tile_d.ty * a.tile_unit, c0 = tile_d.tx * WB_CASC_TC;
 
     // LDS mirror of the stage table (when it is small enough): the tail reads one record per lane
     const size_t stab_off = wb_lds_stab_off(EB, nC, rows, pitch, TR, T, WAVES);
@@ -373,6 +382,8 @@ __device__ __forceinline__ void cascade_tile_body(const CascArgs &a, const int32
     // workgroup resets them for the next step's octave kernel, which then needs no memset launch in front of it)
     if (blockIdx.x == 0 && blockIdx.y == 0)
         for (int i = tid; i < a.zero_words; i += NT) a.zero[i] = 0u;
+    // (a tile table in units shorter than this kernel's tile: the entry that starts a tile stands for the whole of it)
+    if (r0 % TR != 0) return;
     if constexpr (BAKED) {
         // the specialised stages address LDS by number: the dynamic region must start at LDS address 0
         if ((uint32_t)(size_t)(__attribute__((address_space(3))) unsigned char *)smem != 0u) __builtin_trap();
@@ -529,33 +540,44 @@ __device__ __forceinline__ void cascade_tile_body(const CascArgs &a, const int32
     WB_STAMP(1);
     if (a.dbg & 2) return;
 
-    // ---- phase A: RPW windows per lane through stages [0, S0)
+    // ---- phase A: RPW windows per lane through stages [0, S0), in passes of PR rows.  A pass holds its rows' sums, window
+    //      addresses and leaf values in vector registers; what a finished pass leaves behind is its rows' lane masks (scalar
+    //      registers) and sums.  Eight rows in ONE pass need twice the registers of four (the 8 x 4 point of the geometry
+    //      sweep); in two passes the 64-row tile runs at the 32-row tile's register count.
+    constexpr int PR = RPW > 4 ? 4 : RPW;                  // rows per pass
+    static_assert(RPW % PR == 0, "whole passes");
     float hs[RPW];
     unsigned long long lm[RPW];          // liveness of the 64 windows of row j as a lane mask: the bookkeeping
-    int base[RPW];                       // (counts, rejection) is then scalar work, not per-lane VALU
-    const int wr = wave * RPW;
+    const int wr = wave * RPW;           // (counts, rejection) is then scalar work, not per-lane VALU
+    const int row_bytes = pitch * px_stride;
+    const int base0 = (wr * pitch + lane) * px_stride;
+    auto base_of = [&](int j) WB_INLINE_LAMBDA { return base0 + j * row_bytes; };   // byte offset of the window (row j, lane)
 #pragma unroll
     for (int j = 0; j < RPW; ++j) {
         hs[j] = 0.f;
         lm[j] = __ballot((c0 + lane < nc) && (r0 + wr + j < nr));
-        base[j] = ((wr + j) * pitch + lane) * px_stride;
     }
     const int tA = T < S0 ? T : S0;
     static_assert(S0 <= 64, "one lane per phase-A stage");
-    uint32_t entered = 0;                 // windows of this wave entering stage `lane` (phase A)
+    uint32_t entered = 0;                 // windows of this wave entering stage `lane` (phase A), over all passes
     // FULL: the cascade has at least S0 stages (the usual case) -- phase A is then straight-line code, no per-stage
     // bound checks: the scheduler is free to request a stage's record while the previous stage is being evaluated
-    auto phase_a = [&](auto full_tag) WB_INLINE_LAMBDA {
+    // J0: the pass's first row; ent: its windows entering stage `lane`
+    auto phase_a = [&](auto full_tag, auto j0_tag, uint32_t &ent) WB_INLINE_LAMBDA {
         constexpr bool FULL = decltype(full_tag)::value;
+        constexpr int J0 = decltype(j0_tag)::value;
+        int base[PR];
+#pragma unroll
+        for (int j = 0; j < PR; ++j) base[j] = base_of(J0 + j);
         if constexpr (BAKED) {
             wb_static_for<0, S0, G>([&](auto tt) {
                 constexpr int t = decltype(tt)::value;
                 if (!FULL && t >= tA) return false;
-                float p[G][RPW];
+                float p[G][PR];
                 wb_static_for<0, G, 1>([&](auto gg) {
                     constexpr int g = decltype(gg)::value;
 #pragma unroll
-                    for (int j = 0; j < RPW; ++j) p[g][j] = StageAt<D, EB, TR, t + g>::eval(tile, base[j]);
+                    for (int j = 0; j < PR; ++j) p[g][j] = StageAt<D, EB, TR, t + g>::eval(tile, base[j]);
                     return true;
                 });
                 bool more = true;
@@ -564,14 +586,14 @@ __device__ __forceinline__ void cascade_tile_body(const CascArgs &a, const int32
                     if (!FULL && t + g >= tA) return more = false;
                     int cnt = 0;
 #pragma unroll
-                    for (int j = 0; j < RPW; ++j) cnt += __popcll(lm[j]);
-                    asm volatile("v_writelane_b32 %0, %1, %2" : "+v"(entered) : "s"(cnt), "n"(t + g));
+                    for (int j = 0; j < PR; ++j) cnt += __popcll(lm[J0 + j]);
+                    asm volatile("v_writelane_b32 %0, %1, %2" : "+v"(ent) : "s"(cnt), "n"(t + g));
                     const float theta = StageAt<D, EB, TR, t + g>::theta();
                     const unsigned long long never = never_rejects<true>(theta) ? ~0ull : 0ull;
 #pragma unroll
-                    for (int j = 0; j < RPW; ++j) {
-                        hs[j] = hs[j] + p[g][j];
-                        lm[j] &= __ballot(hs[j] >= theta) | never;
+                    for (int j = 0; j < PR; ++j) {
+                        hs[J0 + j] = hs[J0 + j] + p[g][j];
+                        lm[J0 + j] &= __ballot(hs[J0 + j] >= theta) | never;
                     }
                     return true;
                 });
@@ -586,38 +608,46 @@ __device__ __forceinline__ void cascade_tile_body(const CascArgs &a, const int32
             const int32_t *sp = stages + (size_t)t * SD;
 #pragma unroll
             for (int g = 0; g < G; ++g) st[g].load(sp + g * SD);
-            float p[G][RPW];
+            float p[G][PR];
 #pragma unroll
             for (int g = 0; g < G; ++g)
 #pragma unroll
-                for (int j = 0; j < RPW; ++j) p[g][j] = st[g].template eval<EB>(tile, base[j]);
+                for (int j = 0; j < PR; ++j) p[g][j] = st[g].template eval<EB>(tile, base[j]);
 #pragma unroll
             for (int g = 0; g < G; ++g) {
                 if (!FULL && t + g >= tA) break;
                 int cnt = 0;
 #pragma unroll
-                for (int j = 0; j < RPW; ++j) cnt += __popcll(lm[j]);
+                for (int j = 0; j < PR; ++j) cnt += __popcll(lm[J0 + j]);
                 // lane t keeps stage t's count (one LDS atomic per wave after the phase): both operands are scalars, so
                 // this is ONE v_writelane instead of a move, a compare and a select
                 // (the loops are fully unrolled: the lane index is an immediate)
-                asm volatile("v_writelane_b32 %0, %1, %2" : "+v"(entered) : "s"(cnt), "n"(t + g));
+                asm volatile("v_writelane_b32 %0, %1, %2" : "+v"(ent) : "s"(cnt), "n"(t + g));
                 // theta == -inf never rejects (a NaN sum would fail `>=`): folded into the mask, not a branch,
-                // so the RPW rows stay in one basic block and share the stage's constants in registers
+                // so the PR rows stay in one basic block and share the stage's constants in registers
                 // (the bits of the scalar theta compared as an integer: a scalar compare; as a float compare it was
                 // a vector instruction per stage)
                 const unsigned long long never = never_rejects<BAKED>(st[g].theta) ? ~0ull : 0ull;
 #pragma unroll
-                for (int j = 0; j < RPW; ++j) {
-                    hs[j] = hs[j] + p[g][j];                      // (a dead window's sum is never read again)
-                    lm[j] &= __ballot(hs[j] >= st[g].theta) | never;
+                for (int j = 0; j < PR; ++j) {
+                    hs[J0 + j] = hs[J0 + j] + p[g][j];            // (a dead window's sum is never read again)
+                    lm[J0 + j] &= __ballot(hs[J0 + j] >= st[g].theta) | never;
                 }
             }
         }
     };
-    if (tA == S0)
-        phase_a(WbTag<true>{});
-    else
-        phase_a(WbTag<false>{});
+    // (a pass whose rows all lie below the level's last window row has nothing alive, and so has every pass behind it: a
+    // wave-uniform scalar branch -- what a tile cut by its level's bottom edge wastes stays a matter of PR rows)
+    wb_static_for<0, RPW, PR>([&](auto jj) {
+        if (r0 + wr + decltype(jj)::value >= nr) return false;
+        uint32_t ent = 0;
+        if (tA == S0)
+            phase_a(WbTag<true>{}, jj, ent);
+        else
+            phase_a(WbTag<false>{}, jj, ent);
+        entered += ent;
+        return true;
+    });
     if (entered) atomicAdd(&hist[lane], entered);
     if (a.dbg & 4) return;
 
@@ -625,7 +655,11 @@ __device__ __forceinline__ void cascade_tile_body(const CascArgs &a, const int32
     //      pooled: by stage 8 a wave keeps only a fraction of its windows (half-empty chunks in
     //      every wave); pooled, they fill whole chunks of 64 for a few waves and the others are
     //      done.  (A second pooling at stage 16 was measured slower.)
-    const uint32_t shard = blockIdx.x % WB_DET_SHARDS;
+    // (a tile taller than the table's unit may hold a whole shard's worth of detections: each wave's rows go to a shard
+    // of their own, nine apart, so that the shards fill as evenly as under 32-row tiles)
+    const uint32_t shard_step = TR > a.tile_unit ? 9u : 0u;
+    auto shard_of = [&](int w) WB_INLINE_LAMBDA { return (blockIdx.x + shard_step * (uint32_t)w) % WB_DET_SHARDS; };
+    const uint32_t shard = shard_of(wave);
     int my_cnt = 0;
 #pragma unroll
     for (int j = 0; j < RPW; ++j) my_cnt += __popcll(lm[j]);
@@ -663,7 +697,7 @@ __device__ __forceinline__ void cascade_tile_body(const CascArgs &a, const int32
             const unsigned long long never = never_rejects<BAKED>(st.theta) ? ~0ull : 0ull;
 #pragma unroll
             for (int j = 0; j < RPW; ++j) {
-                hs[j] = hs[j] + st.template eval<EB>(tile, base[j]);
+                hs[j] = hs[j] + st.template eval<EB>(tile, base_of(j));
                 lm[j] &= __ballot(hs[j] >= st.theta) | never;
             }
         }
@@ -685,7 +719,8 @@ __device__ __forceinline__ void cascade_tile_body(const CascArgs &a, const int32
                 recount();
             }
         }
-        pooled = t_done < T && total <= 64u * WAVES;              // same decision in every wave
+        // (a tall tile pools whatever its queue holds; the 32-row tile's threshold is the one it was measured with)
+        pooled = t_done < T && total <= (TR > 32 ? (uint32_t)QCAP : 64u * WAVES);   // same decision in every wave
     }
     int n_q = my_cnt;
     if (QPREFIX && t_done >= T) {
@@ -748,9 +783,12 @@ __device__ __forceinline__ void cascade_tile_body(const CascArgs &a, const int32
                 dyn_total = (int)total;
                 n_q = 0;
             } else {
-                queue = wgq + 64 * wave;
-                int left = (int)total - 64 * wave;
-                n_q = left < 0 ? 0 : (left > 64 ? 64 : left);
+                // (whole chunks, the same number for every wave: one each up to 64 * WAVES survivors, two each behind a
+                // tall tile's phase A)
+                const int share = 64 * (((int)total + 64 * WAVES - 1) / (64 * WAVES));
+                queue = wgq + share * wave;
+                int left = (int)total - share * wave;
+                n_q = left < 0 ? 0 : (left > share ? share : left);
             }
         }
     }
@@ -912,9 +950,10 @@ __device__ __forceinline__ void cascade_tile_body(const CascArgs &a, const int32
             }
             total2 = (uint32_t)__builtin_amdgcn_readfirstlane((int)total2);
             before2 = (uint32_t)__builtin_amdgcn_readfirstlane((int)before2);
-            const uint32_t room = (uint32_t)QCAP - 64u * WAVES;         // queue entries behind the pooled chunks
+            const uint32_t list2_at = (total + 63u) & ~63u;             // (the pooled chunks occupy the entries in front of it)
+            const uint32_t room = (uint32_t)QCAP - list2_at;            // queue entries behind the pooled chunks
             if (total2 <= ((uint32_t)a.spar_wg < room ? (uint32_t)a.spar_wg : room)) {   // same decision in every wave
-                uint2 *list2 = wgq + 64 * WAVES;                      // (the pooled chunks occupy the first 64 * WAVES entries)
+                uint2 *list2 = wgq + list2_at;
                 for (int i = lane; i < n_q; i += 64) list2[before2 + i] = queue[i];
                 __syncthreads();
                 scatter = true;
@@ -1060,6 +1099,7 @@ __device__ __forceinline__ void cascade_tile_body(const CascArgs &a, const int32
             for (int w = 0; w < 2; ++w) {
                 if (!alive[w]) continue;                              // wave-uniform
                 if (lane == 0) {
+                    const uint32_t shard = shard_of((pos[w] >> 6) / RPW);         // (the shard of the window's own rows)
                     const uint32_t slot = atomicAdd(a.det_count + shard, 1u);
                     if (slot < a.det_cap) {
                         WbDet d;

@@ -64,6 +64,9 @@ struct WbFormRecords {
     int32_t *stages_dev;    // (n_stages + G) stage records
     int32_t *stages_host;   // the byte forms: host copy the generator of the specialised kernel bakes in
     int lds_bytes;          // dynamic LDS of the tile kernel
+    int rpw;                // window rows per wave of this form's tile kernel (the model's, or twice that: choose_geometry)
+    int tile_rows;          // = rpw * waves: a multiple of the model's tile_rows, the unit of the tile table
+    int lds_rows;           // tile_rows + m - 1
     int elem_bytes;         // wb_form_elem_bytes
     void *jit;              // model-specialised kernel (wb_jit.hip, wb_model_specialize): hipFunction_t, or null; always the handle's own
     int refused;            // 1 = its specialised kernel failed the self-test, no retry
@@ -81,9 +84,9 @@ struct WbRankTable {
 
 struct WbModel {
     int n_stages, depth, m, n, C;
-    int rpw;          // window rows per wave in the cascade tile
+    int rpw;          // window rows per wave in the cascade tile: the float32 form's, and the least of any form
     int waves;        // wavefronts per workgroup
-    int tile_rows;    // = rpw * waves
+    int tile_rows;    // = rpw * waves: the unit of WbTile.ty (a form's own tile is this tall or a multiple: WbFormRecords)
     int lds_rows;     // tile_rows + m - 1
     int lds_pitch;    // WB_CASC_TC + n - 1 pixels + 1 pad column
     int lds_stages;   // stage records mirrored in LDS (n_stages if the table is <= 16 KiB, else 0)
@@ -111,6 +114,10 @@ struct WbModel {
 inline const WbRankTable &wb_rank_table(const WbModel *model, int form) { return model->ranks[form - WB_FORM_RANK8]; }
 
 // ---- the tile kernel's host side (wb_cascade.hip), as wb_model_create needs it ----
+#ifndef WB_CASC_BYTE_RPW
+#define WB_CASC_BYTE_RPW 8      // rows per wave of the one-byte forms' tile (choose_geometry): 64 x 64 windows on eight waves
+#endif
+bool wb_cascade_has_kernel(int depth, int rpw, int waves);   // an instance of the tile kernel exists for this shape
 int wb_cascade_prepare(int depth, int rpw, int waves);  // the instances' dynamic-LDS limit raised; WB_ERR_UNSUPPORTED: no kernel for this shape
 int wb_cascade_group(int depth);                        // stages evaluated per group
 int wb_cascade_lds_bytes(int eb, int C, int rows, int pitch, int TR, int waves, int T, int lds_stages,

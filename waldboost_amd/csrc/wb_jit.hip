@@ -80,6 +80,7 @@ std::string make_source(const int32_t *words, size_t n_words, int T, int D, int 
     s += "\n#define WB_JIT_SEGMENTS(X)" + segment_list(T) + "\n";
     s += "#define WB_JIT_LDS_STAGES " + std::to_string(lds_stages < 0 ? T : lds_stages) + "\n";
     // (the occupancy floor can be overridden per build through WB_JIT_DEFS: diagnostics)
+    s += "#define WB_JIT_RPW " + std::to_string(rpw) + "\n";
     s += "#define WB_JIT_WAVES " + std::to_string(waves) + "\n#ifndef WB_JIT_OCC_MIN\n#define WB_JIT_OCC_MIN " + std::to_string(occ_min) +
          "\n#endif\n#ifndef WB_JIT_ATTR_EXTRA\n#define WB_JIT_ATTR_EXTRA\n#endif\n";
     s += "#define WB_JIT_T " + std::to_string(T) + "\n#define WB_JIT_C " + std::to_string(C) + "\n#define WB_JIT_ROWS " +
@@ -344,6 +345,11 @@ extern "C" int wb_jit_compile_check(int depth, int n_stages, const char *arch, i
 }
 
 extern "C" int wb_jit_compile_check2(int depth, int n_stages, int elem_bytes, const char *arch, int64_t *code_bytes) {
+    return wb_jit_compile_check3(depth, n_stages, elem_bytes, 4, arch, code_bytes);
+}
+
+extern "C" int wb_jit_compile_check3(int depth, int n_stages, int elem_bytes, int rpw, const char *arch, int64_t *code_bytes) {
+    WB_REQUIRE(wb_cascade_has_kernel(depth, rpw, 8), "wb_jit_compile_check: no tile kernel of %d rows per wave", rpw);
     WB_REQUIRE(depth >= 1 && depth <= WB_CASC_MAX_DEPTH && n_stages >= 1 && n_stages <= 4096 && arch && code_bytes &&
                (elem_bytes == 1 || elem_bytes == 2), "wb_jit_compile_check: bad argument");
     const int SD = WB_STAGE_DWORDS(depth), NI = WB_STAGE_NI(depth), NL = WB_STAGE_NL(depth), G = wb_cascade_group(depth);
@@ -368,7 +374,7 @@ extern "C" int wb_jit_compile_check2(int depth, int n_stages, int elem_bytes, co
     const int lds_stages = n_stages * SD * 4 <= 16 * 1024 ? n_stages : 0;
     std::vector<char> code;
     std::string log;
-    const int rc = build_checked(make_source(words.data(), words.size(), n_stages, depth, 4, 8, 4, 4 * 8 + 11, WB_CASC_TC + 12, elem_bytes, lds_stages),
+    const int rc = build_checked(make_source(words.data(), words.size(), n_stages, depth, rpw, 8, 4, rpw * 8 + 11, WB_CASC_TC + 12, elem_bytes, lds_stages),
                                  arch, code, log);
     if (rc != WB_OK) {
         wb_set_error("wb_jit_compile_check: %.400s", log.c_str());
@@ -389,7 +395,8 @@ extern "C" int wb_jit_compile_check2(int depth, int n_stages, int elem_bytes, co
 int wb_jit_selftest(WbModel *model, int chn_dtype, WbFormRecords *rec) {
     static const int passes = getenv("WB_JIT_SELFTEST") ? atoi(getenv("WB_JIT_SELFTEST")) : 6;
     if (passes <= 0) return WB_OK;
-    const int eb = rec->elem_bytes, C = model->C, m = model->m, n = model->n, T = model->n_stages, TR = model->tile_rows;
+    // (the levels in units of the form's own tile; the table in the model's units, whole, as any caller may hand it over)
+    const int eb = rec->elem_bytes, C = model->C, m = model->m, n = model->n, T = model->n_stages, TR = rec->tile_rows, unit = model->tile_rows;
     struct Lv { int gh, gw; } lv[2] = {{2 * TR + TR / 2 + 1, 64 + 37}, {TR / 2 - 3 > 0 ? TR / 2 - 3 : 1, 24}};
     std::vector<WbLevel> levels(2);
     std::vector<WbTile> tiles;
@@ -401,7 +408,7 @@ int wb_jit_selftest(WbModel *model, int chn_dtype, WbFormRecords *rec) {
         levels[l].chn_off = elems;
         elems += (int64_t)levels[l].u * levels[l].v * C;
         windows += (int64_t)lv[l].gh * lv[l].gw;
-        for (int ty = 0; ty * TR < lv[l].gh; ++ty)
+        for (int ty = 0; ty * unit < lv[l].gh; ++ty)
             for (int tx = 0; tx * 64 < lv[l].gw; ++tx) tiles.push_back(WbTile{l, (uint16_t)ty, (uint16_t)tx});
     }
     // bytes: four kinds of 16 x 16 regions (the whole range, dark, middle, bright), LCG noise inside

@@ -47,10 +47,15 @@ void model_free(WbModel *model) {
 
 // The cascade tile of a model: the largest (rpw * waves) x 64 windows whose float32 LDS footprint leaves two workgroups per
 // CU; WB_CASC_RPW / WB_CASC_WAVES override the default for tuning.  Sets the geometry fields and every form's LDS bytes.
+// The tile is chosen per form: a one-byte form (uint8 channels, 8-bit ranks) holds a quarter of the float32 tile's bytes
+// per row and takes rows per wave of its own -- WB_CASC_BYTE_RPW, or WB_CASC_RPW as asked for (not halved by the float32
+// budget) -- when the taller tile is a whole multiple of the model's, has a kernel, and leaves four workgroups per CU
+// (40 KB of LDS); else the model's.  The float32 and the two-byte form keep the model's (at 64 rows: 91 KB, and 46 KB of tile).
 void choose_geometry(WbModel *M) {
-    const int budget = 80 * 1024, D = M->depth;
-    int rpw = 4, waves = 8;
-    if (const char *e = getenv("WB_CASC_RPW")) rpw = atoi(e);
+    const int budget = 80 * 1024, byte_budget = 40 * 1024, D = M->depth;
+    int rpw = 4, waves = 8, byte_rpw = WB_CASC_BYTE_RPW;
+    if (const char *e = getenv("WB_CASC_RPW")) byte_rpw = rpw = atoi(e);
+    if (const char *e = getenv("WB_CASC_BYTE_RPW")) byte_rpw = atoi(e);
     if (const char *e = getenv("WB_CASC_WAVES")) waves = atoi(e);
     M->lds_pitch = WB_CASC_TC + M->n;   // tile row (64 + n - 1 pixels) + one pad column (spare slot of the tile load)
     M->lds_stages = (M->n_stages * WB_STAGE_DWORDS(D) * 4 <= 16 * 1024) ? M->n_stages : 0;
@@ -66,6 +71,20 @@ void choose_geometry(WbModel *M) {
                                                         M->n_stages, M->lds_stages, D);
         }
         if (M->form[WB_FORM_F32].lds_bytes <= budget || rpw <= 1) break;
+    }
+    for (int f = 0; f < WB_FORM_COUNT; ++f) {
+        WbFormRecords &rec = M->form[f];
+        rec.rpw = M->rpw;
+        rec.tile_rows = M->tile_rows;
+        rec.lds_rows = M->lds_rows;
+        if (rec.elem_bytes != 1 || byte_rpw <= M->rpw || byte_rpw % M->rpw != 0 || !wb_cascade_has_kernel(D, byte_rpw, waves)) continue;
+        const int tr = byte_rpw * waves, rows = tr + M->m - 1;
+        const int lds = wb_cascade_lds_bytes(1, M->C, rows, M->lds_pitch, tr, waves, M->n_stages, M->lds_stages, D);
+        if (lds > byte_budget) continue;
+        rec.rpw = byte_rpw;
+        rec.tile_rows = tr;
+        rec.lds_rows = rows;
+        rec.lds_bytes = lds;
     }
 }
 
@@ -229,7 +248,8 @@ extern "C" int wb_model_create(int n_stages, const int32_t *node_off, const uint
         model_free(M);
         return WB_ERR_HIP;
     }
-    rc = wb_cascade_prepare(D, M->rpw, M->waves);
+    for (int f = 0; f < WB_FORM_COUNT && rc == WB_OK; ++f)
+        if (f == WB_FORM_F32 || M->form[f].rpw != M->rpw) rc = wb_cascade_prepare(D, M->form[f].rpw, M->waves);
     if (rc != WB_OK) {
         model_free(M);
         return rc;
@@ -265,6 +285,39 @@ extern "C" int wb_model_info(const WbModel *model, WbModelInfo *info) {
     return WB_OK;
 }
 
+// Window rows of the tile that wb_cascade_launch's kernel for `chn_dtype` covers per workgroup: wb_model_info's tile_rows
+// or a multiple of it (choose_geometry).  A tile table for that form alone needs only the entries that start such a tile.
+extern "C" int wb_model_form_rows(const WbModel *model, int chn_dtype, int *tile_rows, int *lds_bytes) {
+    WB_REQUIRE(model && tile_rows, "wb_model_form_rows: null pointer");
+    WB_REQUIRE(chn_dtype == WB_DTYPE_F32 || chn_dtype == WB_DTYPE_U8 || chn_dtype == WB_DTYPE_RANK8 || chn_dtype == WB_DTYPE_RANK16,
+               "wb_model_form_rows: channel dtype %d (float32, uint8 or ranks)", chn_dtype);
+    const WbFormRecords &rec = model->form[wb_tile_form(chn_dtype)];
+    *tile_rows = model->generic ? model->tile_rows : rec.tile_rows;
+    if (lds_bytes) *lds_bytes = model->generic ? 0 : rec.lds_bytes;
+    return WB_OK;
+}
+
+// The same answer without a handle (and without a GPU): the tile wb_model_create would choose for a cascade of n_stages
+// trees of `depth` on (m, n, C) windows, for channels of chn_dtype.  out = {rows per wave, waves, tile_rows, lds_bytes}.
+extern "C" int wb_model_geometry(int n_stages, int depth, int m, int n, int C, int chn_dtype, int32_t *out) {
+    WB_REQUIRE(out && n_stages >= 0 && depth >= 1 && depth <= WB_CASC_MAX_DEPTH && m >= 1 && n >= 1 && C >= 1, "wb_model_geometry: bad argument");
+    WB_REQUIRE(chn_dtype == WB_DTYPE_F32 || chn_dtype == WB_DTYPE_U8 || chn_dtype == WB_DTYPE_RANK8 || chn_dtype == WB_DTYPE_RANK16,
+               "wb_model_geometry: channel dtype %d (float32, uint8 or ranks)", chn_dtype);
+    WbModel M = {};
+    M.n_stages = n_stages;
+    M.depth = depth;
+    M.m = m;
+    M.n = n;
+    M.C = C;
+    choose_geometry(&M);
+    const WbFormRecords &rec = M.form[wb_tile_form(chn_dtype)];
+    out[0] = rec.rpw;
+    out[1] = M.waves;
+    out[2] = rec.tile_rows;
+    out[3] = rec.lds_bytes;
+    return WB_OK;
+}
+
 // The loaded specialised kernels of a model off (0) or on (1) for wb_cascade_launch: off, the generic kernel scans -- what a
 // caller needs to cross-check a specialised kernel on its own data (engine.py: _live_check), or to retire one it distrusts.
 extern "C" int wb_model_use_specialized(WbModel *model, int enable) {
@@ -297,8 +350,8 @@ extern "C" int wb_model_specialize(WbModel *model, int chn_dtype) {
         wb_set_error("wb_model_specialize: this model's specialised kernel failed its self-test earlier; it stays on the generic kernel");
         return WB_ERR_UNSUPPORTED;
     }
-    int rc = wb_jit_get(rec.stages_host, model->stage_words, model->n_stages, model->depth, model->rpw, model->waves, model->C,
-                        model->lds_rows, model->lds_pitch, rec.elem_bytes, model->lds_stages, &rec.jit);
+    int rc = wb_jit_get(rec.stages_host, model->stage_words, model->n_stages, model->depth, rec.rpw, model->waves, model->C,
+                        rec.lds_rows, model->lds_pitch, rec.elem_bytes, model->lds_stages, &rec.jit);
     if (rc == WB_OK) {
         rc = wb_jit_selftest(model, chn_dtype, &rec);
         if (rc == WB_OK) return WB_OK;

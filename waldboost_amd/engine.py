@@ -168,6 +168,7 @@ class DeviceCascade:
         self._jit_failed = set()
         self._live_left = {}             # live checks a freshly specialised kernel still owes, per channel dtype code
         self._spec_off = False           # use_specialized(False) is in force
+        self._form_rows = {}             # form_rows, per channel dtype code
         info = nat.WbModelInfo()
         nat.check(self._lib.wb_model_info(self.handle, C.byref(info)), "wb_model_info")
         self.n_stages, self.depth = info.n_stages, info.depth
@@ -189,6 +190,16 @@ class DeviceCascade:
         self.group = group               # keeps the handle's owner alive; the group does NOT refer back to its views
         self._setup(nat.load(), handle, False, group.token)      # (a token, not the group: see __init__)
         return self
+
+    def form_rows(self, chn_dtype):
+        """Window rows of the tile the kernel for channels of chn_dtype scans per workgroup (wb_model_form_rows): tile_rows,
+        or a multiple of it on the one-byte forms."""
+        rows = self._form_rows.get(chn_dtype)
+        if rows is None:
+            r = C.c_int()
+            nat.check(self._lib.wb_model_form_rows(self.handle, chn_dtype, C.byref(r), None), "wb_model_form_rows")
+            rows = self._form_rows[chn_dtype] = r.value
+        return rows
 
     def specialized(self):
         """Which byte tiles have a model-specialised kernel loaded: subset of {WB_DTYPE_U8, WB_DTYPE_RANK8, WB_DTYPE_RANK16}."""
@@ -405,8 +416,9 @@ class FinalBuffers:
 class ScanState:
     """What an engine keeps per cascade it scans (PyramidEngine._casc_state).  None: not there (yet, or any more)."""
     dm: DeviceCascade                # (held: the states are keyed by id(dm))
-    tiles: object                    # the cascade's tile list on the device (None: no tile)
+    tiles: object                    # the cascade's tile list on the device (None: no tile): every unit of tile_rows
     n_tiles: int
+    tall: dict                       # rows -> (tile list, count) of a form whose tile is taller (DeviceCascade.form_rows)
     alive: object                    # alive[B, L, T]: a view into the control block
     ranks: bool = False              # the form of the last scan (a re-scan after a buffer overflow repeats it)
     graph: object = None             # detect_enqueue's captured sequence        } dropped by
@@ -787,10 +799,16 @@ class PyramidEngine:
         stt = self._casc.get(key)
         if stt is None:
             tiles = self.plan.casc_tiles(dm.m, dm.n, dm.tile_rows, dm.tile_cols)
+            up = lambda t: torch.from_numpy(t.view(np.uint8).copy()).to(self.dev)
+            tall = {}
+            for dt in {self.spec.wb_dtype, dm.rank_dtype} - {None}:
+                rows = dm.form_rows(dt)
+                if tiles.size and rows != dm.tile_rows and rows not in tall:
+                    t = self.plan.casc_tiles(dm.m, dm.n, rows, dm.tile_cols, ty_unit=dm.tile_rows)
+                    tall[rows] = (up(t), int(t.size))
             T1 = max(dm.n_stages, 1)
             alive = self._alive_view(T1)                # (may re-allocate the control block and drop other states)
-            stt = ScanState(dm, torch.from_numpy(tiles.view(np.uint8).copy()).to(self.dev) if tiles.size else None,
-                            int(tiles.size), alive)
+            stt = ScanState(dm, up(tiles) if tiles.size else None, int(tiles.size), tall, alive)
             if len(self._casc) >= 4:         # a few cascades resident per engine (waldboost.detect scans several models)
                 self._casc.pop(next(iter(self._casc)))
             self._casc[key] = stt
@@ -805,13 +823,15 @@ class PyramidEngine:
             return stt
         if ranks and self.rank_owner is not dm.rank_key:
             raise RuntimeError("the rank buffer does not hold this cascade's ranks (launch_channels(rank_dm=...) first)")
-        dm.note_scan(dm.rank_dtype if ranks else self.spec.wb_dtype)
+        chn_dtype = dm.rank_dtype if ranks else self.spec.wb_dtype
+        dm.note_scan(chn_dtype)
         zk = self.ctrl[: self._mm_words] if zero_keys else None
+        tiles, n_tiles = stt.tall.get(dm.form_rows(chn_dtype), (stt.tiles, stt.n_tiles))
         nat.check(self.lib.wb_cascade_launch_z(nat.stream_ptr(), dm.handle, nat.ptr(self.rank if ranks else self.chn),
-                                               dm.rank_dtype if ranks else self.spec.wb_dtype,
+                                               chn_dtype,
                                                self.chn_stride,
                                                self.batch, nat.ptr(self.levels), self.plan.n_levels,
-                                               nat.ptr(stt.tiles), stt.n_tiles,
+                                               nat.ptr(tiles), n_tiles,
                                                nat.ptr(self.detb.recs), nat.ptr(self.detb.counts), self.detb.cap,
                                                nat.ptr(stt.alive if stats else None), nat.ptr(zk),
                                                0 if zk is None else zk.numel()),

@@ -243,7 +243,10 @@ class PyramidPlan:
         valid, exactly like reference model.py:243."""
         return [(max(lv["u"] - m, 0), max(lv["v"] - n, 0)) for lv in self.levels]
 
-    def casc_tiles(self, m, n, tile_rows, tile_cols):
+    def casc_tiles(self, m, n, tile_rows, tile_cols, ty_unit=None):
+        """The cascade's tile table for tiles of tile_rows x tile_cols windows.  ty_unit: the rows one step of `ty` stands
+        for (wb_model_info's tile_rows) when the tile is a multiple of it -- a form with taller tiles of its own
+        (wb_model_form_rows): the table then holds the entries that start a tile, in the model's units."""
         grid = self.window_grid(m, n)
         # the cascade's short workgroups: tiles cut by an edge of their level
         nr = np.array([g[0] for g in grid], np.int64)
@@ -254,7 +257,11 @@ class PyramidPlan:
             cols = np.minimum(tile_cols, nc[nat["level"]] - nat["tx"].astype(np.int64) * tile_cols)
             cost = rows * cols / float(tile_rows * tile_cols)
             return cost < 1.0, cost
-        return self._tiles(grid, tile_rows, tile_cols, cheap=cheap, short_last=self._short_last)
+        tiles = self._tiles(grid, tile_rows, tile_cols, cheap=cheap, short_last=self._short_last)
+        if ty_unit is not None and ty_unit != tile_rows:
+            assert tile_rows % ty_unit == 0
+            tiles["ty"] *= tile_rows // ty_unit
+        return tiles
 
     def n_loc(self, m, n):
         return int(sum(r * c for r, c in self.window_grid(m, n)))
