@@ -51,6 +51,9 @@
  *   reference waldboost/samples.py:46-216 (label_boxes, select_candidates, get_samples_from_image: hard-negative mining),
  *        for a scanned batch and with a stated selection rule in place of np.random.choice
  *        -> wb_mine_select_launch, wb_mine_gather_launch
+ *   no reference counterpart (its thetas are fitted during training only, training.py fit_rejection_threshold): the
+ *        running score of a sample after every stage and the pruning minimum, for threshold calibration
+ *        -> wb_samples_trace_launch, wb_calib_min_launch
  */
 #ifndef WALDBOOST_HIP_H
 #define WALDBOOST_HIP_H
@@ -452,6 +455,33 @@ int wb_gather_samples_launch(void *stream, const void *X, int x_dtype, int u, in
  * sample is alive, -inf once a stage rejected it; mask[i] (uint8) = 1 if it passed every stage. */
 int wb_samples_predict_launch(void *stream, const WbModel *model, const void *X, int x_dtype,
                               int64_t n_samples, float *H, uint8_t *mask);
+
+/* Threshold calibration (direct backward pruning, Zhang & Viola 2007; the reference has no counterpart: its thetas come
+ * from training.py fit_rejection_threshold while a stage is trained).  New symbols of ABI 8 (the version number did not
+ * change: nothing that existed did).
+ *
+ * The stage-score trace of the cascade on per-sample arrays X[n_samples][m][n][C] (as wb_samples_predict_launch):
+ *   trace  dev float32 [T][n_samples], STAGE-major (a wave's 64 samples store 256 contiguous bytes per stage), or NULL:
+ *          trace[t][i] = running score of sample i after stage t: h = h + pred in fp32, in stage order, from 0.f
+ *   final  dev float32 [n_samples] or NULL: the last row of the trace
+ *   alive  dev uint32 [T + 1] or NULL: alive[t] = samples entering stage t (alive[0] = n_samples), alive[T] = samples
+ *          that passed every stage; set inside the call, whatever it held
+ *   reject 0: the thetas are ignored, every sample walks all T stages;  1: they apply as in the cascade (`h >= theta`,
+ *          -inf never rejects): from the rejecting stage on a sample's trace entries and its final are -inf, so final is
+ *          wb_samples_predict_launch's H.
+ * Any output may be NULL, not all three (WB_ERR_INVALID).  n_samples == 0 succeeds without a launch. */
+int wb_samples_trace_launch(void *stream, const WbModel *model, const void *X, int x_dtype, int64_t n_samples,
+                            int reject, float *trace, float *final, uint32_t *alive);
+
+/* The pruning step on the same samples: a sample is RETAINED when its unrejected final score is >= floor;
+ *   stage_min   dev float32 [T]: the minimum over the retained samples of the unrejected running score after stage t
+ *               (+inf everywhere when no sample is retained)
+ *   n_retained  dev uint32 [1]: the number of retained samples
+ * The walk is computed again (no N x T trace is read); the minimum is taken on order-preserving integer keys of the
+ * floats, so it is exact and does not depend on order or run.  Both outputs are initialised inside the call (two memsets
+ * on the stream).  n_samples == 0: +inf and 0. */
+int wb_calib_min_launch(void *stream, const WbModel *model, const void *X, int x_dtype, int64_t n_samples,
+                        float floor, float *stage_min, uint32_t *n_retained);
 
 /* One tree on per-sample arrays X[n_samples][m][n][C]: node[i] = index of the leaf reached (reference
  * training.py:73-83 DTree.apply; DTree.predict is prediction[node]).  Tree arrays dev, as for

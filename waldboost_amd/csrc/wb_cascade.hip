@@ -11,7 +11,9 @@
 //   * cascade_generic_kernel: the node-walk fallback for models without a tile kernel;
 //   * training-time callers of the same walks: tree_eval_kernel (wb_tree_eval_launch), samples_predict_kernel
 //     (wb_samples_predict_launch), tree_apply_kernel (wb_tree_apply_launch) and gather_samples_kernel
-//     (wb_gather_samples_launch).
+//     (wb_gather_samples_launch);
+//   * threshold calibration on samples: samples_trace_kernel (wb_samples_trace_launch: the running score after every
+//     stage, per-stage survival) and calib_min_kernel (wb_calib_min_launch: per-stage minimum over the retained samples).
 // The two walks -- a stage of the model's flat arrays, one tree's uint8 / int8 arrays -- stand here once each (flat_stage,
 // tree_leaf).  What reads the detection records the cascade leaves is in wb_det.hip.
 //
@@ -229,6 +231,131 @@ __global__ __launch_bounds__(256) void samples_predict_kernel(FlatModel a, const
         alive = flat_stage(a, t, h, [&](int fr, int fc, int ch) { return chn_at(X, x_u8, base + ((fr * a.n + fc) * a.C + ch)); });
     H[i] = alive ? h : -INFINITY;
     mask[i] = alive ? 1 : 0;
+}
+
+// -------------------------------------------------------------------------------------------
+// Threshold calibration (direct backward pruning): the running score of a sample after EVERY stage, and the per-stage
+// minimum of it over the samples a final-score floor retains.  One thread per sample, 256 samples per workgroup, the same
+// walk (flat_stage) as samples_predict_kernel; a wave is at one stage at a time, so the counts are ballots and a stage's
+// 64 running scores leave as one 256-byte store.  Per-stage results of a workgroup meet in an LDS table of WB_CALIB_CHUNK
+// stages at a time (any number of stages) and reach memory with one atomic per (workgroup, stage).
+#define WB_CALIB_CHUNK 1024
+
+// pixel (row, col, channel) of sample i of X[n_samples][m][n][C]
+struct SampleFetch {
+    const void *X;
+    int x_u8, n, C;
+    int64_t base;
+    __device__ float operator()(int fr, int fc, int ch) const { return chn_at(X, x_u8, base + ((fr * n + fc) * C + ch)); }
+};
+
+struct TraceArgs {
+    FlatModel model;
+    const void *X;
+    int x_u8, reject;
+    int64_t n_samples;
+    float *trace, *fin;      // [T][n_samples], [n_samples]
+    uint32_t *alive;         // [T + 1], zeroed ahead of the launch
+};
+
+__global__ __launch_bounds__(256) void samples_trace_kernel(TraceArgs a) {
+    __shared__ uint32_t hist[WB_CALIB_CHUNK];
+    const int T = a.model.T, tid = threadIdx.x, lane = tid & 63;
+    const int64_t i = (int64_t)blockIdx.x * 256 + tid, N = a.n_samples;
+    const bool valid = i < N;                                  // (no early return: every thread meets the barriers)
+    const SampleFetch fetch = {a.X, a.x_u8, a.model.n, a.model.C, (valid ? i : 0) * (int64_t)a.model.m * a.model.n * a.model.C};
+    float h = 0.f;
+    bool alive = valid;
+    // slot t of the counts: samples entering stage t; slot T: those that passed every stage
+    for (int t0 = 0; t0 <= T; t0 += WB_CALIB_CHUNK) {
+        const int t1 = t0 + WB_CALIB_CHUNK < T + 1 ? t0 + WB_CALIB_CHUNK : T + 1;
+        if (a.alive) {
+            for (int k = tid; k < t1 - t0; k += 256) hist[k] = 0u;
+            __syncthreads();
+        }
+        for (int t = t0; t < t1; ++t) {
+            if (a.alive) {
+                const int cnt = __popcll(__ballot(alive));
+                if (lane == 0 && cnt) atomicAdd(&hist[t - t0], (uint32_t)cnt);
+            }
+            if (t == T) break;
+            if (alive) {
+                const bool pass = flat_stage(a.model, t, h, fetch);
+                alive = a.reject ? pass : true;
+            }
+            if (a.trace && valid) a.trace[(int64_t)t * N + i] = alive ? h : -INFINITY;
+        }
+        if (a.alive) {
+            __syncthreads();
+            for (int k = tid; k < t1 - t0; k += 256)          // (the thread that zeroes slot k for the next chunk)
+                if (hist[k]) atomicAdd(a.alive + t0 + k, hist[k]);
+        }
+    }
+    if (a.fin && valid) a.fin[i] = alive ? h : -INFINITY;
+}
+
+struct CalibArgs {
+    FlatModel model;
+    const void *X;
+    int x_u8;
+    float floor;
+    int64_t n_samples;
+    uint32_t *keys;          // [T] order-preserving keys (wb_f32_key) of the minima, all ones ahead of the launch
+    uint32_t *n_retained;    // [1], zeroed ahead of the launch
+};
+
+// the smallest key of a wave, in every lane
+__device__ inline uint32_t wave_min_u32(uint32_t k) {
+    for (int off = 32; off >= 1; off >>= 1) {
+        const uint32_t o = (uint32_t)__shfl_xor((int)k, off);
+        k = o < k ? o : k;
+    }
+    return k;
+}
+
+__global__ __launch_bounds__(256) void calib_min_kernel(CalibArgs a) {
+    __shared__ uint32_t slot[WB_CALIB_CHUNK];
+    __shared__ uint32_t kept;
+    const int T = a.model.T, tid = threadIdx.x, lane = tid & 63;
+    const int64_t i = (int64_t)blockIdx.x * 256 + tid;
+    const bool valid = i < a.n_samples;
+    const SampleFetch fetch = {a.X, a.x_u8, a.model.n, a.model.C, (valid ? i : 0) * (int64_t)a.model.m * a.model.n * a.model.C};
+    if (tid == 0) kept = 0u;
+    // the unrejected final score decides who is retained ...
+    float h = 0.f;
+    if (valid)
+        for (int t = 0; t < T; ++t) flat_stage(a.model, t, h, fetch);
+    const bool retained = valid && h >= a.floor;
+    const unsigned long long wave_kept = __ballot(retained);
+    __syncthreads();
+    if (lane == 0 && wave_kept) atomicAdd(&kept, (uint32_t)__popcll(wave_kept));
+    // ... and the same walk again gives the retained samples' running scores, stage by stage (no trace is stored): the key
+    // in a register, the wave's smallest, the workgroup's in LDS, one atomic min per stage
+    h = 0.f;
+    for (int t0 = 0; t0 < T; t0 += WB_CALIB_CHUNK) {
+        const int t1 = t0 + WB_CALIB_CHUNK < T ? t0 + WB_CALIB_CHUNK : T;
+        for (int k = tid; k < t1 - t0; k += 256) slot[k] = 0xFFFFFFFFu;
+        __syncthreads();
+        if (wave_kept)
+            for (int t = t0; t < t1; ++t) {
+                if (retained) flat_stage(a.model, t, h, fetch);
+                const uint32_t k = wave_min_u32(retained ? wb_f32_key(h) : 0xFFFFFFFFu);
+                if (lane == 0) atomicMin(&slot[t - t0], k);
+            }
+        __syncthreads();
+        for (int k = tid; k < t1 - t0; k += 256)              // (the thread that resets slot k for the next chunk)
+            if (slot[k] != 0xFFFFFFFFu) atomicMin(a.keys + t0 + k, slot[k]);
+    }
+    __syncthreads();
+    if (tid == 0 && kept) atomicAdd(a.n_retained, kept);
+}
+
+// the keys back to floats, in place; a stage no sample reached keeps +inf
+__global__ __launch_bounds__(256) void calib_keys_kernel(uint32_t *keys, int T) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= T) return;
+    const uint32_t k = keys[t];
+    reinterpret_cast<float *>(keys)[t] = k == 0xFFFFFFFFu ? INFINITY : wb_key_f32(k);
 }
 
 // DTree.apply on samples
@@ -455,6 +582,49 @@ extern "C" int wb_samples_predict_launch(void *stream, const WbModel *model, con
     hipLaunchKernelGGL(samples_predict_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, flat_model(model), X,
                        (int)(x_dtype == WB_DTYPE_U8), n_samples, H, mask);
     WB_HIP_CHECK(hipGetLastError());
+    return WB_OK;
+}
+
+extern "C" int wb_samples_trace_launch(void *stream, const WbModel *model, const void *X, int x_dtype, int64_t n_samples,
+                                       int reject, float *trace, float *final, uint32_t *alive) {
+    WB_REQUIRE(n_samples >= 0, "wb_samples_trace_launch: negative count");
+    if (n_samples == 0) return WB_OK;
+    WB_REQUIRE(model && X, "wb_samples_trace_launch: null pointer");
+    WB_REQUIRE(trace || final || alive, "wb_samples_trace_launch: no output asked for");
+    WB_REQUIRE(x_dtype == WB_DTYPE_F32 || x_dtype == WB_DTYPE_U8, "wb_samples_trace_launch: sample dtype %d (float32 or uint8)", x_dtype);
+    WB_REQUIRE(reject == 0 || reject == 1, "wb_samples_trace_launch: reject %d (0 or 1)", reject);
+    const int64_t blocks = (n_samples + 255) / 256;
+    WB_REQUIRE(blocks <= 0x7fffffff, "wb_samples_trace_launch: too many samples for one launch");
+    hipStream_t st = (hipStream_t)stream;
+    if (alive) WB_HIP_CHECK(hipMemsetAsync(alive, 0, ((size_t)model->n_stages + 1) * 4, st));
+    const TraceArgs a = {flat_model(model), X, (int)(x_dtype == WB_DTYPE_U8), reject, n_samples, trace, final, alive};
+    hipLaunchKernelGGL(samples_trace_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a);
+    WB_HIP_CHECK(hipGetLastError());
+    return WB_OK;
+}
+
+extern "C" int wb_calib_min_launch(void *stream, const WbModel *model, const void *X, int x_dtype, int64_t n_samples,
+                                   float floor, float *stage_min, uint32_t *n_retained) {
+    WB_REQUIRE(n_samples >= 0, "wb_calib_min_launch: negative count");
+    WB_REQUIRE(model && stage_min && n_retained && (X || n_samples == 0), "wb_calib_min_launch: null pointer");
+    WB_REQUIRE(x_dtype == WB_DTYPE_F32 || x_dtype == WB_DTYPE_U8, "wb_calib_min_launch: sample dtype %d (float32 or uint8)", x_dtype);
+    const int64_t blocks = (n_samples + 255) / 256;
+    WB_REQUIRE(blocks <= 0x7fffffff, "wb_calib_min_launch: too many samples for one launch");
+    hipStream_t st = (hipStream_t)stream;
+    const int T = model->n_stages;
+    uint32_t *keys = reinterpret_cast<uint32_t *>(stage_min);
+    // whatever the outputs held: all-ones keys (above every score's) and a zero count, behind earlier work on the stream
+    if (T) WB_HIP_CHECK(hipMemsetAsync(keys, 0xFF, (size_t)T * 4, st));
+    WB_HIP_CHECK(hipMemsetAsync(n_retained, 0, 4, st));
+    if (n_samples) {
+        const CalibArgs a = {flat_model(model), X, (int)(x_dtype == WB_DTYPE_U8), floor, n_samples, keys, n_retained};
+        hipLaunchKernelGGL(calib_min_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a);
+        WB_HIP_CHECK(hipGetLastError());
+    }
+    if (T) {
+        hipLaunchKernelGGL(calib_keys_kernel, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, st, keys, T);
+        WB_HIP_CHECK(hipGetLastError());
+    }
     return WB_OK;
 }
 

@@ -533,6 +533,17 @@ class Model:
                                                        nat.ptr(mask)), "wb_samples_predict_launch")
         return H.cpu().numpy(), mask.cpu().numpy().astype(bool)
 
+    def stage_scores(self, X, reject=False, device=False):
+        """The running score of every sample of X[N, m, n, C] after every stage -> (N, T) float32: entry [i, t] is
+        ``h = h + pred`` accumulated in fp32 over stages 0 .. t, from 0 (wb_samples_trace_launch; the result is the
+        transpose view of the stage-major device trace).  X: an ndarray or device tensor of any dtype
+        compare.channel_tensor takes.  reject=False: the thetas are ignored; True: they apply as in predict -- from the
+        rejecting stage on a sample's entries are -inf, so ``stage_scores(X, reject=True)[:, -1]`` is ``predict(X)[0]``
+        bit for bit.  device=True: a device tensor.  ValueError when N * T >= 2**31 or X has another sample shape.
+        What calibration.calibrate prunes the thetas with."""
+        from . import calibration
+        return calibration.stage_scores(self, X, reject, device)
+
     # ---- wire format (reference model.py:285-344)
     def as_proto(self, proto):
         proto.Clear()
