@@ -27,7 +27,7 @@ __global__ __launch_bounds__(256) void resize_level_kernel(const T *src, int src
         if (mn != mn || mx != mx) v = __builtin_nan("");
         else v = v < mn ? mn : (v > mx ? mx : v);
         switch (cast_mode) {
-            case WB_CAST_TRUNC: v = trunc(v); break;
+            case WB_CAST_TRUNC: v = trunc(v) + 0.0; break;      // (+ 0.0: trunc(-0.5) is -0.0, the integer types have one zero)
             case WB_CAST_BOOL: v = v != 0.0 ? 1.0 : 0.0; break;
             case WB_CAST_F16: v = wb_round_f16(v); break;
         }

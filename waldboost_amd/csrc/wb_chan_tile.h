@@ -175,7 +175,7 @@ template <> struct Src<double> {
         if (mn != mn || mx != mx) return __builtin_nanf("");     // (np.clip with a NaN bound: see Src<float>::finish)
         t = t < mn ? mn : (t > mx ? mx : t);
         switch (src_int) {
-            case WB_CAST_TRUNC: t = trunc(t); break;
+            case WB_CAST_TRUNC: t = trunc(t) + 0.0; break;      // (+ 0.0: trunc(-0.5) is -0.0, the integer types have one zero)
             case WB_CAST_BOOL: t = t != 0.0 ? 1.0 : 0.0; break;
             case WB_CAST_F16: t = wb_round_f16(t); break;
         }
