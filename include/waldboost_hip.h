@@ -615,6 +615,55 @@ int wb_mine_select_launch(void *stream, const WbDet *det, int64_t n_det, const f
 int wb_mine_gather_launch(void *stream, const void *buf, int dtype, int64_t img_stride, int n_images, const WbMineLevel *levels,
                           int n_levels, int C, const void *rows, int64_t n_rows, int m, int n, void *out, uint32_t *err);
 
+/* Multiple-instance pruning of a finished cascade (Zhang & Viola 2007; the reference has no counterpart; DESIGN.md 4.14 has the
+ * rule, tests/mip_reference.py states it in NumPy).  New symbols of ABI 8 (the version number did not change: nothing that
+ * existed did).
+ * wb_mip_windows_launch: the acceptable windows of the window grids of n_images pyramids against their ground truth.
+ *   levels_host     HOST WbMineLevel [n_levels]: level l is u x v channels (chn_off is not looked at: no pyramid is read); its
+ *                   windows are those the scan visits, r in [0, u - m), c in [0, v - n); u, v in [0, 65536]
+ *   inv_scale_host  HOST float [n_levels], wb_boxes_launch's values: the box of a window is float32 [c, r, c+n, r+m] * inv_scale[l]
+ *   gt, gt_off, gt_ignore  as for wb_mine_select_launch (dev; both ends of a range clamped to [0, n_gt])
+ *   * best / owner of a window: wb_match_launch's (float64 IoU, operation by operation; the FIRST candidate that reaches the
+ *     maximum);
+ *   * a window is ACCEPTABLE when its image has candidates, best > min_iou (strict, float64) and gt_ignore[owner] == 0 --
+ *     wb_mine_select_launch's TP hit, without caps; it belongs to the bag of its owner only.
+ *   rows       dev, 16-byte aligned: the acceptable windows as wb_mine_select_launch's 32-byte rows {WbDet det (score 0); double
+ *              best; int32 owner; int32 label = 1}, in NO particular order.  n_rows dev uint32 [1]: their FULL number, also when
+ *              it exceeds out_capacity: rows beyond the capacity are not written, the caller allocates n_rows rows and calls again.
+ * One thread per window; an image's ground truth passes through LDS in chunks of 256 boxes.  One memset and one launch per
+ * level that has windows; no scratch, no host synchronisation.  No window or n_gt == 0: n_rows = 0 without a launch.
+ * Negative sizes, null or misaligned pointers, a level beyond 65536: WB_ERR_INVALID.  More than 1024 images, 256 levels,
+ * 16384 (image, level) groups or 2^32 - 1 windows: WB_ERR_UNSUPPORTED.
+ * wb_mip_prune_launch: the stage-sequential prune over bags.
+ *   trace      dev float32 [n_stages][stride], stride >= n_windows: the unrejected running scores of the acceptable windows
+ *              (wb_samples_trace_launch with reject = 0); no NaN
+ *   bag        dev int32 [n_windows]: the bag of every window; a window whose bag lies outside [0, n_bags) is never retained;
+ *              bag ids without windows are legal and contribute nothing
+ *   * a window is retained at the start when trace[n_stages - 1][i] >= floor;
+ *   * for t = 0 .. n_stages - 1, in order: theta[t] = the minimum, over the bags that have a retained window, of the maximum of
+ *     trace[t][i] over the bag's retained windows; then every retained window with `not (trace[t][i] >= theta[t])` (the
+ *     cascade's test) stops being retained: removed_at[i] = t;
+ *   * maxima and minima are taken on the order-preserving integer keys of the floats (as wb_calib_min_launch: -0 below +0), so
+ *     they are exact and depend neither on the order of the windows nor on the run.
+ *   theta      dev float32 [n_stages]: +inf everywhere when no window is retained
+ *   removed_at dev int32 [n_windows]: -1 for a window never retained, n_stages for one that survives every stage
+ *   counts     dev uint32 [2]: the bags with a window retained at the start; the windows that survive every stage
+ *   scratch    dev, 4-byte aligned, wb_mip_scratch_bytes(n_bags) bytes (4 per bag); its content on entry does not matter,
+ *              nor does that of the outputs
+ * Every retained bag keeps a window through all stages (the one that holds the bag's maximum at a stage is at or above that
+ * stage's theta).  A stage depends on the one before it through one number; the dependency is carried by the order of
+ * 2 * n_stages + 3 small launches (and three memsets) enqueued back to back: no workgroup waits for another and there is
+ * no host synchronisation.  n_windows == 0, n_stages == 0 or n_bags == 0: +inf, -1 and zeros by memsets alone.
+ * Negative sizes, stride < n_windows, (n_stages - 1) * stride + n_windows >= 2^31, n_bags >= 2^31, null or misaligned
+ * pointers, a short scratch: WB_ERR_INVALID. */
+int wb_mip_windows_launch(void *stream, const WbMineLevel *levels_host, const float *inv_scale_host, int n_levels, int m, int n,
+                          const double *gt, const int32_t *gt_off, const uint8_t *gt_ignore, int64_t n_gt, int n_images,
+                          double min_iou, void *rows, int64_t out_capacity, uint32_t *n_rows);
+int wb_mip_scratch_bytes(int64_t n_bags, size_t *bytes);
+int wb_mip_prune_launch(void *stream, const float *trace, int64_t stride, int n_stages, int64_t n_windows, const int32_t *bag,
+                        int64_t n_bags, float floor, void *scratch, size_t scratch_bytes, float *theta, int32_t *removed_at,
+                        uint32_t *counts);
+
 /* Split search of the FPGA flavour's tree learner (reference fpga/training.py:15-57), one tree level per call.
  * New symbols of ABI 8 (the version number did not change: nothing that existed did).
  *   xt       dev uint8 [n_features][n_samples]: the samples, FEATURE-major

@@ -125,6 +125,9 @@ SYMBOLS = {
     "wb_mine_select_launch": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_int64, _P, C.c_int, C.c_double,
                                         C.c_double, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_uint32, _P, C.c_size_t, _P, C.c_int64, _P]),
     "wb_mine_gather_launch": (C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int, _P, C.c_int, C.c_int, _P, C.c_int64, C.c_int, C.c_int, _P, _P]),
+    "wb_mip_windows_launch": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_int64, C.c_int, C.c_double, _P, C.c_int64, _P]),
+    "wb_mip_scratch_bytes": (C.c_int, [C.c_int64, C.POINTER(C.c_size_t)]),
+    "wb_mip_prune_launch": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int64, _P, C.c_int64, C.c_float, _P, C.c_size_t, _P, _P, _P]),
     "wb_fit_scratch_bytes": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
     "wb_fit_level_launch": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, _P, C.c_int, C.c_int, _P, C.c_int, _P, C.c_int, _P,
                                       C.c_size_t, _P]),

@@ -15,6 +15,11 @@ somewhere, and no theta can be raised without losing a retained sample.  The run
 stage order) and the minimum (on order-preserving integer keys) come from csrc/wb_cascade.hip:
 wb_samples_trace_launch and wb_calib_min_launch; the selection of the floor is a device sort.  tests/calib_reference.py
 is the NumPy statement.
+
+prune_instances is the paper's other half, multiple-instance pruning over whole images: every ground-truth box owns a bag of
+acceptable windows (instance_windows) and only one window of a bag has to survive, so the thetas are never below backward
+pruning's on the same windows (csrc/wb_mip.hip: wb_mip_windows_launch, wb_mip_prune_launch; DESIGN.md 4.14;
+tests/mip_reference.py is the NumPy statement).
 """
 import ctypes as C
 import math
@@ -159,6 +164,291 @@ def calibrate(model, positives, recall=0.99, margin=0.0, inplace=True):
     with np.errstate(over="ignore"):
         theta = (stage_min.cpu().numpy() - np.float32(margin)).astype(np.float32)
     res = Calibration(theta, list(model.theta), floor, N, int(n_ret.item()))
+    if inplace:
+        model.theta = [float(x) for x in theta]
+    return res
+
+
+# --------------------------------------------------------------------------------------- multiple-instance pruning
+def _check_operating_point(recall, margin):
+    if not (0.0 < recall <= 1.0):
+        raise ValueError(f"recall must lie in (0, 1], given {recall}")
+    if not (math.isfinite(margin) and margin >= 0.0):
+        raise ValueError(f"margin must be finite and not negative, given {margin}")
+
+
+def _check_predictions(model):
+    for t, w in enumerate(model.classifier):
+        if not np.isfinite(np.asarray(w.prediction)[np.asarray(w.left) < 0]).all():
+            raise ValueError(f"stage {t} has a non-finite prediction: its running scores cannot be ordered")
+
+
+def _gt_pairs(flat, gt_off):
+    """Flat ground-truth indices of a batch as int64 [K, 2] rows (image, index inside the image's list)."""
+    flat = np.asarray(flat, np.int64).reshape(-1)
+    image = np.searchsorted(gt_off.astype(np.int64), flat, side="right") - 1
+    return np.stack([image, flat - gt_off[image]], axis=1).astype(np.int64).reshape(-1, 2)
+
+
+def instance_windows(model, images, gt_boxes_per_image, min_iou=0.7):
+    """The ACCEPTABLE windows of a batch `images` [B, H, W] (or one [H, W]) for the ground truth of every image (a list
+    of B Boxes / None; for one image the Boxes itself), cropped out of the pyramid -- no scan: the thetas play no part.
+
+    The windows of pyramid level l (u x v channels, window m x n) are those the scan visits, r in [0, u - m), c in
+    [0, v - n); the box of a window is float32 [c, r, c+n, r+m] * float32(1 / scale[l]); best and owner are mine_batch's
+    (boxes.iou's float64 arithmetic, the first argmax).  A window is acceptable when its image has ground truth, best >
+    min_iou (strict) and the owner's 'ignore' flag is 0 -- label_boxes' TP rule without caps -- and belongs to the bag
+    of its owner only (wb_mip_windows_launch; the crops are wb_mine_gather_launch's).
+
+    Returns (mined, bag, reachable, unreachable): mined a MinedSamples of the acceptable windows in (image, level, row,
+    col) order (scores 0, tp_label 1, instance_id the owner); bag a device int32 tensor, the bag of every row = the
+    position of its (image, owner) in reachable; reachable / unreachable int64 ndarrays [K, 2] of (image, index in the
+    image's list) in that order: the non-ignored ground-truth boxes that own an acceptable window, and those that own
+    none (no window of the pyramid overlaps them enough: they are reported, and are no bag).
+
+    Host traffic: one upload (ground truth, offsets, flags, level table), two waits (the number of rows; the gather's
+    error word with the bags' ground-truth indices), a third and a second labelling launch when more than 4096 windows
+    per image are acceptable."""
+    import torch
+    from . import channels as _channels
+    from . import engine as _engine
+    from . import samples as _samples_mod
+    min_iou = float(min_iou)
+    if not (0.0 <= min_iou < 1.0):
+        raise ValueError(f"min_iou must lie in [0, 1), given {min_iou}")
+    if getattr(images, "ndim", None) == 2:
+        images = images[None]
+        gts = list(gt_boxes_per_image) if isinstance(gt_boxes_per_image, (list, tuple)) else [gt_boxes_per_image]
+    elif getattr(images, "ndim", None) == 3:
+        gts = list(gt_boxes_per_image)
+    else:
+        raise ValueError("images must have 3 dimensions [B,H,W] (or 2: one image)")
+    B, H, W = (int(x) for x in images.shape)
+    if len(gts) != B:
+        raise ValueError(f"instance_windows: {B} images, ground truth of {len(gts)}")
+    gt, gt_off, ignore = _samples_mod._ground_truth_arrays(gts)
+    shrink, n_per_oct, smooth, spec = _channels.read_opts(model.channel_opts)
+    m, n, Cc = (int(x) for x in model.shape)
+    assert Cc == spec.n_channels, f"Invalid number of channels. Expected {Cc} given {spec.n_channels}."
+    dev = nat.require_gpu()
+    eng = _engine.get_engine(H, W, _engine.array_dtype(images), shrink, n_per_oct, smooth, B, channels=spec)
+    L = eng.plan.n_levels
+    open_gt = np.flatnonzero(ignore == 0)
+    none = np.zeros((0, 2), np.int64)
+    empty = lambda: (_samples_mod._empty_mined(model.shape, eng.chn.dtype, dev), torch.empty(0, dtype=torch.int32, device=dev), none,
+                     _gt_pairs(open_gt, gt_off))
+    if L == 0 or gt.shape[0] == 0:
+        return empty()
+    lib = eng.lib
+    eng.load_images(images)
+    eng.run_channels()
+    table = np.zeros(L, nat.MINE_LEVEL_DTYPE)
+    for k in ("chn_off", "u", "v"):
+        table[k] = eng.level_np[k]
+    inv = np.ascontiguousarray(eng.inv_scales(), np.float32)
+    # one upload: ground truth | level table | offsets | ignore flags (the doubles first: all aligned)
+    parts = [gt.reshape(-1).view(np.uint8), table.view(np.uint8), gt_off.view(np.uint8), ignore]
+    offs = np.concatenate([[0], np.cumsum([p.size for p in parts])])
+    blob = torch.from_numpy(np.concatenate(parts)).to(dev)
+    at = lambda k: C.c_void_p(blob.data_ptr() + int(offs[k]))
+    n_rows = torch.zeros(1, dtype=torch.int32, device=dev)
+    room = 4096 * B
+    while True:
+        rows = torch.empty((room, 8), dtype=torch.int32, device=dev)
+        nat.check(lib.wb_mip_windows_launch(nat.stream_ptr(), table.ctypes.data_as(C.c_void_p), inv.ctypes.data_as(C.c_void_p), L, m, n,
+                                            at(0), at(2), at(3), gt.shape[0], B, min_iou, nat.ptr(rows), room, nat.ptr(n_rows)),
+                  "wb_mip_windows_launch")
+        N = int(n_rows.item()) & 0xFFFFFFFF
+        if N <= room:
+            break
+        room = N                                           # the full count: the second call has room for all
+    if N == 0:
+        return empty()
+    rows = _samples_mod.order_rows(rows[:N])
+    crops = torch.empty((N, m, n, Cc), dtype=eng.chn.dtype, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    nat.check(lib.wb_mine_gather_launch(nat.stream_ptr(), nat.ptr(eng.chn), eng.spec.wb_dtype, eng.chn_stride, B, at(1), L, Cc,
+                                        nat.ptr(rows), N, m, n, nat.ptr(crops), nat.ptr(err)), "wb_mine_gather_launch")
+    det = rows[:, :4].contiguous()
+    boxes = torch.empty((N, 4), dtype=torch.float32, device=dev)
+    scores = torch.empty(N, dtype=torch.float32, device=dev)
+    inv_dev = torch.from_numpy(inv).to(dev)
+    nat.check(lib.wb_boxes_launch(nat.stream_ptr(), nat.ptr(det), N, nat.ptr(inv_dev), m, n, nat.ptr(boxes), nat.ptr(scores)),
+              "wb_boxes_launch")
+    # bags: the distinct flat ground-truth indices that own a row, in ascending order = (image, index) order
+    off_dev = torch.from_numpy(gt_off[:-1].astype(np.int64)).to(dev)
+    flat = off_dev[rows[:, 0].to(torch.int64)] + rows[:, 6].to(torch.int64)
+    owners, bag = torch.unique(flat, return_inverse=True)
+    h = torch.cat([err.to(torch.int64), owners]).cpu().numpy()            # one wait: the error word and the owners
+    if int(h[0]):
+        raise RuntimeError("instance_windows: a window lies outside its pyramid level")
+    rc = rows[:, 2]
+    mined = _samples_mod.MinedSamples(samples=crops, scores=scores, tp_label=rows[:, 7].clone(), instance_id=rows[:, 6].clone(),
+                                      image=rows[:, 0].clone(), level=rows[:, 1].clone(), row=rc & 0xFFFF, col=(rc >> 16) & 0xFFFF,
+                                      boxes=boxes, best=rows[:, 4:6].contiguous().view(torch.float64).reshape(-1))
+    return mined, bag.to(torch.int32), _gt_pairs(h[1:], gt_off), _gt_pairs(np.setdiff1d(open_gt, h[1:]), gt_off)
+
+
+class InstancePruning:
+    """What prune_instances found: theta (float32 [T], the new thresholds), old_theta (the model's list before the
+    call), floor (the final-score floor, a float), n_bags (reachable ground-truth boxes), retained (bags with a window at
+    or above the floor: each keeps a window through every stage), recall = retained / n_bags, unreachable (int64 [K, 2]:
+    (position of the image in the iterable, index in its list) of the non-ignored boxes no window reaches), n_windows
+    (acceptable windows) and surviving (those that pass every stage)."""
+    __slots__ = ("theta", "old_theta", "floor", "n_bags", "retained", "unreachable", "n_windows", "surviving")
+
+    def __init__(self, theta, old_theta, floor, n_bags, retained, unreachable, n_windows, surviving):
+        self.theta, self.old_theta, self.floor, self.n_bags, self.retained = theta, old_theta, floor, n_bags, retained
+        self.unreachable, self.n_windows, self.surviving = unreachable, n_windows, surviving
+
+    @property
+    def recall(self):
+        return self.retained / self.n_bags
+
+    def __repr__(self):
+        return (f"InstancePruning(stages={self.theta.size}, floor={self.floor!r}, retained={self.retained}/{self.n_bags} bags, "
+                f"recall={self.recall:.4f}, unreachable={len(self.unreachable)}, surviving={self.surviving}/{self.n_windows} windows)")
+
+
+def _ordered_ints(F):
+    """int32 values whose signed order is the float order of the float32 tensor F (-0 below +0): wb_f32_key's order."""
+    import torch
+    b = F.contiguous().view(torch.int32)
+    return torch.where(b < 0, b ^ 0x7FFFFFFF, b)
+
+
+def bag_floor(F, bag, n_bags, recall):
+    """The floor of prune_instances on the device: (floor as a one-element float32 tensor, keep) -- the keep-th largest of
+    the bags' maxima of F (device float32 [N], N >= 1; bag: device int [N] in [0, n_bags)), keep = keep_count(recall, bags
+    that have a window).  One sort of (bag, ordered integer of F) pairs, so the sign of a zero is settled as in the kernels;
+    the last pair of every bag is its maximum.  One wait (the number of bags that have windows)."""
+    import torch
+    pair = (bag.to(torch.int64) << 32) | (_ordered_ints(F).to(torch.int64) + 2 ** 31)
+    pair = torch.sort(pair).values
+    last = torch.ones_like(pair, dtype=torch.bool)
+    last[:-1] = (pair[1:] >> 32) != (pair[:-1] >> 32)
+    G = ((pair[last] & 0xFFFFFFFF) - 2 ** 31).to(torch.int32)
+    keep = keep_count(recall, int(G.numel()))
+    g = torch.sort(G, descending=True).values[keep - 1:keep]
+    return torch.where(g < 0, g ^ 0x7FFFFFFF, g).view(torch.float32), keep
+
+
+def prune_launch(trace, bag, n_bags, floor):
+    """wb_mip_prune_launch on a device trace [T, N] (stage-major, contiguous rows) -> (theta float32 [T], removed_at int32
+    [N], counts int32 [2]) as device tensors."""
+    import torch
+    T, N = (int(x) for x in trace.shape)
+    assert N <= 1 or trace.stride(1) == 1, "the rows of the trace must be contiguous"
+    dev = trace.device
+    need = C.c_size_t()
+    nat.check(nat.load().wb_mip_scratch_bytes(n_bags, C.byref(need)), "wb_mip_scratch_bytes")
+    scratch = torch.empty(max(need.value, 4), dtype=torch.uint8, device=dev)
+    theta = torch.empty(T, dtype=torch.float32, device=dev)
+    removed_at = torch.empty(N, dtype=torch.int32, device=dev)
+    counts = torch.empty(2, dtype=torch.int32, device=dev)
+    nat.check(nat.load().wb_mip_prune_launch(nat.stream_ptr(), nat.ptr(trace), int(trace.stride(0)) if T > 1 else N, T, N, nat.ptr(bag),
+                                             n_bags, C.c_float(floor), nat.ptr(scratch), scratch.numel(), nat.ptr(theta),
+                                             nat.ptr(removed_at), nat.ptr(counts)), "wb_mip_prune_launch")
+    return theta, removed_at, counts
+
+
+def prune_trace(trace, bag, n_bags, recall, margin=0.0):
+    """The floor and the prune of prune_instances on a device trace [T, N] (unrejected, stage-major) with the bag of every
+    window (device int32 [N] in [0, n_bags), every bag with a window): (theta float32 ndarray [T], floor, retained bags,
+    surviving windows, removed_at device int32 [N]).  Two waits: the floor with the finiteness of the final scores; the
+    thetas with the counts.  ValueError for a final score that is not finite."""
+    import torch
+    T = int(trace.shape[0])
+    floor_t, _ = bag_floor(trace[T - 1], bag, n_bags, recall)
+    finite = torch.isfinite(trace[T - 1]).all()
+    h = torch.cat([floor_t.view(torch.int32), finite.to(torch.int32).reshape(1)]).cpu().numpy()
+    floor = float(h[:1].view(np.float32)[0])
+    if not (h[1] and math.isfinite(floor)):
+        raise ValueError("a final score is not finite: the running scores cannot be ordered")
+    theta_t, removed_at, counts = prune_launch(trace, bag, n_bags, floor)
+    h = torch.cat([theta_t.view(torch.int32), counts]).cpu().numpy()
+    with np.errstate(over="ignore"):
+        theta = (h[:T].view(np.float32) - np.float32(margin)).astype(np.float32)
+    return theta, floor, int(h[T]), int(h[T + 1]), removed_at
+
+
+def prune_instances(model, images, recall=0.99, margin=0.0, min_iou=0.7, batch=8, inplace=True):
+    """Choose all rejection thresholds of `model` by multiple-instance pruning (Zhang & Viola 2007) over whole images.
+
+    images : an iterable of dicts with 'image' and 'groundtruth_boxes', as train takes it; `batch` images of equal shape
+        and dtype go through one pyramid, as DeviceSamplePool.update batches them.
+    Every non-ignored ground-truth box owns a BAG: the acceptable windows it owns (instance_windows: best IoU > min_iou,
+    the box the first argmax).  Only one window of a bag has to survive:
+
+      * F[i] is the unrejected final score of window i, G[k] the largest F of bag k; keep = keep_count(recall, n_bags);
+        floor is the keep-th largest G; a window is retained at the start when F[i] >= floor, a bag when it has such a
+        window (ties at the floor are all kept);
+      * for t = 0 .. T - 1, in order: theta[t] is the minimum, over the bags with a retained window, of the maximum of
+        the running score after stage t over the bag's retained windows; then every window with `not (score >= theta[t])`
+        stops being retained.
+
+    So every retained bag keeps at least one window through all T stages, with its unrejected score, which is at least
+    floor; and no theta is below what calibrate(recall=1.0) gives on the windows retained at the start, so no sample set
+    costs more under these thresholds than under those.  margin (>= 0) is subtracted from every theta in float32, as in
+    calibrate, after the prune (which works with the unlowered values).  Maxima and minima are taken on wb_f32_key keys.
+
+    Per batch: the windows (wb_mip_windows_launch), their crops, their trace (wb_samples_trace_launch, reject = 0); only
+    the traces [T][N_b] and the bags are kept.  Then one floor selection on the device and one wb_mip_prune_launch.
+    The thresholds are stored in model.theta as Python floats holding float32 values (inplace).
+
+    ValueError: recall outside (0, 1], margin negative or not finite, min_iou outside [0, 1), an empty model, a
+    non-finite tree prediction or final score, no reachable ground truth, N * T >= 2**31.  Returns an InstancePruning."""
+    import torch
+    recall, margin, min_iou = float(recall), float(margin), float(min_iou)
+    _check_operating_point(recall, margin)
+    if not (0.0 <= min_iou < 1.0):
+        raise ValueError(f"min_iou must lie in [0, 1), given {min_iou}")
+    T = len(model)
+    if T == 0:
+        raise ValueError("prune_instances needs a model with at least one stage")
+    _check_predictions(model)
+    batch = max(int(batch), 1)
+    traces, bags, unreachable = [], [], []
+    state = dict(n_bags=0, n_images=0, n_windows=0)
+
+    def flush(group):
+        first = group[0]["image"]
+        stack = np.stack if isinstance(first, np.ndarray) else torch.stack
+        mined, bag, reach, unreach = instance_windows(model, stack([it["image"] for it in group]),
+                                                      [it["groundtruth_boxes"] for it in group], min_iou=min_iou)
+        if len(unreach):
+            unreachable.append(unreach + np.array([state["n_images"], 0]))
+        state["n_images"] += len(group)
+        if len(mined):
+            state["n_windows"] += len(mined)
+            if state["n_windows"] * T >= 2 ** 31:
+                raise ValueError(f"a trace of {state['n_windows']} windows x {T} stages has 2**31 entries or more: use fewer images")
+            traces.append(trace_launch(model, mined.samples, False, trace=True)[0])          # the crops are dropped here
+            bags.append(bag + state["n_bags"])
+            state["n_bags"] += len(reach)
+
+    group, kind = [], None
+    for item in images:
+        image = item["image"]
+        its = (tuple(image.shape), str(image.dtype))
+        if group and its != kind:                          # a shape change: what waits goes first
+            flush(group)
+            group = []
+        kind = its
+        group.append(item)
+        if len(group) == batch:
+            flush(group)
+            group = []
+    if group:
+        flush(group)
+    n_bags, N = state["n_bags"], state["n_windows"]
+    unreachable = np.concatenate(unreachable) if unreachable else np.zeros((0, 2), np.int64)
+    if n_bags == 0:
+        raise ValueError("prune_instances: no ground-truth box is reachable (no window of any pyramid overlaps one enough)")
+    trace = traces[0] if len(traces) == 1 else torch.cat(traces, dim=1).contiguous()
+    bag = bags[0] if len(bags) == 1 else torch.cat(bags)
+    theta, floor, retained, surviving, _ = prune_trace(trace, bag, n_bags, recall, margin)
+    res = InstancePruning(theta, list(model.theta), floor, n_bags, retained, unreachable, N, surviving)
     if inplace:
         model.theta = [float(x) for x in theta]
     return res
