@@ -28,6 +28,7 @@ import numpy as np
 
 from . import _native as nat
 from .compare import channel_tensor
+from .samples import LabelledBatch, _empty_mined, image_batches, stack_images
 
 
 def sample_count(model, X):
@@ -115,6 +116,34 @@ class Calibration:
                 f"recall={self.recall:.4f})")
 
 
+def _check_operating_point(recall, margin):
+    if not (0.0 < recall <= 1.0):
+        raise ValueError(f"recall must lie in (0, 1], given {recall}")
+    if not (math.isfinite(margin) and margin >= 0.0):
+        raise ValueError(f"margin must be finite and not negative, given {margin}")
+
+
+def _check_predictions(model):
+    for t, w in enumerate(model.classifier):
+        if not np.isfinite(np.asarray(w.prediction)[np.asarray(w.left) < 0]).all():
+            raise ValueError(f"stage {t} has a non-finite prediction: its running scores cannot be ordered")
+
+
+def _lowered(values, margin):
+    """float32(values) - float32(margin), in float32."""
+    with np.errstate(over="ignore"):
+        return (np.asarray(values, np.float32) - np.float32(margin)).astype(np.float32)
+
+
+def _new_thetas(model, values, margin, inplace):
+    """(theta, old_theta): the stage values read back from the device lowered by the margin, and the model's list before
+    the call; inplace: the thetas stored in model.theta as Python floats holding float32 values."""
+    theta, old = _lowered(values, margin), list(model.theta)
+    if inplace:
+        model.theta = [float(x) for x in theta]
+    return theta, old
+
+
 def calibrate(model, positives, recall=0.99, margin=0.0, inplace=True):
     """Choose all rejection thresholds of `model` by direct backward pruning on `positives` (module docstring).
 
@@ -135,16 +164,11 @@ def calibrate(model, positives, recall=0.99, margin=0.0, inplace=True):
     finite.  Returns a Calibration."""
     import torch
     recall, margin = float(recall), float(margin)
-    if not (0.0 < recall <= 1.0):
-        raise ValueError(f"recall must lie in (0, 1], given {recall}")
-    if not (math.isfinite(margin) and margin >= 0.0):
-        raise ValueError(f"margin must be finite and not negative, given {margin}")
+    _check_operating_point(recall, margin)
     T = len(model)
     if T == 0:
         raise ValueError("calibrate needs a model with at least one stage")
-    for t, w in enumerate(model.classifier):
-        if not np.isfinite(np.asarray(w.prediction)[np.asarray(w.left) < 0]).all():
-            raise ValueError(f"stage {t} has a non-finite prediction: its running scores cannot be ordered")
+    _check_predictions(model)
     if hasattr(positives, "get_true_positives"):
         positives = positives.get_true_positives()[0]
     N = sample_count(model, positives)
@@ -161,28 +185,11 @@ def calibrate(model, positives, recall=0.99, margin=0.0, inplace=True):
     n_ret = torch.empty(1, dtype=torch.int32, device=Xd.device)
     nat.check(nat.load().wb_calib_min_launch(nat.stream_ptr(), model.device_cascade().handle, nat.ptr(Xd), wdt, N,
                                              C.c_float(floor), nat.ptr(stage_min), nat.ptr(n_ret)), "wb_calib_min_launch")
-    with np.errstate(over="ignore"):
-        theta = (stage_min.cpu().numpy() - np.float32(margin)).astype(np.float32)
-    res = Calibration(theta, list(model.theta), floor, N, int(n_ret.item()))
-    if inplace:
-        model.theta = [float(x) for x in theta]
-    return res
+    theta, old = _new_thetas(model, stage_min.cpu().numpy(), margin, inplace)
+    return Calibration(theta, old, floor, N, int(n_ret.item()))
 
 
 # --------------------------------------------------------------------------------------- multiple-instance pruning
-def _check_operating_point(recall, margin):
-    if not (0.0 < recall <= 1.0):
-        raise ValueError(f"recall must lie in (0, 1], given {recall}")
-    if not (math.isfinite(margin) and margin >= 0.0):
-        raise ValueError(f"margin must be finite and not negative, given {margin}")
-
-
-def _check_predictions(model):
-    for t, w in enumerate(model.classifier):
-        if not np.isfinite(np.asarray(w.prediction)[np.asarray(w.left) < 0]).all():
-            raise ValueError(f"stage {t} has a non-finite prediction: its running scores cannot be ordered")
-
-
 def _gt_pairs(flat, gt_off):
     """Flat ground-truth indices of a batch as int64 [K, 2] rows (image, index inside the image's list)."""
     flat = np.asarray(flat, np.int64).reshape(-1)
@@ -206,86 +213,44 @@ def instance_windows(model, images, gt_boxes_per_image, min_iou=0.7):
     image's list) in that order: the non-ignored ground-truth boxes that own an acceptable window, and those that own
     none (no window of the pyramid overlaps them enough: they are reported, and are no bag).
 
-    Host traffic: one upload (ground truth, offsets, flags, level table), two waits (the number of rows; the gather's
-    error word with the bags' ground-truth indices), a third and a second labelling launch when more than 4096 windows
-    per image are acceptable."""
+    Host traffic: two uploads (ground truth, offsets, flags, level table and 1 / scale in one; the images' first flat
+    ground-truth indices for the bags), two waits (the number of rows; the gather's error word with the bags'
+    ground-truth indices), a third and a second labelling launch when more than 4096 windows per image are acceptable."""
     import torch
-    from . import channels as _channels
-    from . import engine as _engine
-    from . import samples as _samples_mod
     min_iou = float(min_iou)
     if not (0.0 <= min_iou < 1.0):
         raise ValueError(f"min_iou must lie in [0, 1), given {min_iou}")
-    if getattr(images, "ndim", None) == 2:
-        images = images[None]
-        gts = list(gt_boxes_per_image) if isinstance(gt_boxes_per_image, (list, tuple)) else [gt_boxes_per_image]
-    elif getattr(images, "ndim", None) == 3:
-        gts = list(gt_boxes_per_image)
-    else:
-        raise ValueError("images must have 3 dimensions [B,H,W] (or 2: one image)")
-    B, H, W = (int(x) for x in images.shape)
-    if len(gts) != B:
-        raise ValueError(f"instance_windows: {B} images, ground truth of {len(gts)}")
-    gt, gt_off, ignore = _samples_mod._ground_truth_arrays(gts)
-    shrink, n_per_oct, smooth, spec = _channels.read_opts(model.channel_opts)
-    m, n, Cc = (int(x) for x in model.shape)
-    assert Cc == spec.n_channels, f"Invalid number of channels. Expected {Cc} given {spec.n_channels}."
-    dev = nat.require_gpu()
-    eng = _engine.get_engine(H, W, _engine.array_dtype(images), shrink, n_per_oct, smooth, B, channels=spec)
-    L = eng.plan.n_levels
-    open_gt = np.flatnonzero(ignore == 0)
+    b = LabelledBatch(model, images, gt_boxes_per_image, "instance_windows")
+    B, L, dev, gt_off = b.B, b.L, b.dev, b.gt_off
+    open_gt = np.flatnonzero(b.ignore == 0)
     none = np.zeros((0, 2), np.int64)
-    empty = lambda: (_samples_mod._empty_mined(model.shape, eng.chn.dtype, dev), torch.empty(0, dtype=torch.int32, device=dev), none,
+    empty = lambda: (_empty_mined(model.shape, b.eng.chn.dtype, dev), torch.empty(0, dtype=torch.int32, device=dev), none,
                      _gt_pairs(open_gt, gt_off))
-    if L == 0 or gt.shape[0] == 0:
+    if L == 0 or b.gt.shape[0] == 0:
         return empty()
-    lib = eng.lib
-    eng.load_images(images)
-    eng.run_channels()
-    table = np.zeros(L, nat.MINE_LEVEL_DTYPE)
-    for k in ("chn_off", "u", "v"):
-        table[k] = eng.level_np[k]
-    inv = np.ascontiguousarray(eng.inv_scales(), np.float32)
-    # one upload: ground truth | level table | offsets | ignore flags (the doubles first: all aligned)
-    parts = [gt.reshape(-1).view(np.uint8), table.view(np.uint8), gt_off.view(np.uint8), ignore]
-    offs = np.concatenate([[0], np.cumsum([p.size for p in parts])])
-    blob = torch.from_numpy(np.concatenate(parts)).to(dev)
-    at = lambda k: C.c_void_p(blob.data_ptr() + int(offs[k]))
+    b.run_channels()
+    b.upload()
     n_rows = torch.zeros(1, dtype=torch.int32, device=dev)
     room = 4096 * B
     while True:
         rows = torch.empty((room, 8), dtype=torch.int32, device=dev)
-        nat.check(lib.wb_mip_windows_launch(nat.stream_ptr(), table.ctypes.data_as(C.c_void_p), inv.ctypes.data_as(C.c_void_p), L, m, n,
-                                            at(0), at(2), at(3), gt.shape[0], B, min_iou, nat.ptr(rows), room, nat.ptr(n_rows)),
-                  "wb_mip_windows_launch")
+        nat.check(b.eng.lib.wb_mip_windows_launch(nat.stream_ptr(), b.table.ctypes.data_as(C.c_void_p), b.inv.ctypes.data_as(C.c_void_p), L,
+                                                  b.m, b.n, b.ptr["gt"], b.ptr["gt_off"], b.ptr["ignore"], b.gt.shape[0], B, min_iou,
+                                                  nat.ptr(rows), room, nat.ptr(n_rows)), "wb_mip_windows_launch")
         N = int(n_rows.item()) & 0xFFFFFFFF
         if N <= room:
             break
         room = N                                           # the full count: the second call has room for all
     if N == 0:
         return empty()
-    rows = _samples_mod.order_rows(rows[:N])
-    crops = torch.empty((N, m, n, Cc), dtype=eng.chn.dtype, device=dev)
-    err = torch.zeros(1, dtype=torch.int32, device=dev)
-    nat.check(lib.wb_mine_gather_launch(nat.stream_ptr(), nat.ptr(eng.chn), eng.spec.wb_dtype, eng.chn_stride, B, at(1), L, Cc,
-                                        nat.ptr(rows), N, m, n, nat.ptr(crops), nat.ptr(err)), "wb_mine_gather_launch")
-    det = rows[:, :4].contiguous()
-    boxes = torch.empty((N, 4), dtype=torch.float32, device=dev)
-    scores = torch.empty(N, dtype=torch.float32, device=dev)
-    inv_dev = torch.from_numpy(inv).to(dev)
-    nat.check(lib.wb_boxes_launch(nat.stream_ptr(), nat.ptr(det), N, nat.ptr(inv_dev), m, n, nat.ptr(boxes), nat.ptr(scores)),
-              "wb_boxes_launch")
+    mined, err = b.mined(rows[:N])
     # bags: the distinct flat ground-truth indices that own a row, in ascending order = (image, index) order
     off_dev = torch.from_numpy(gt_off[:-1].astype(np.int64)).to(dev)
-    flat = off_dev[rows[:, 0].to(torch.int64)] + rows[:, 6].to(torch.int64)
+    flat = off_dev[mined.image.to(torch.int64)] + mined.instance_id.to(torch.int64)
     owners, bag = torch.unique(flat, return_inverse=True)
     h = torch.cat([err.to(torch.int64), owners]).cpu().numpy()            # one wait: the error word and the owners
     if int(h[0]):
         raise RuntimeError("instance_windows: a window lies outside its pyramid level")
-    rc = rows[:, 2]
-    mined = _samples_mod.MinedSamples(samples=crops, scores=scores, tp_label=rows[:, 7].clone(), instance_id=rows[:, 6].clone(),
-                                      image=rows[:, 0].clone(), level=rows[:, 1].clone(), row=rc & 0xFFFF, col=(rc >> 16) & 0xFFFF,
-                                      boxes=boxes, best=rows[:, 4:6].contiguous().view(torch.float64).reshape(-1))
     return mined, bag.to(torch.int32), _gt_pairs(h[1:], gt_off), _gt_pairs(np.setdiff1d(open_gt, h[1:]), gt_off)
 
 
@@ -367,16 +332,14 @@ def prune_trace(trace, bag, n_bags, recall, margin=0.0):
         raise ValueError("a final score is not finite: the running scores cannot be ordered")
     theta_t, removed_at, counts = prune_launch(trace, bag, n_bags, floor)
     h = torch.cat([theta_t.view(torch.int32), counts]).cpu().numpy()
-    with np.errstate(over="ignore"):
-        theta = (h[:T].view(np.float32) - np.float32(margin)).astype(np.float32)
-    return theta, floor, int(h[T]), int(h[T + 1]), removed_at
+    return _lowered(h[:T].view(np.float32), margin), floor, int(h[T]), int(h[T + 1]), removed_at
 
 
 def prune_instances(model, images, recall=0.99, margin=0.0, min_iou=0.7, batch=8, inplace=True):
     """Choose all rejection thresholds of `model` by multiple-instance pruning (Zhang & Viola 2007) over whole images.
 
     images : an iterable of dicts with 'image' and 'groundtruth_boxes', as train takes it; `batch` images of equal shape
-        and dtype go through one pyramid, as DeviceSamplePool.update batches them.
+        and dtype go through one pyramid (samples.image_batches).
     Every non-ignored ground-truth box owns a BAG: the acceptable windows it owns (instance_windows: best IoU > min_iou,
     the box the first argmax).  Only one window of a bag has to survive:
 
@@ -412,10 +375,8 @@ def prune_instances(model, images, recall=0.99, margin=0.0, min_iou=0.7, batch=8
     state = dict(n_bags=0, n_images=0, n_windows=0)
 
     def flush(group):
-        first = group[0]["image"]
-        stack = np.stack if isinstance(first, np.ndarray) else torch.stack
-        mined, bag, reach, unreach = instance_windows(model, stack([it["image"] for it in group]),
-                                                      [it["groundtruth_boxes"] for it in group], min_iou=min_iou)
+        mined, bag, reach, unreach = instance_windows(model, stack_images(group), [it["groundtruth_boxes"] for it in group],
+                                                      min_iou=min_iou)
         if len(unreach):
             unreachable.append(unreach + np.array([state["n_images"], 0]))
         state["n_images"] += len(group)
@@ -427,19 +388,7 @@ def prune_instances(model, images, recall=0.99, margin=0.0, min_iou=0.7, batch=8
             bags.append(bag + state["n_bags"])
             state["n_bags"] += len(reach)
 
-    group, kind = [], None
-    for item in images:
-        image = item["image"]
-        its = (tuple(image.shape), str(image.dtype))
-        if group and its != kind:                          # a shape change: what waits goes first
-            flush(group)
-            group = []
-        kind = its
-        group.append(item)
-        if len(group) == batch:
-            flush(group)
-            group = []
-    if group:
+    for group in image_batches(images, batch):
         flush(group)
     n_bags, N = state["n_bags"], state["n_windows"]
     unreachable = np.concatenate(unreachable) if unreachable else np.zeros((0, 2), np.int64)
@@ -447,8 +396,6 @@ def prune_instances(model, images, recall=0.99, margin=0.0, min_iou=0.7, batch=8
         raise ValueError("prune_instances: no ground-truth box is reachable (no window of any pyramid overlaps one enough)")
     trace = traces[0] if len(traces) == 1 else torch.cat(traces, dim=1).contiguous()
     bag = bags[0] if len(bags) == 1 else torch.cat(bags)
-    theta, floor, retained, surviving, _ = prune_trace(trace, bag, n_bags, recall, margin)
-    res = InstancePruning(theta, list(model.theta), floor, n_bags, retained, unreachable, N, surviving)
-    if inplace:
-        model.theta = [float(x) for x in theta]
-    return res
+    stage_theta, floor, retained, surviving, _ = prune_trace(trace, bag, n_bags, recall)     # margin 0: the unlowered values
+    theta, old = _new_thetas(model, stage_theta, margin, inplace)                             # (x - 0.0f is x, bit for bit)
+    return InstancePruning(theta, old, floor, n_bags, retained, unreachable, N, surviving)

@@ -364,7 +364,7 @@ extern "C" int wb_cart_sort_launch(void *stream, const float *xt, int64_t n_samp
         wb_set_error("wb_cart_sort_launch: at most %d samples and %d features", WB_CART_MAX_SAMPLES, WB_CART_MAX_FEATURES);
         return WB_ERR_UNSUPPORTED;
     }
-    WB_REQUIRE(reinterpret_cast<uintptr_t>(xt) % 4 == 0 && reinterpret_cast<uintptr_t>(order) % 4 == 0,
+    WB_REQUIRE(wb_aligned(xt, 4) && wb_aligned(order, 4),
                "wb_cart_sort_launch: misaligned pointer");
     hipLaunchKernelGGL(cart_sort_kernel, dim3((unsigned)n_features), dim3(WB_CART_SORT_THREADS), 0,
                        static_cast<hipStream_t>(stream), xt, (int)n_samples, order);
@@ -414,10 +414,10 @@ extern "C" int wb_cart_level_launch(void *stream, const float *xt, int64_t n_sam
                "%s: min_samples_leaf >= 1, child_base >= 0", who);
     WB_REQUIRE(scale > 0.0 && scale < __builtin_inf(), "%s: scale must be positive and finite", who);
     WB_REQUIRE(xt && q && cls && order_in && order_out && node && scratch && splits && order_in != order_out, "%s: null pointer", who);
-    WB_REQUIRE(reinterpret_cast<uintptr_t>(xt) % 4 == 0 && reinterpret_cast<uintptr_t>(q) % 8 == 0 &&
-               reinterpret_cast<uintptr_t>(order_in) % 4 == 0 && reinterpret_cast<uintptr_t>(order_out) % 4 == 0 &&
-               reinterpret_cast<uintptr_t>(node) % 4 == 0 && reinterpret_cast<uintptr_t>(scratch) % 16 == 0 &&
-               reinterpret_cast<uintptr_t>(splits) % 8 == 0, "%s: misaligned pointer", who);
+    WB_REQUIRE(wb_aligned(xt, 4) && wb_aligned(q, 8) &&
+               wb_aligned(order_in, 4) && wb_aligned(order_out, 4) &&
+               wb_aligned(node, 4) && wb_aligned(scratch, 16) &&
+               wb_aligned(splits, 8), "%s: misaligned pointer", who);
     size_t need = 0;
     if (int rc = wb_cart_scratch_bytes(n_features, n_open, &need)) return rc;
     WB_REQUIRE(scratch_bytes >= need, "%s: scratch of %zu bytes, %zu needed", who, scratch_bytes, need);

@@ -304,15 +304,6 @@ struct CalibArgs {
     uint32_t *n_retained;    // [1], zeroed ahead of the launch
 };
 
-// the smallest key of a wave, in every lane
-__device__ inline uint32_t wave_min_u32(uint32_t k) {
-    for (int off = 32; off >= 1; off >>= 1) {
-        const uint32_t o = (uint32_t)__shfl_xor((int)k, off);
-        k = o < k ? o : k;
-    }
-    return k;
-}
-
 __global__ __launch_bounds__(256) void calib_min_kernel(CalibArgs a) {
     __shared__ uint32_t slot[WB_CALIB_CHUNK];
     __shared__ uint32_t kept;
@@ -339,7 +330,7 @@ __global__ __launch_bounds__(256) void calib_min_kernel(CalibArgs a) {
         if (wave_kept)
             for (int t = t0; t < t1; ++t) {
                 if (retained) flat_stage(a.model, t, h, fetch);
-                const uint32_t k = wave_min_u32(retained ? wb_f32_key(h) : 0xFFFFFFFFu);
+                const uint32_t k = wb_wave_min_u32(retained ? wb_f32_key(h) : 0xFFFFFFFFu);
                 if (lane == 0) atomicMin(&slot[t - t0], k);
             }
         __syncthreads();
@@ -350,7 +341,7 @@ __global__ __launch_bounds__(256) void calib_min_kernel(CalibArgs a) {
     if (tid == 0 && kept) atomicAdd(a.n_retained, kept);
 }
 
-// the keys back to floats, in place; a stage no sample reached keeps +inf
+// keys of minima back to floats, in place; all ones (no sample reached the stage, no bag) becomes +inf: wb_keys_to_floats_launch
 __global__ __launch_bounds__(256) void calib_keys_kernel(uint32_t *keys, int T) {
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t >= T) return;
@@ -414,6 +405,13 @@ struct CascEnv {
 };
 
 }  // namespace
+
+int wb_keys_to_floats_launch(hipStream_t st, uint32_t *keys, int T) {
+    if (T == 0) return WB_OK;
+    hipLaunchKernelGGL(calib_keys_kernel, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, st, keys, T);
+    WB_HIP_CHECK(hipGetLastError());
+    return WB_OK;
+}
 
 int wb_cascade_group(int depth) { return depth >= 3 ? 2 : 4; }
 
@@ -621,11 +619,7 @@ extern "C" int wb_calib_min_launch(void *stream, const WbModel *model, const voi
         hipLaunchKernelGGL(calib_min_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a);
         WB_HIP_CHECK(hipGetLastError());
     }
-    if (T) {
-        hipLaunchKernelGGL(calib_keys_kernel, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, st, keys, T);
-        WB_HIP_CHECK(hipGetLastError());
-    }
-    return WB_OK;
+    return wb_keys_to_floats_launch(st, keys, T);
 }
 
 extern "C" int wb_tree_apply_launch(void *stream, const void *X, int x_dtype, int64_t n_samples, int m, int n, int C,

@@ -728,12 +728,12 @@ extern "C" int wb_channels_launch_x(void *stream, const void *img, int64_t img_s
     const int rank_form = rank ? wb_tile_form(rank_dtype) : -1;
     const bool wide = rank_form == WB_FORM_RANK16;
     WB_REQUIRE(!wide || rank_model->form[WB_FORM_RANK16].present, "wb_channels_launch_x: this model has no 16-bit rank tables (wb_model_info: rank16_ok)");
-    WB_REQUIRE(!wide || reinterpret_cast<uintptr_t>(rank) % 8 == 0, "wb_channels_launch_x: 16-bit ranks must be 8-byte aligned");
+    WB_REQUIRE(!wide || wb_aligned(rank, 8), "wb_channels_launch_x: 16-bit ranks must be 8-byte aligned");
     WB_REQUIRE(!patches || (dtype == WB_DTYPE_U8 && channel_func != WB_CHN_GRAD_MAG),
                "wb_channels_launch_x: the patch table goes with uint8 images and the gradient-histogram kernels");
     WB_REQUIRE(!rank || channel_func == WB_CHN_GRAD_HIST, "wb_channels_launch: ranks are written for grad_hist channels only");
     WB_REQUIRE(!rank || wide || rank_model->form[WB_FORM_RANK8].present, "wb_channels_launch: this model has no rank tables (wb_model_info: rank_ok)");
-    WB_REQUIRE(!rank || reinterpret_cast<uintptr_t>(rank) % 4 == 0, "wb_channels_launch: rank must be 4-byte aligned");
+    WB_REQUIRE(!rank || wb_aligned(rank, 4), "wb_channels_launch: rank must be 4-byte aligned");
     WB_REQUIRE(cs_sn || channel_func != WB_CHN_GRAD_HIST, "wb_channels_launch: grad_hist needs the orientation constants");
     WB_REQUIRE(batch >= 1 && n_levels >= 1 && n_tiles >= 1, "wb_channels_launch: empty launch");
     WB_REQUIRE(batch <= 65535, "wb_channels_launch: batch %d exceeds grid.y limit", batch);

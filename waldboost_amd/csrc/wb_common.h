@@ -35,6 +35,22 @@ __host__ __device__ inline float wb_key_f32(uint32_t k) {
     return f;
 }
 
+// the smallest key of a wave, in every lane
+__device__ inline uint32_t wb_wave_min_u32(uint32_t k) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const uint32_t o = (uint32_t)__shfl_xor((int)k, off, WB_WAVE);
+        k = o < k ? o : k;
+    }
+    return k;
+}
+// T keys of minima back to floats, in place, behind the work on the stream (wb_cascade.hip); all ones -- a minimum over
+// nothing -- becomes +inf
+int wb_keys_to_floats_launch(hipStream_t st, uint32_t *keys, int T);
+
+// ---- a launcher's alignment test (host)
+inline bool wb_aligned(const void *p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
+
 // ---- how a float64-held image dtype is cast back after the resize / pooled in the octaves (WB_DTYPE_F64 .. WB_DTYPE_F16) ----
 #define WB_CAST_NONE 0     // float64
 #define WB_CAST_TRUNC 1    // integers: truncation toward zero

@@ -9,10 +9,10 @@
 //   * det_finish_sorted_kernel<16>  the same in the reference's order (wb_det_finish_sorted_launch);
 //   * det_bucket_kernel + det_finish_sorted_kernel<4>   a batch's records by image, each image ordered
 //                                   (wb_det_order_batch_launch).
-// Every step the kernels share stands here once: the shard prefix, the sort key, the box arithmetic, the unordered finish
+// Every step the kernels share stands here once: the shard prefix, the sort key, the box arithmetic (wb_match_iou.h), the unordered finish
 // of one shard and the bisection from a packed position to its record.  Each is a bit-exactness contract with the
 // reference's get_boxes and result order.
-#include "wb_common.h"
+#include "wb_match_iou.h"   // window_box: Model.get_boxes' arithmetic, shared with the labelling of windows
 
 namespace {
 
@@ -41,12 +41,6 @@ int det_key_fits(const char *who, int n_levels, int max_rows, int max_cols, uint
     wb_set_error("%s: %d levels of up to %d x %d windows, %u records do not fit the %d/%d/%d/%d-bit key", who, n_levels, max_rows,
                  max_cols, out_capacity, DET_KEY_LEVEL_BITS, DET_KEY_ROW_BITS, DET_KEY_COL_BITS, DET_KEY_POS_BITS);
     return WB_ERR_UNSUPPORTED;
-}
-
-// Model.get_boxes (reference model.py:136-147): [c, r, c+n, r+m] as fp32, times fp32(1/scale)
-__device__ inline float4 det_box(uint32_t level, uint32_t r, uint32_t c, const float *inv_scale, int m, int n) {
-    const float sc = inv_scale[level];
-    return make_float4((float)c * sc, (float)r * sc, (float)((int)c + n) * sc, (float)((int)r + m) * sc);
 }
 
 // ---- the shard counters, as every lane of a wave sees them (lane = shard)
@@ -91,7 +85,7 @@ struct FinishBlock {
 };
 
 // The unordered finish, one workgroup of 256 per shard: for every valid record of the shard, at its packed position
-// `at` < out_cap, keys[at] = det_key(level, r, c, at), boxes[at] = det_box, scores[at] = score.  The host sorts the keys and
+// `at` < out_cap, keys[at] = det_key(level, r, c, at), boxes[at] = window_box, scores[at] = score.  The host sorts the keys and
 // gathers -- no per-field arithmetic on the host.
 __device__ inline void finish_shard(const WbDet *det, uint32_t cap, int shard, const ShardPrefix &p, const float *inv_scale, int m, int n,
                                     const FinishBlock &o, uint32_t out_cap) {
@@ -102,7 +96,7 @@ __device__ inline void finish_shard(const WbDet *det, uint32_t cap, int shard, c
         if (at >= out_cap) break;
         const WbDet d = src[i];
         o.keys[at] = det_key((uint32_t)d.level, d.r, d.c, at);
-        o.boxes[at] = det_box((uint32_t)d.level, d.r, d.c, inv_scale, m, n);
+        o.boxes[at] = window_box(inv_scale[(uint32_t)d.level], d.r, d.c, m, n);
         o.scores[at] = d.score;
     }
 }
@@ -127,7 +121,7 @@ __global__ void boxes_kernel(const WbDet *det, int64_t n_det, const float *inv_s
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_det) return;
     WbDet d = det[i];
-    reinterpret_cast<float4 *>(boxes)[i] = det_box((uint32_t)d.level, d.r, d.c, inv_scale, m, n);
+    reinterpret_cast<float4 *>(boxes)[i] = window_box(inv_scale[(uint32_t)d.level], d.r, d.c, m, n);
     scores[i] = d.score;
 }
 
@@ -240,7 +234,7 @@ __global__ __launch_bounds__(256) void det_finish_sorted_kernel(const WbDet *det
     for (uint32_t d = 1; d < TPR; d <<= 1) smaller += (uint32_t)__shfl_xor((int)smaller, (int)d);
     if (live && part == 0) {
         o.keys[smaller] = me;
-        o.boxes[smaller] = det_box(det_key_level(me), det_key_row(me), det_key_col(me), inv_scale, m, n);
+        o.boxes[smaller] = window_box(inv_scale[det_key_level(me)], det_key_row(me), det_key_col(me), m, n);
         o.scores[smaller] = sscore[q];
     }
 }
@@ -317,7 +311,7 @@ extern "C" int wb_det_pack_launch(void *stream, const WbDet *det, const uint32_t
                                   int32_t *packed, uint32_t packed_capacity) {
     WB_REQUIRE(det_count && packed, "wb_det_pack_launch: null pointer");
     WB_REQUIRE(det || shard_capacity == 0, "wb_det_pack_launch: det is null but capacity > 0");
-    WB_REQUIRE(reinterpret_cast<uintptr_t>(packed) % 16 == 0, "wb_det_pack_launch: packed must be 16-byte aligned");
+    WB_REQUIRE(wb_aligned(packed, 16), "wb_det_pack_launch: packed must be 16-byte aligned");
     hipLaunchKernelGGL(det_pack_kernel, dim3(WB_DET_SHARDS), dim3(256), 0, (hipStream_t)stream, det, det_count,
                        shard_capacity, packed, packed_capacity);
     WB_HIP_CHECK(hipGetLastError());
@@ -329,7 +323,7 @@ extern "C" int wb_det_finish_launch(void *stream, const WbDet *det, const uint32
                                     void *out, uint32_t out_capacity) {
     WB_REQUIRE(det_count && out && inv_scale, "wb_det_finish_launch: null pointer");
     WB_REQUIRE(det || shard_capacity == 0, "wb_det_finish_launch: det is null but capacity > 0");
-    WB_REQUIRE(reinterpret_cast<uintptr_t>(out) % 16 == 0, "wb_det_finish_launch: out must be 16-byte aligned");
+    WB_REQUIRE(wb_aligned(out, 16), "wb_det_finish_launch: out must be 16-byte aligned");
     WB_REQUIRE(out_capacity % 2 == 0, "wb_det_finish_launch: out_capacity must be even (16-byte aligned sections)");
     if (int rc = det_key_fits("wb_det_finish_launch", n_levels, max_rows, max_cols, out_capacity)) return rc;
     hipLaunchKernelGGL(det_finish_kernel, dim3(WB_DET_SHARDS), dim3(256), 0, (hipStream_t)stream, det, det_count,
@@ -344,7 +338,7 @@ extern "C" int wb_det_finish_sorted_launch(void *stream, const WbDet *det, const
     WB_REQUIRE(tail || tail_words == 0, "wb_det_finish_sorted_launch: tail is null but tail_words > 0");
     WB_REQUIRE(det_count && out && inv_scale, "wb_det_finish_sorted_launch: null pointer");
     WB_REQUIRE(det || shard_capacity == 0, "wb_det_finish_sorted_launch: det is null but capacity > 0");
-    WB_REQUIRE(reinterpret_cast<uintptr_t>(out) % 16 == 0, "wb_det_finish_sorted_launch: out must be 16-byte aligned");
+    WB_REQUIRE(wb_aligned(out, 16), "wb_det_finish_sorted_launch: out must be 16-byte aligned");
     WB_REQUIRE(out_capacity % 2 == 0, "wb_det_finish_sorted_launch: out_capacity must be even (16-byte aligned sections)");
     if (int rc = det_key_fits("wb_det_finish_sorted_launch", n_levels, max_rows, max_cols, out_capacity)) return rc;
     hipLaunchKernelGGL(det_finish_sorted_kernel<16>, dim3(WB_FINISH_SORT_MAX * 16 / 256), dim3(256), 0, (hipStream_t)stream, det, det_count,
@@ -359,7 +353,7 @@ extern "C" int wb_det_order_batch_launch(void *stream, const WbDet *det, const u
     WB_REQUIRE(det_count && out && inv_scale && scratch, "wb_det_order_batch_launch: null pointer");
     WB_REQUIRE(det || shard_capacity == 0, "wb_det_order_batch_launch: det is null but capacity > 0");
     WB_REQUIRE(n_images >= 1 && n_images <= 65535, "wb_det_order_batch_launch: 1 .. 65535 images");
-    WB_REQUIRE(reinterpret_cast<uintptr_t>(out) % 16 == 0 && reinterpret_cast<uintptr_t>(scratch) % 16 == 0,
+    WB_REQUIRE(wb_aligned(out, 16) && wb_aligned(scratch, 16),
                "wb_det_order_batch_launch: out and scratch must be 16-byte aligned");
     WB_REQUIRE(out_capacity % 4 == 0 && out_capacity >= 4, "wb_det_order_batch_launch: out_capacity must be a multiple of 4 (16-byte aligned blocks)");
     if (int rc = det_key_fits("wb_det_order_batch_launch", n_levels, max_rows, max_cols, out_capacity)) return rc;

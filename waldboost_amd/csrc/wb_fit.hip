@@ -269,9 +269,9 @@ extern "C" int wb_fit_level_launch(void *stream, const uint8_t *xt, int64_t n_sa
     WB_REQUIRE(xt && q && cls && node && allowed && scratch && splits, "wb_fit_level_launch: null pointer");
     WB_REQUIRE(n_samples >= 1 && n_features >= 1 && n_allowed >= 1, "wb_fit_level_launch: empty problem");
     WB_REQUIRE(n_samples <= 0x7fffffff, "wb_fit_level_launch: at most 2^31 - 1 samples");
-    WB_REQUIRE(reinterpret_cast<uintptr_t>(q) % 8 == 0 && reinterpret_cast<uintptr_t>(node) % 4 == 0 &&
-               reinterpret_cast<uintptr_t>(allowed) % 4 == 0 && reinterpret_cast<uintptr_t>(scratch) % 16 == 0 &&
-               reinterpret_cast<uintptr_t>(splits) % 8 == 0, "wb_fit_level_launch: misaligned pointer");
+    WB_REQUIRE(wb_aligned(q, 8) && wb_aligned(node, 4) &&
+               wb_aligned(allowed, 4) && wb_aligned(scratch, 16) &&
+               wb_aligned(splits, 8), "wb_fit_level_launch: misaligned pointer");
     size_t need = 0;
     if (int rc = wb_fit_scratch_bytes(n_allowed, n_open, &need)) return rc;
     WB_REQUIRE(scratch_bytes >= need, "wb_fit_level_launch: scratch of %zu bytes, %zu needed", scratch_bytes, need);
@@ -297,7 +297,7 @@ extern "C" int wb_fit_route_launch(void *stream, const uint8_t *xt, int64_t n_sa
     WB_REQUIRE(xt && node && splits, "wb_fit_route_launch: null pointer");
     WB_REQUIRE(n_samples >= 1 && n_samples <= 0x7fffffff && n_features >= 1, "wb_fit_route_launch: 1 .. 2^31 - 1 samples");
     WB_REQUIRE(child_base >= level_base + n_level, "wb_fit_route_launch: children are numbered behind their level");
-    WB_REQUIRE(reinterpret_cast<uintptr_t>(node) % 4 == 0 && reinterpret_cast<uintptr_t>(splits) % 8 == 0,
+    WB_REQUIRE(wb_aligned(node, 4) && wb_aligned(splits, 8),
                "wb_fit_route_launch: misaligned pointer");
     hipStream_t st = static_cast<hipStream_t>(stream);
     const unsigned blocks = (unsigned)((n_samples + WB_FIT_THREADS - 1) / WB_FIT_THREADS);

@@ -4,10 +4,11 @@
 //
 // Semantics (tests/match_designs.py proves the expected answers in exact arithmetic):
 //   * detection i belongs to image b = dt_image[i]; its candidates are gt[gt_off[b] .. gt_off[b + 1]);
-//   * iou is boxes.iou's float64 arithmetic, operation by operation (this file is built with -ffp-contract=off: no fused
-//     multiply-add; the float64 divide is the correctly rounded one);
+//   * iou is boxes.iou's float64 arithmetic, operation by operation (wb_match_iou.h; this file is built with
+//     -ffp-contract=off: no fused multiply-add; the float64 divide is the correctly rounded one);
 //   * best[i] is the largest iou, owner[i] the FIRST candidate that reaches it, counted inside the image's own list
-//     (np.argmax): a detection that overlaps nothing is owned by candidate 0;  no candidates: best 0, owner -1.
+//     (np.argmax; wb_match_iou.h: match_argmax): a detection that overlaps nothing is owned by candidate 0;  no candidates:
+//     best 0, owner -1.
 //
 // One kernel, one thread per detection, 256 per workgroup.  A workgroup whose detections all belong to one image stages
 // that image's candidates through LDS, WB_MATCH_CHUNK = 64 boxes at a time: 64 boxes are 256 doubles, ONE coalesced 8-byte
@@ -19,10 +20,8 @@
 //
 // Whatever dt_image and gt_off hold, nothing outside the buffers is read: the image is clamped to [0, n_images), both ends
 // of a range to [0, n_gt], and an end in front of its start gives an empty range.  Every loop is bounded by n_gt.
-#include "wb_common.h"
-#include "wb_match_iou.h"   // match_range, match_iou: shared with the miner (wb_mine.hip)
+#include "wb_match_iou.h"   // the IoU, the candidate range and the argmax step
 
-#define WB_MATCH_MAX (1 << 26)      // most detections of one call (what one detect call can return)
 #define WB_MATCH_CHUNK 64           // candidates staged in LDS at a time: 4 * 64 doubles = one per thread
 
 namespace {
@@ -47,9 +46,8 @@ __global__ __launch_bounds__(256) void match_kernel(const double *dt, const int3
     __syncthreads();
     const bool one_image = s_mixed == 0;                       // (workgroup-uniform)
     const MatchRange r = match_range(gt_off, b, n_gt);
-    const double ax1 = dt[4 * ii], ay1 = dt[4 * ii + 1], ax2 = dt[4 * ii + 2], ay2 = dt[4 * ii + 3];
-    const double area_a = (ax2 - ax1) * (ay2 - ay1);
-    double bestv = -1.0;                                       // (an iou is never negative and never NaN: the first candidate takes it)
+    const MatchBox box = match_box(dt[4 * ii], dt[4 * ii + 1], dt[4 * ii + 2], dt[4 * ii + 3]);
+    double bestv = -1.0;
     int32_t own = -1;
     if (one_image) {
         for (int64_t c0 = r.lo; c0 < r.hi; c0 += WB_MATCH_CHUNK) {     // (r is the same in every thread)
@@ -57,22 +55,10 @@ __global__ __launch_bounds__(256) void match_kernel(const double *dt, const int3
             __syncthreads();                                   // the last chunk has been read by everyone
             if (tid < 4u * m) sg[tid] = gt[4 * c0 + tid];
             __syncthreads();
-            for (uint32_t k = 0; k < m; ++k) {
-                const double v = match_iou(ax1, ay1, ax2, ay2, area_a, sg[4 * k], sg[4 * k + 1], sg[4 * k + 2], sg[4 * k + 3]);
-                if (v > bestv) {
-                    bestv = v;
-                    own = (int32_t)(c0 - r.lo) + (int32_t)k;
-                }
-            }
+            match_argmax(bestv, own, box, sg, 0u, m, (int32_t)(c0 - r.lo));
         }
     } else {
-        for (int64_t c = r.lo; c < r.hi; ++c) {
-            const double v = match_iou(ax1, ay1, ax2, ay2, area_a, gt[4 * c], gt[4 * c + 1], gt[4 * c + 2], gt[4 * c + 3]);
-            if (v > bestv) {
-                bestv = v;
-                own = (int32_t)(c - r.lo);
-            }
-        }
+        match_argmax(bestv, own, box, gt, r.lo, r.hi, 0);
     }
     if (live) {
         best[i] = own < 0 ? 0.0 : bestv;
@@ -89,14 +75,11 @@ extern "C" int wb_match_launch(void *stream, const double *dt, const int32_t *dt
     if (n_dt == 0) return WB_OK;
     WB_REQUIRE(dt && dt_image && gt_off && best && owner && (gt || n_gt == 0), "wb_match_launch: null pointer");
     WB_REQUIRE(n_images >= 1, "wb_match_launch: %lld detections of no image", (long long)n_dt);
-    WB_REQUIRE(reinterpret_cast<uintptr_t>(dt) % 8 == 0 && reinterpret_cast<uintptr_t>(gt) % 8 == 0 &&
-                   reinterpret_cast<uintptr_t>(best) % 8 == 0,
-               "wb_match_launch: dt, gt and best must be 8-byte aligned");
-    WB_REQUIRE(reinterpret_cast<uintptr_t>(dt_image) % 4 == 0 && reinterpret_cast<uintptr_t>(gt_off) % 4 == 0 &&
-                   reinterpret_cast<uintptr_t>(owner) % 4 == 0,
+    WB_REQUIRE(wb_aligned(dt, 8) && wb_aligned(gt, 8) && wb_aligned(best, 8), "wb_match_launch: dt, gt and best must be 8-byte aligned");
+    WB_REQUIRE(wb_aligned(dt_image, 4) && wb_aligned(gt_off, 4) && wb_aligned(owner, 4),
                "wb_match_launch: dt_image, gt_off and owner must be 4-byte aligned");
-    if (n_dt > WB_MATCH_MAX) {
-        wb_set_error("wb_match_launch: %lld detections (at most %d in one call)", (long long)n_dt, WB_MATCH_MAX);
+    if (n_dt > WB_LABEL_MAX_DET) {
+        wb_set_error("wb_match_launch: %lld detections (at most %d in one call)", (long long)n_dt, WB_LABEL_MAX_DET);
         return WB_ERR_UNSUPPORTED;
     }
     hipLaunchKernelGGL(match_kernel, dim3((uint32_t)((n_dt + 255) / 256)), dim3(256), 0, (hipStream_t)stream, dt, dt_image, gt,

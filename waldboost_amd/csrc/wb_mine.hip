@@ -5,9 +5,9 @@
 //
 // The rule (tests/mine_reference.py states it in NumPy, tests/mine_designs.py proves designed answers):
 //   * record (image, level, r, c): image and level clamped into [0, n_images) and [0, n_levels); its box is float32
-//     [c, r, c + n, r + m] * inv_scale[level] (wb_boxes_launch's arithmetic);
-//   * best / owner: match_kernel's float64 IoU over gt[gt_off[image] .. gt_off[image + 1]), first argmax; no candidates:
-//     best 0, owner -1;
+//     [c, r, c + n, r + m] * inv_scale[level] (wb_match_iou.h: window_box);
+//   * best / owner: the float64 IoU over gt[gt_off[image] .. gt_off[image + 1]), first argmax; no candidates: best 0,
+//     owner -1 (wb_match_iou.h: match_iou, match_argmax);
 //   * FP hit: best < max_fp_iou, or no candidates at all;  TP hit: candidates, best > min_tp_iou and gt_ignore[owner] == 0;
 //   * key = fmix32(((r << 16) | c) ^ g),  g = fmix32(fmix32(seed ^ fmix32(serial[image] + 0x9E3779B9)) ^ (level * 0x9E3779B1));
 //     fmix32 is a bijection and (r, c) unique inside a group, so the keys of a group never tie;
@@ -30,13 +30,8 @@
 // Nothing outside the buffers is read or written whatever the records hold: image, level and the candidate range are
 // clamped, an output row is written only below out_capacity, and the gather checks every window against its level and
 // every level against the image stride before it reads (a window that fails is written as zeros and flagged).
-#include "wb_common.h"
-#include "wb_match_iou.h"
+#include "wb_match_iou.h"   // the window's box, the IoU and its argmax, the output row, the limits of a batch
 
-#define WB_MINE_MAX_DET (1 << 26)       // most records of one call (what one scan can return)
-#define WB_MINE_MAX_IMAGES 1024
-#define WB_MINE_MAX_LEVELS 256
-#define WB_MINE_MAX_GROUPS 16384        // (image, level) groups: a group index and two hit bits share 16 bits of scratch
 #define WB_MINE_PENDING 0xFFFFFFFFFFFFFFFFull
 
 namespace {
@@ -45,13 +40,6 @@ struct MineState {       // per (group, class)
     uint32_t prefix;     // the digits fixed so far of the cap-th smallest key
     uint32_t krem;       // how many of the hits that match the prefix are still to choose
     uint64_t limit;      // chosen: key < limit;  WB_MINE_PENDING while the select runs
-};
-
-struct MineRow {         // one chosen window: 32 bytes
-    WbDet det;
-    double best;
-    int32_t owner;
-    int32_t label;
 };
 
 struct MineArgs {
@@ -86,20 +74,11 @@ __device__ inline uint32_t mine_key(const MineArgs &a, int32_t image, int32_t le
 
 // label_boxes for one record (image and level already clamped)
 __device__ inline MineMatch mine_match(const MineArgs &a, int32_t image, int32_t level, uint32_t r, uint32_t c) {
-    const float sc = a.inv_scale[level];
-    const double ax1 = (double)((float)c * sc), ay1 = (double)((float)r * sc);
-    const double ax2 = (double)((float)((int)c + a.n) * sc), ay2 = (double)((float)((int)r + a.m) * sc);
-    const double area_a = (ax2 - ax1) * (ay2 - ay1);
+    const MatchBox box = match_box(window_box(a.inv_scale[level], r, c, a.m, a.n));
     const MatchRange rg = match_range(a.gt_off, image, a.n_gt);
-    double bestv = -1.0;                                   // (an iou is never negative and never NaN: the first candidate takes it)
+    double bestv = -1.0;
     int32_t own = -1;
-    for (int64_t k = rg.lo; k < rg.hi; ++k) {
-        const double v = match_iou(ax1, ay1, ax2, ay2, area_a, a.gt[4 * k], a.gt[4 * k + 1], a.gt[4 * k + 2], a.gt[4 * k + 3]);
-        if (v > bestv) {
-            bestv = v;
-            own = (int32_t)(k - rg.lo);
-        }
-    }
+    match_argmax(bestv, own, box, a.gt, rg.lo, rg.hi, 0);
     MineMatch out;
     out.best = own < 0 ? 0.0 : bestv;
     out.owner = own;
@@ -202,18 +181,11 @@ __global__ __launch_bounds__(256) void mine_emit_kernel(const WbDet *det, int64_
     }
     const int32_t label = chosen[1] ? -1 : (chosen[0] ? 1 : 0);      // TP first, then FP: FP wins
     if (label == 0) return;
-    const uint32_t at = atomicAdd(n_rows, 1u);
-    if ((int64_t)at >= out_capacity) return;               // (the launcher refuses a capacity the rule could exceed)
+    uint32_t at;
+    if (!row_take(n_rows, out_capacity, at)) return;       // (the launcher refuses a capacity the rule could exceed)
     const WbDet d = det[i];
     const MineMatch mt = mine_match(a, mine_clamp(d.image, a.n_images), mine_clamp(d.level, a.n_levels), d.r, d.c);
-    uint4 lo, hi;
-    __builtin_memcpy(&lo, &d, 16);
-    __builtin_memcpy(&hi.x, &mt.best, 8);
-    hi.z = (uint32_t)mt.owner;
-    hi.w = (uint32_t)label;
-    uint4 *dst = reinterpret_cast<uint4 *>(rows + at);
-    dst[0] = lo;
-    dst[1] = hi;
+    row_store(rows, at, d, mt.best, mt.owner, label);
 }
 
 // crops of the chosen rows: one workgroup per row, element by element (a crop is m * n * C elements, rows of n * C contiguous
@@ -257,27 +229,13 @@ inline MineLayout mine_layout(int64_t n_det, int n_images, int n_levels) {
     return l;
 }
 
-inline int mine_sizes_ok(const char *who, int64_t n_det, int n_images, int n_levels) {
-    WB_REQUIRE(n_det >= 0 && n_images >= 0 && n_levels >= 0, "%s: n_det = %lld, n_images = %d, n_levels = %d: negative", who,
-               (long long)n_det, n_images, n_levels);
-    if (n_det > WB_MINE_MAX_DET || n_images > WB_MINE_MAX_IMAGES || n_levels > WB_MINE_MAX_LEVELS ||
-        (int64_t)n_images * n_levels > WB_MINE_MAX_GROUPS) {
-        wb_set_error("%s: %lld records, %d images, %d levels (at most %d records, %d images, %d levels, %d images * levels)", who,
-                     (long long)n_det, n_images, n_levels, WB_MINE_MAX_DET, WB_MINE_MAX_IMAGES, WB_MINE_MAX_LEVELS, WB_MINE_MAX_GROUPS);
-        return WB_ERR_UNSUPPORTED;
-    }
-    return WB_OK;
-}
-
-inline bool mine_aligned(const void *p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
-
 }  // namespace
 
-static_assert(sizeof(MineRow) == 32 && sizeof(MineState) == 16 && sizeof(WbMineLevel) == 16, "wb_mine layouts");
+static_assert(sizeof(MineState) == 16 && sizeof(WbMineLevel) == 16, "wb_mine layouts");
 
 extern "C" int wb_mine_scratch_bytes(int64_t n_det, int n_images, int n_levels, size_t *bytes) {
     WB_REQUIRE(bytes, "wb_mine_scratch_bytes: null pointer");
-    const int rc = mine_sizes_ok("wb_mine_scratch_bytes", n_det, n_images, n_levels);
+    const int rc = label_sizes_ok("wb_mine_scratch_bytes", n_det, n_images, n_levels);
     if (rc != WB_OK) return rc;
     *bytes = mine_layout(n_det, n_images, n_levels).total;
     return WB_OK;
@@ -288,7 +246,7 @@ extern "C" int wb_mine_select_launch(void *stream, const WbDet *det, int64_t n_d
                                      const uint32_t *serial, int n_images, double min_tp_iou, double max_fp_iou, int64_t max_tp,
                                      int64_t max_fp, int want_tp, int want_fp, uint32_t seed, void *scratch, size_t scratch_bytes,
                                      void *rows, int64_t out_capacity, uint32_t *n_rows) {
-    const int rc = mine_sizes_ok("wb_mine_select_launch", n_det, n_images, n_levels);
+    const int rc = label_sizes_ok("wb_mine_select_launch", n_det, n_images, n_levels);
     if (rc != WB_OK) return rc;
     WB_REQUIRE(n_gt >= 0 && max_tp >= 0 && max_fp >= 0 && out_capacity >= 0 && m >= 1 && n >= 1 && m <= 65536 && n <= 65536,
                "wb_mine_select_launch: n_gt = %lld, max_tp = %lld, max_fp = %lld, out_capacity = %lld, m = %d, n = %d", (long long)n_gt,
@@ -297,10 +255,10 @@ extern "C" int wb_mine_select_launch(void *stream, const WbDet *det, int64_t n_d
     WB_REQUIRE(det && inv_scale && gt_off && serial && scratch && rows && n_rows && ((gt && gt_ignore) || n_gt == 0),
                "wb_mine_select_launch: null pointer");
     WB_REQUIRE(n_images >= 1 && n_levels >= 1, "wb_mine_select_launch: %lld records of no image or level", (long long)n_det);
-    WB_REQUIRE(mine_aligned(det, 16) && mine_aligned(rows, 16) && mine_aligned(scratch, 16),
+    WB_REQUIRE(wb_aligned(det, 16) && wb_aligned(rows, 16) && wb_aligned(scratch, 16),
                "wb_mine_select_launch: det, rows and scratch must be 16-byte aligned");
-    WB_REQUIRE(mine_aligned(gt, 8), "wb_mine_select_launch: gt must be 8-byte aligned");
-    WB_REQUIRE(mine_aligned(inv_scale, 4) && mine_aligned(gt_off, 4) && mine_aligned(serial, 4) && mine_aligned(n_rows, 4),
+    WB_REQUIRE(wb_aligned(gt, 8), "wb_mine_select_launch: gt must be 8-byte aligned");
+    WB_REQUIRE(wb_aligned(inv_scale, 4) && wb_aligned(gt_off, 4) && wb_aligned(serial, 4) && wb_aligned(n_rows, 4),
                "wb_mine_select_launch: inv_scale, gt_off, serial and n_rows must be 4-byte aligned");
     const MineLayout l = mine_layout(n_det, n_images, n_levels);
     WB_REQUIRE(scratch_bytes >= l.total, "wb_mine_select_launch: scratch of %zu bytes, %zu needed", scratch_bytes, l.total);
@@ -345,17 +303,17 @@ extern "C" int wb_mine_gather_launch(void *stream, const void *buf, int dtype, i
         wb_set_error("wb_mine_gather_launch: dtype %d (float32 and uint8 channels have crops)", dtype);
         return WB_ERR_UNSUPPORTED;
     }
-    if (n_rows > WB_MINE_MAX_DET) {
-        wb_set_error("wb_mine_gather_launch: %lld rows (at most %d in one call)", (long long)n_rows, WB_MINE_MAX_DET);
+    if (n_rows > WB_LABEL_MAX_DET) {
+        wb_set_error("wb_mine_gather_launch: %lld rows (at most %d in one call)", (long long)n_rows, WB_LABEL_MAX_DET);
         return WB_ERR_UNSUPPORTED;
     }
     WB_REQUIRE(err, "wb_mine_gather_launch: null pointer");
-    WB_REQUIRE(mine_aligned(err, 4), "wb_mine_gather_launch: err must be 4-byte aligned");
+    WB_REQUIRE(wb_aligned(err, 4), "wb_mine_gather_launch: err must be 4-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     WB_HIP_CHECK(hipMemsetAsync(err, 0, 4, st));
     if (n_rows == 0) return WB_OK;
     WB_REQUIRE(buf && levels && rows && out, "wb_mine_gather_launch: null pointer");
-    WB_REQUIRE(mine_aligned(rows, 16) && mine_aligned(levels, 8) && (dtype == WB_DTYPE_U8 || (mine_aligned(buf, 4) && mine_aligned(out, 4))),
+    WB_REQUIRE(wb_aligned(rows, 16) && wb_aligned(levels, 8) && (dtype == WB_DTYPE_U8 || (wb_aligned(buf, 4) && wb_aligned(out, 4))),
                "wb_mine_gather_launch: rows 16-byte, levels 8-byte, float buffers 4-byte aligned");
     const dim3 grid((uint32_t)n_rows), wg(256);
     if (dtype == WB_DTYPE_F32)

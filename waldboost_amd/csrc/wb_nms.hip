@@ -415,7 +415,7 @@ extern "C" int wb_nms_finish_scratch_bytes(uint32_t out_capacity, int n_images, 
 static int nms_check_common(const char *who, double iou_threshold, const void *scratch) {
     WB_REQUIRE(iou_threshold == iou_threshold && iou_threshold >= 0.0, "%s: iou_threshold must be a number >= 0", who);
     WB_REQUIRE(scratch != nullptr, "%s: null pointer", who);
-    WB_REQUIRE(reinterpret_cast<uintptr_t>(scratch) % 16 == 0, "%s: scratch must be 16-byte aligned", who);
+    WB_REQUIRE(wb_aligned(scratch, 16), "%s: scratch must be 16-byte aligned", who);
     return WB_OK;
 }
 
@@ -425,9 +425,9 @@ static int nms_plain(const char *who, void *stream, const float *boxes, const fl
     WB_REQUIRE(n >= 0, "%s: n = %lld is negative", who, (long long)n);
     if (int rc = nms_check_common(who, iou_threshold, scratch)) return rc;
     WB_REQUIRE(n_keep != nullptr && (n == 0 || (boxes && scores && keep && (visit || !ordered))), "%s: null pointer", who);
-    WB_REQUIRE(reinterpret_cast<uintptr_t>(boxes) % 16 == 0, "%s: boxes must be 16-byte aligned", who);
-    WB_REQUIRE(reinterpret_cast<uintptr_t>(scores) % 4 == 0 && reinterpret_cast<uintptr_t>(group) % 4 == 0 &&
-                   reinterpret_cast<uintptr_t>(n_keep) % 4 == 0 && reinterpret_cast<uintptr_t>(visit) % 4 == 0,
+    WB_REQUIRE(wb_aligned(boxes, 16), "%s: boxes must be 16-byte aligned", who);
+    WB_REQUIRE(wb_aligned(scores, 4) && wb_aligned(group, 4) &&
+                   wb_aligned(n_keep, 4) && wb_aligned(visit, 4),
                "%s: scores, group, order and n_keep must be 4-byte aligned", who);
     WB_REQUIRE(!use_score_threshold || score_threshold == score_threshold, "%s: score_threshold is NaN", who);
     if (n > n_most) {
@@ -477,7 +477,7 @@ extern "C" int wb_nms_finish_launch(void *stream, const void *fin, uint32_t out_
                                     void *result) {
     if (int rc = nms_check_common("wb_nms_finish_launch", iou_threshold, scratch)) return rc;
     WB_REQUIRE(fin != nullptr && result != nullptr, "wb_nms_finish_launch: null pointer");
-    WB_REQUIRE(reinterpret_cast<uintptr_t>(fin) % 16 == 0 && reinterpret_cast<uintptr_t>(result) % 4 == 0,
+    WB_REQUIRE(wb_aligned(fin, 16) && wb_aligned(result, 4),
                "wb_nms_finish_launch: fin must be 16-byte, result 4-byte aligned");
     WB_REQUIRE(n_images >= 1 && n_images <= 65535, "wb_nms_finish_launch: 1 .. 65535 images");
     WB_REQUIRE(out_capacity >= 4 && out_capacity % 4 == 0 && out_capacity <= (1u << 26),

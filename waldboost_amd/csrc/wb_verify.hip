@@ -259,10 +259,10 @@ extern "C" int wb_verify_launch(void *stream, const void *X, int x_dtype, int64_
         return WB_ERR_UNSUPPORTED;
     }
     WB_REQUIRE(X && weights && scores_in && scratch && out, "wb_verify_launch: null pointer");
-    WB_REQUIRE(x_dtype == WB_DTYPE_U8 || reinterpret_cast<uintptr_t>(X) % 4 == 0, "wb_verify_launch: float32 crops must be 4-byte aligned");
-    WB_REQUIRE(reinterpret_cast<uintptr_t>(weights) % 16 == 0 && reinterpret_cast<uintptr_t>(scratch) % 16 == 0,
+    WB_REQUIRE(x_dtype == WB_DTYPE_U8 || wb_aligned(X, 4), "wb_verify_launch: float32 crops must be 4-byte aligned");
+    WB_REQUIRE(wb_aligned(weights, 16) && wb_aligned(scratch, 16),
                "wb_verify_launch: weights and scratch must be 16-byte aligned");
-    WB_REQUIRE(reinterpret_cast<uintptr_t>(scores_in) % 4 == 0 && reinterpret_cast<uintptr_t>(out) % 4 == 0,
+    WB_REQUIRE(wb_aligned(scores_in, 4) && wb_aligned(out, 4),
                "wb_verify_launch: scores_in and out must be 4-byte aligned");
     const size_t need = (size_t)n_windows * (size_t)L.F * sizeof(float);
     WB_REQUIRE(scratch_bytes >= need, "wb_verify_launch: scratch of %zu bytes, %zu needed (wb_verify_scratch_bytes)", scratch_bytes,

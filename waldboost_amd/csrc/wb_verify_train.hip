@@ -594,11 +594,10 @@ extern "C" int wb_verify_train_step(void *stream, const void *X, int x_dtype, co
     if (rc != WB_OK) return rc;
     WB_REQUIRE(n_pool >= 1 && n_pool <= INT32_MAX, "%s: a pool of %lld windows", who, (long long)n_pool);
     WB_REQUIRE(X && H && Y && idx && params && adam_m && adam_v && t && hyper && scratch && loss_out, "%s: null pointer", who);
-    auto aligned = [](const void *p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; };
-    WB_REQUIRE(x_dtype == WB_DTYPE_U8 || aligned(X, 4), "%s: float32 crops must be 4-byte aligned", who);
-    WB_REQUIRE(aligned(params, 16) && aligned(adam_m, 16) && aligned(adam_v, 16) && aligned(scratch, 16),
+    WB_REQUIRE(x_dtype == WB_DTYPE_U8 || wb_aligned(X, 4), "%s: float32 crops must be 4-byte aligned", who);
+    WB_REQUIRE(wb_aligned(params, 16) && wb_aligned(adam_m, 16) && wb_aligned(adam_v, 16) && wb_aligned(scratch, 16),
                "%s: params, adam_m, adam_v and scratch must be 16-byte aligned", who);
-    WB_REQUIRE(aligned(H, 4) && aligned(Y, 4) && aligned(idx, 4) && aligned(t, 4) && aligned(loss_out, 4) && aligned(grads_out, 4),
+    WB_REQUIRE(wb_aligned(H, 4) && wb_aligned(Y, 4) && wb_aligned(idx, 4) && wb_aligned(t, 4) && wb_aligned(loss_out, 4) && wb_aligned(grads_out, 4),
                "%s: H, Y, idx, t, loss_out and grads_out must be 4-byte aligned", who);
     const WbVerifyTrainHyper &hy = *hyper;
     WB_REQUIRE(hy.lr >= 0.0 && hy.lr < 1e30 && hy.beta1 >= 0.0 && hy.beta1 < 1.0 && hy.beta2 >= 0.0 && hy.beta2 < 1.0 &&

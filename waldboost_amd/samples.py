@@ -292,6 +292,85 @@ def order_rows(rows):
     return _engine.sort_records(rows)
 
 
+def level_table(eng):
+    """The pyramid levels of an engine as wb_mine_gather_launch's table (nat.MINE_LEVEL_DTYPE [L])."""
+    table = np.zeros(eng.plan.n_levels, nat.MINE_LEVEL_DTYPE)
+    for k in ("chn_off", "u", "v"):
+        table[k] = eng.level_np[k]
+    return table
+
+
+class LabelledBatch:
+    """What mine_batch and calibration.instance_windows share around their labelling call: a batch `images` [B, H, W] (or
+    one [H, W]) with the ground truth of every image (a list of B Boxes / None; for one image the Boxes itself), checked
+    (`who` names the caller in the messages), and its engine.  Attributes: images [B, H, W], B, gt / gt_off / ignore
+    (_ground_truth_arrays), m, n, C (the model's window), dev, eng, L (pyramid levels; 0: nothing to run) and, after
+    run_channels, table (level_table) and inv (float32 1 / scale); after upload, ptr (the device pointers by name)."""
+
+    def __init__(self, model, images, gt_boxes_per_image, who):
+        from . import channels as _channels
+        from . import engine as _engine
+        if getattr(images, "ndim", None) == 2:
+            images = images[None]
+            gts = list(gt_boxes_per_image) if isinstance(gt_boxes_per_image, (list, tuple)) else [gt_boxes_per_image]
+        elif getattr(images, "ndim", None) == 3:
+            gts = list(gt_boxes_per_image)
+        else:
+            raise ValueError("images must have 3 dimensions [B,H,W] (or 2: one image)")
+        B, H, W = (int(x) for x in images.shape)
+        if len(gts) != B:
+            raise ValueError(f"{who}: {B} images, ground truth of {len(gts)}")
+        self.images, self.B = images, B
+        self.gt, self.gt_off, self.ignore = _ground_truth_arrays(gts)
+        shrink, n_per_oct, smooth, spec = _channels.read_opts(model.channel_opts)
+        self.m, self.n, self.C = (int(x) for x in model.shape)
+        assert self.C == spec.n_channels, f"Invalid number of channels. Expected {self.C} given {spec.n_channels}."
+        self.dev = nat.require_gpu()
+        self.eng = _engine.get_engine(H, W, _engine.array_dtype(images), shrink, n_per_oct, smooth, B, channels=spec)
+        self.L = self.eng.plan.n_levels
+
+    def run_channels(self):
+        """The pyramid of the batch, where it stays; the level table and 1 / scale on the host."""
+        self.eng.load_images(self.images)
+        self.eng.run_channels()
+        self.table = level_table(self.eng)
+        self.inv = np.ascontiguousarray(self.eng.inv_scales(), np.float32)
+
+    def upload(self, **more):
+        """The one upload: gt | table | gt_off | `more` (the caller's own 4-byte arrays) | inv_scale | ignore (the doubles
+        first: all aligned), as ptr[name]."""
+        import ctypes as C
+        import torch
+        assert hasattr(self, "table"), "LabelledBatch.upload comes after run_channels"
+        parts = dict(gt=self.gt.reshape(-1), table=self.table, gt_off=self.gt_off, **more, inv_scale=self.inv, ignore=self.ignore)
+        offs = np.cumsum([0] + [p.nbytes for p in parts.values()])
+        self.blob = torch.from_numpy(np.concatenate([p.view(np.uint8) for p in parts.values()])).to(self.dev)
+        self.ptr = {k: C.c_void_p(self.blob.data_ptr() + int(o)) for k, o in zip(parts, offs)}
+
+    def mined(self, rows):
+        """The labelled rows (device int32 [N, 8], N >= 1) as a MinedSamples in (image, level, r, c) order -- order_rows,
+        the crops (wb_mine_gather_launch), the boxes (wb_boxes_launch) -- and the gather's error word, a device tensor
+        that is not waited for here: non-zero when a window lies outside its pyramid level."""
+        import torch
+        assert hasattr(self, "ptr"), "LabelledBatch.mined comes after run_channels and upload"
+        eng, lib, m, n, dev = self.eng, self.eng.lib, self.m, self.n, self.dev
+        N = int(rows.shape[0])
+        rows = order_rows(rows)
+        crops = torch.empty((N, m, n, self.C), dtype=eng.chn.dtype, device=dev)
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+        nat.check(lib.wb_mine_gather_launch(nat.stream_ptr(), nat.ptr(eng.chn), eng.spec.wb_dtype, eng.chn_stride, self.B, self.ptr["table"],
+                                            self.L, self.C, nat.ptr(rows), N, m, n, nat.ptr(crops), nat.ptr(err)), "wb_mine_gather_launch")
+        det = rows[:, :4].contiguous()
+        boxes = torch.empty((N, 4), dtype=torch.float32, device=dev)
+        scores = torch.empty(N, dtype=torch.float32, device=dev)
+        nat.check(lib.wb_boxes_launch(nat.stream_ptr(), nat.ptr(det), N, self.ptr["inv_scale"], m, n, nat.ptr(boxes), nat.ptr(scores)),
+                  "wb_boxes_launch")
+        rc = rows[:, 2]
+        return MinedSamples(samples=crops, scores=scores, tp_label=rows[:, 7].clone(), instance_id=rows[:, 6].clone(),
+                            image=rows[:, 0].clone(), level=rows[:, 1].clone(), row=rc & 0xFFFF, col=(rc >> 16) & 0xFFFF, boxes=boxes,
+                            best=rows[:, 4:6].contiguous().view(torch.float64).reshape(-1)), err
+
+
 def mine_batch(model, images, gt_boxes_per_image, tp=True, fp=True, min_tp_iou=0.7, max_fp_iou=0.3, max_tp_candidates=100,
                max_fp_candidates=100, seed=0, serial0=0):
     """get_samples_from_image for a batch, on the device: `images` [B, H, W] (or one [H, W]; what the engine accepts) go
@@ -315,40 +394,21 @@ def mine_batch(model, images, gt_boxes_per_image, tp=True, fp=True, min_tp_iou=0
     replacement and depends on (seed, serial, level, r, c) alone -- not on the batch an image sits in, the order of the
     scan's records or the run.
 
-    Host traffic: one upload (ground truth, offsets, flags, serials, level table), four waits (the scan's counters
-    twice as in every scan, the number of chosen rows with the scan statistics, the gather's error word); neither
+    Host traffic: one upload (ground truth, offsets, flags, serials, level table, 1 / scale), four waits (the scan's
+    counters twice as in every scan, the number of chosen rows with the scan statistics, the gather's error word); neither
     records, pyramid nor crops leave the device.  Images too small for any level, or no detections: an empty result
     without a mining launch."""
     import ctypes as C
     import torch
-    from . import channels as _channels
     from . import engine as _engine
-    single = getattr(images, "ndim", None) == 2
-    if single:
-        images = images[None]
-        gts = list(gt_boxes_per_image) if isinstance(gt_boxes_per_image, (list, tuple)) else [gt_boxes_per_image]
-    elif getattr(images, "ndim", None) == 3:
-        gts = list(gt_boxes_per_image)
-    else:
-        raise ValueError("images must have 3 dimensions [B,H,W] (or 2: one image)")
-    B, H, W = (int(x) for x in images.shape)
-    if len(gts) != B:
-        raise ValueError(f"mine_batch: {B} images, ground truth of {len(gts)}")
+    b = LabelledBatch(model, images, gt_boxes_per_image, "mine_batch")
     if max_tp_candidates < 0 or max_fp_candidates < 0:
         raise ValueError("max_tp_candidates and max_fp_candidates must not be negative")
-    gt, gt_off, ignore = _ground_truth_arrays(gts)
-    shrink, n_per_oct, smooth, spec = _channels.read_opts(model.channel_opts)
-    m, n, Cc = (int(x) for x in model.shape)
-    assert Cc == spec.n_channels, f"Invalid number of channels. Expected {Cc} given {spec.n_channels}."
-    dev = nat.require_gpu()
-    eng = _engine.get_engine(H, W, _engine.array_dtype(images), shrink, n_per_oct, smooth, B, channels=spec)
+    B, L, m, n, dev, eng = b.B, b.L, b.m, b.n, b.dev, b.eng
     chn_dtype = eng.chn.dtype
-    L = eng.plan.n_levels
     if L == 0:
         return _empty_mined(model.shape, chn_dtype, dev)
-    lib = eng.lib
-    eng.load_images(images)
-    eng.run_channels()
+    b.run_channels()
     dm = model.device_cascade()
     stt = eng.run_cascade(dm)                              # float / uint8 channels, not rank bytes
     total = eng.ensure_capacity(dm)                        # (grows the buffer and scans again when a shard overflowed)
@@ -358,49 +418,60 @@ def mine_batch(model, images, gt_boxes_per_image, tp=True, fp=True, min_tp_iou=0
         model.n_weak += int(_engine.alive_host(stt.alive, T).sum())
         return _empty_mined(model.shape, chn_dtype, dev)
     recs = eng.pack()[1:1 + total]                         # the valid records, shard order
-    # one upload: ground truth | level table | offsets | serials | 1 / scale | ignore flags (the doubles first: all aligned)
-    table = np.zeros(L, nat.MINE_LEVEL_DTYPE)
-    for k in ("chn_off", "u", "v"):
-        table[k] = eng.level_np[k]
-    serial = ((int(serial0) + np.arange(B, dtype=np.int64)) & 0xFFFFFFFF).astype(np.uint32)
-    parts = [gt.reshape(-1).view(np.uint8), table.view(np.uint8), gt_off.view(np.uint8), serial.view(np.uint8),
-             eng.inv_scales().view(np.uint8), ignore]
-    offs = np.concatenate([[0], np.cumsum([p.size for p in parts])])
-    blob = torch.from_numpy(np.concatenate(parts)).to(dev)
-    at = lambda k: C.c_void_p(blob.data_ptr() + int(offs[k]))
+    b.upload(serial=((int(serial0) + np.arange(B, dtype=np.int64)) & 0xFFFFFFFF).astype(np.uint32))
     k_tp = min(int(max_tp_candidates), total) if tp else 0
     k_fp = min(int(max_fp_candidates), total) if fp else 0
     room = min(total, B * L * (k_tp + k_fp))
     need = C.c_size_t()
-    nat.check(lib.wb_mine_scratch_bytes(total, B, L, C.byref(need)), "wb_mine_scratch_bytes")
+    nat.check(eng.lib.wb_mine_scratch_bytes(total, B, L, C.byref(need)), "wb_mine_scratch_bytes")
     scratch = torch.empty(need.value, dtype=torch.uint8, device=dev)
     rows = torch.empty((max(room, 1), 8), dtype=torch.int32, device=dev)
     n_rows = torch.zeros(1, dtype=torch.int32, device=dev)
-    nat.check(lib.wb_mine_select_launch(nat.stream_ptr(), nat.ptr(recs), total, at(4), L, m, n, at(0), at(2), at(5), gt.shape[0], at(3),
-                                        B, float(min_tp_iou), float(max_fp_iou), int(max_tp_candidates), int(max_fp_candidates),
-                                        int(bool(tp)), int(bool(fp)), int(seed) & 0xFFFFFFFF, nat.ptr(scratch), scratch.numel(),
-                                        nat.ptr(rows), room, nat.ptr(n_rows)), "wb_mine_select_launch")
+    nat.check(eng.lib.wb_mine_select_launch(nat.stream_ptr(), nat.ptr(recs), total, b.ptr["inv_scale"], L, m, n, b.ptr["gt"], b.ptr["gt_off"],
+                                            b.ptr["ignore"], b.gt.shape[0], b.ptr["serial"], B, float(min_tp_iou), float(max_fp_iou),
+                                            int(max_tp_candidates), int(max_fp_candidates), int(bool(tp)), int(bool(fp)),
+                                            int(seed) & 0xFFFFFFFF, nat.ptr(scratch), scratch.numel(), nat.ptr(rows), room, nat.ptr(n_rows)),
+              "wb_mine_select_launch")
     h = torch.cat([n_rows, stt.alive.reshape(-1)]).cpu().numpy()      # one wait: the chosen rows' number and the statistics
     N = int(h[0])
     model.n_weak += int(h[1:].reshape(stt.alive.shape)[:, :, :T].astype(np.int64).sum())
     if N == 0:
         return _empty_mined(model.shape, chn_dtype, dev)
     assert N <= room
-    rows = order_rows(rows[:N])
-    crops = torch.empty((N, m, n, Cc), dtype=chn_dtype, device=dev)
-    err = torch.zeros(1, dtype=torch.int32, device=dev)
-    nat.check(lib.wb_mine_gather_launch(nat.stream_ptr(), nat.ptr(eng.chn), eng.spec.wb_dtype, eng.chn_stride, B, at(1), L, Cc,
-                                        nat.ptr(rows), N, m, n, nat.ptr(crops), nat.ptr(err)), "wb_mine_gather_launch")
-    det = rows[:, :4].contiguous()
-    boxes = torch.empty((N, 4), dtype=torch.float32, device=dev)
-    scores = torch.empty(N, dtype=torch.float32, device=dev)
-    nat.check(lib.wb_boxes_launch(nat.stream_ptr(), nat.ptr(det), N, at(4), m, n, nat.ptr(boxes), nat.ptr(scores)), "wb_boxes_launch")
+    got, err = b.mined(rows[:N])
     if int(err.item()):
         raise RuntimeError("mine_batch: a chosen window lies outside its pyramid level (the records do not belong to this pyramid)")
-    rc = rows[:, 2]
-    return MinedSamples(samples=crops, scores=scores, tp_label=rows[:, 7].clone(), instance_id=rows[:, 6].clone(),
-                        image=rows[:, 0].clone(), level=rows[:, 1].clone(), row=rc & 0xFFFF, col=(rc >> 16) & 0xFFFF, boxes=boxes,
-                        best=rows[:, 4:6].contiguous().view(torch.float64).reshape(-1))
+    return got
+
+
+def image_batches(iterable, batch):
+    """The items of `iterable` (dicts with 'image') as lists of at most `batch` consecutive items whose images have one
+    (shape, dtype), in order.  A list is yielded as soon as it is full, before the next item is read; an item of another
+    kind is read, and then what waits goes first; the remainder comes at the end.  So a caller that stops after a list
+    has taken from its iterator exactly the items of the lists it saw -- and the one item whose kind ended the last."""
+    group, kind = [], None
+    for item in iterable:
+        image = item["image"]
+        its = (tuple(image.shape), str(image.dtype))
+        if group and its != kind:                          # a shape change: what waits goes first
+            yield group
+            group = []
+        kind = its
+        group.append(item)
+        if len(group) == batch:
+            yield group
+            group = []
+    if group:
+        yield group
+
+
+def stack_images(items):
+    """The images of one of image_batches' lists as one [B, H, W] array (ndarrays) or tensor."""
+    first = items[0]["image"]
+    if isinstance(first, np.ndarray):
+        return np.stack([it["image"] for it in items])
+    import torch
+    return torch.stack([it["image"] for it in items])
 
 
 class DeviceSamplePool(object):
@@ -458,10 +529,7 @@ class DeviceSamplePool(object):
 
     def _mine(self, model, items, missing):
         """Mine one batch of items; the new samples (or None)."""
-        import torch
-        first = items[0]["image"]
-        stack = np.stack if isinstance(first, np.ndarray) else torch.stack
-        got = mine_batch(model, stack([it["image"] for it in items]), [it["groundtruth_boxes"] for it in items],
+        got = mine_batch(model, stack_images(items), [it["groundtruth_boxes"] for it in items],
                          tp=missing[SampleLabel.TRUE_POSITIVE] > 0, fp=missing[SampleLabel.FALSE_POSITIVE] > 0, seed=self.seed,
                          serial0=self.images_seen, **self.label_boxes_args)
         if len(got):
@@ -481,34 +549,15 @@ class DeviceSamplePool(object):
         self.logger.log(15, f"Pool needs tp: {missing[SampleLabel.TRUE_POSITIVE]}, fp: {missing[SampleLabel.FALSE_POSITIVE]}")
         if not any(missing.values()):
             return
-        fresh, group, kind = [], [], None
-
-        def flush():
-            """Mine the waiting group; True once both quotas are filled."""
+        fresh = []
+        for group in image_batches(iterable, self.batch):
             got = self._mine(model, group, missing)
-            group.clear()
             if got is not None:
                 for lab, cnt in self._counts(got.tp_label).items():
                     missing[lab] -= cnt
                 fresh.append(got)
-            return all(v <= 0 for v in missing.values())
-
-        done = False
-        for item in iterable:
-            image = item["image"]
-            its = (tuple(image.shape), str(image.dtype))
-            if group and its != kind:                      # a shape change: what waits goes first
-                done = flush()
-                if done:
-                    break
-            kind = its
-            group.append(item)
-            if len(group) == self.batch:
-                done = flush()
-                if done:
-                    break
-        if group and not done:
-            flush()
+            if all(v <= 0 for v in missing.values()):
+                break
         if fresh:
             self.samples = MinedSamples.cat(([self.samples] if self.samples is not None else []) + fresh)
 
