@@ -575,12 +575,16 @@ def test_multi_model_detect_rescans_only_the_cascade_whose_results_did_not_fit(m
 
 
 # ------------------------------------------------------------------------------ batches / configs
-@pytest.mark.parametrize("ordered_on_device", [True, False])
-def test_detect_batch_equals_per_image_detect(ordered_on_device, monkeypatch):
-    """ordered_on_device: the batch's results split by image and ordered by wb_det_order_batch_launch (one read-back);
-    False: the form it falls back to (device sort of all records, wb_boxes_launch)."""
+@pytest.mark.parametrize("post", ["ordered", "host", "device"])
+def test_detect_batch_equals_per_image_detect(post, monkeypatch):
+    """post: where the batch's results are put in order -- "ordered": split by image and ordered by
+    wb_det_order_batch_launch (one read-back); the forms it falls back to: "host" (few detections: from the packed
+    read-back) and "device" (device sort of all records, wb_boxes_launch)."""
     import waldboost_amd.model as wm
-    monkeypatch.setattr(wm, "_ORDER_BATCH", ordered_on_device)
+    if post != "ordered":
+        monkeypatch.setattr(wm, "_ORDER_BATCH", False)
+    if post == "device":
+        monkeypatch.setattr(wm, "_HOST_POST_BATCH", 0)
     imgs = np.stack([synth_image(210, 290, 600 + b) for b in range(5)])
     M = random_model(42, 30, 2)
     per = []

@@ -247,6 +247,47 @@ def test_stream_with_more_detections_than_one_read_back_holds(batch, monkeypatch
         E._ENGINES.clear()
 
 
+def test_one_image_ordered_on_the_device_when_one_read_back_does_not_hold_it(monkeypatch):
+    """Model.detect_raw on ONE image with more detections than its one-copy read-back holds and the host's ordering
+    switched off: the packed records stay on the device for a sort and wb_boxes_launch.  Bit for bit the oracle's result;
+    with an iou_threshold, non_max_suppression of that result."""
+    from waldboost_amd import engine as E
+    import waldboost_amd.model as wm
+    E._ENGINES.clear()
+    monkeypatch.setattr(E.PyramidEngine, "_FETCH_ROWS", 64)
+    monkeypatch.setattr(wm, "_HOST_POST_MAX", 0)
+    real, calls = E.sort_records, []
+    monkeypatch.setattr(E, "sort_records", lambda d: (calls.append(int(d.shape[0])), real(d))[1])
+    try:
+        M = load()
+        ims = [synth_image(240, 320, 950 + i) for i in range(7)]
+        refs = [oracle_detect(M, im) for im in ims]
+        assert max(r["scores"].size for r in refs) > 64
+        for i, (im, ref) in enumerate(zip(ims, refs)):
+            n0 = len(calls)
+            res = M.detect_raw(im)
+            # (every record in one device sort: the route was taken)
+            assert ref["scores"].size <= 64 or ref["scores"].size in calls[n0:], f"image {i}"
+            for k in ("level", "r", "c", "alive"):
+                assert np.array_equal(res[k], ref[k]), f"image {i}: {k}"
+            for k in ("boxes", "scores"):
+                assert np.array_equal(res[k].view(np.uint32), ref[k].view(np.uint32)), f"image {i}: {k}"
+            plain = wb.Boxes(res["boxes"])
+            for k in ("scores", "level", "r", "c"):
+                plain.set_field(k, res[k])
+            want = wb.non_max_suppression(plain, 0.3)
+            n0 = len(calls)
+            got = M.detect_raw(im, _nms=(0.3, None))
+            assert ref["scores"].size <= 64 or ref["scores"].size in calls[n0:], f"image {i}"
+            assert np.array_equal(got["boxes"].view(np.uint32), want.get().view(np.uint32)), f"image {i}"
+            assert np.array_equal(got["scores"].view(np.uint32), want.get_field("scores").view(np.uint32)), f"image {i}"
+            for k in ("level", "r", "c"):
+                assert np.array_equal(got[k], want.get_field(k)), f"image {i}: {k}"
+            assert np.array_equal(got["alive"], ref["alive"])
+    finally:
+        E._ENGINES.clear()
+
+
 def test_detect_takes_page_locked_arrays_and_torch_tensors():
     """An extension of the reference's host-ndarray input (model.py:149): page-locked arrays are uploaded asynchronously,
     torch tensors (host, page-locked, device) are taken as they are -- same Boxes as from a plain ndarray."""

@@ -5,8 +5,8 @@ import pytest
 
 import waldboost_amd as wb
 from waldboost_amd import _native as nat
-from waldboost_amd.readback import (FinishBlock, Finished, ImageResult, Packed, host_boxes, key_fits, key_positions,
-                                    split_keys)
+from waldboost_amd.readback import (Detections, FinishBlock, Finished, ImageResult, Packed, from_finished, from_image_result,
+                                    from_ordered, from_packed, host_boxes, key_fits, key_positions, split_keys)
 
 
 @pytest.mark.parametrize("rows", [4, 64, 4096])
@@ -101,3 +101,131 @@ def test_result_tuples_have_their_fields():
     assert Finished._fields == ("keys", "boxes", "scores", "alive", "ordered", "keep")
     assert ImageResult._fields == ("keys", "boxes", "scores", "keep")
     assert Packed._fields == ("total", "records", "alive")
+
+
+# ------------------------------------------------------------------------------ one result type, one converter per form
+WIN = (13, 9)
+INV = np.array([np.float32(1.0 / s) for s in SCALES], np.float32)
+
+
+def designed(counts, seed, stale=0):
+    """Per image of `counts` that many detections at distinct windows over 3 levels, as the reference orders them:
+    [(level, r, c, boxes, scores, keep)], the boxes by Model.get_boxes; and WbDet records of all of them in a shuffled
+    order, with `stale` more that belong to the slot behind the last image."""
+    rng = np.random.default_rng(seed)
+    M = wb.Model(WIN + (4,), {})
+    want, recs = [], []
+    for b, k in enumerate(list(counts) + [stale]):
+        cells = np.sort(rng.choice(3 * 40 * 50, k, replace=False))
+        level, r, c = (cells // 2000).astype(np.int32), (cells // 50 % 40).astype(np.int64), (cells % 50).astype(np.int64)
+        scores = rng.standard_normal(k).astype(np.float32)
+        d = np.zeros(k, nat.DET_DTYPE)
+        d["image"], d["level"], d["r"], d["c"], d["score"] = b, level, r, c, scores
+        recs.append(d)
+        if b < len(counts):
+            boxes = [M.get_boxes(r[level == lv], c[level == lv], SCALES[lv]).get() for lv in range(3)]
+            want.append((level, r, c, np.concatenate(boxes).astype(np.float32), scores, rng.random(k) < 0.5))
+    recs = np.concatenate(recs)
+    return want, recs[rng.permutation(recs.size)]
+
+
+def keys_of(level, r, c, pos):
+    return (level.astype(np.uint64) << np.uint64(54) | r.astype(np.uint64) << np.uint64(40) | c.astype(np.uint64) << np.uint64(26)
+            | pos.astype(np.uint64))
+
+
+def block(w, rows, pos):
+    """One image's finish-block sections of `rows` rows with detection i at row pos[i] (stale values elsewhere):
+    (keys by detection, boxes, scores, keep by row)."""
+    level, r, c, boxes, scores, keep = w
+    bx, sc, kp = np.full((rows, 4), -7.0, np.float32), np.full(rows, -7.0, np.float32), np.zeros(rows, bool)
+    bx[pos], sc[pos], kp[pos] = boxes, scores, keep
+    return keys_of(level, r, c, pos), bx, sc, kp
+
+
+def forms(want, recs, seed):
+    """name -> (convert() -> [Detections per image], the arrays it reads, whether it carries keep flags)."""
+    rng = np.random.default_rng(seed)
+    count, m, n = len(want), *WIN
+    out = {}
+    if count == 1:
+        k = want[0][0].size
+        alive = np.zeros((1, 3, 2), np.int64)
+        keys, bx, sc, kp = block(want[0], k + 5, np.arange(k))
+        out["finished_ordered"] = (lambda: [from_finished(Finished(keys, bx, sc, alive, True, kp[:k]))], [keys, bx, sc, kp], True)
+        pos = rng.permutation(k + 5)[:k]
+        ukeys, ubx, usc, ukp = block(want[0], k + 5, pos)
+        mix = rng.permutation(k)
+        ukeys = ukeys[mix]
+        assert k < 2 or (not np.array_equal(pos, np.arange(k)) and not np.array_equal(ukeys, np.sort(ukeys)))
+        out["finished_unordered"] = (lambda: [from_finished(Finished(ukeys, ubx, usc, alive, False, ukp))], [ukeys, ubx, usc, ukp], True)
+    blocks = [block(w, w[0].size + 3, np.arange(w[0].size)) for w in want]
+    out["image_results"] = (lambda: [from_image_result(ImageResult(ks, bx[:ks.size], sc[:ks.size], kp[:ks.size])) for ks, bx, sc, kp in blocks],
+                            [a for blk in blocks for a in blk], True)
+    rows = recs.view(np.int32).reshape(-1, 4).copy()
+    out["packed"] = (lambda: from_packed(rows, count, m, n, INV), [rows], False)
+    if count == 1 and recs.size == want[0][0].size:          # (no other slot's records: what a one-image engine packs)
+        rows1 = rows.copy()
+        out["packed_one_slot"] = (lambda: from_packed(rows1, 1, m, n, INV, one_slot=True), [rows1], False)
+    image, level, r, c, boxes, scores = host_boxes(recs, m, n, INV, with_image=True)     # (its order and boxes: tested above)
+    srt = np.zeros(recs.size, nat.DET_DTYPE)
+    srt["image"], srt["level"], srt["r"], srt["c"], srt["score"] = image, level, r, c, scores
+    srt = srt.view(np.int32).reshape(-1, 4)
+    out["device_ordered"] = (lambda: from_ordered(srt, boxes, scores, count), [srt], False)
+    return out
+
+
+def same(got, w, with_keep):
+    level, r, c = got.windows()
+    assert [a.dtype for a in (got.boxes, got.scores, level, r, c)] == [np.float32, np.float32, np.int32, np.int64, np.int64]
+    assert got.boxes.shape == (w[0].size, 4) and got.scores.shape == level.shape == r.shape == c.shape == (w[0].size,)
+    assert np.array_equal(level, w[0]) and np.array_equal(r, w[1]) and np.array_equal(c, w[2])
+    assert np.array_equal(got.boxes.view(np.uint32), w[3].view(np.uint32))
+    assert np.array_equal(got.scores.view(np.uint32), w[4].view(np.uint32))
+    if with_keep:
+        assert got.keep.dtype == bool and np.array_equal(got.keep, w[5])
+    else:
+        assert got.keep is None
+
+
+@pytest.mark.parametrize("counts,stale", [((0,), 0), ((1,), 0), ((200,), 0), ((200,), 30), ((40, 0, 60), 0), ((40, 0, 60), 25),
+                                          ((0, 0, 0), 7)])
+def test_every_read_back_form_gives_the_same_detections_and_owns_them(counts, stale):
+    want, recs = designed(counts, 31 + sum(counts) + stale, stale)
+    assert recs.size == sum(counts) + stale
+    fs = forms(want, recs, 77)
+    assert set(fs) == ({"image_results", "packed", "device_ordered"} | ({"finished_ordered", "finished_unordered"} if len(counts) == 1 else set())
+                       | ({"packed_one_slot"} if len(counts) == 1 and not stale else set()))
+    for name, (convert, sources, with_keep) in fs.items():
+        got = convert()
+        assert len(got) == len(counts) and all(isinstance(g, Detections) for g in got), name
+        for g, w in zip(got, want):
+            same(g, w, with_keep)
+        # the results are the caller's own: the read-back buffers are written again by the next scan
+        for g in got:
+            for a in (g.boxes, g.scores, g.keep, g._keys) + (g._windows or ()):
+                assert a is None or not any(np.shares_memory(a, s) for s in sources), name
+        for s in sources:
+            s.view(np.uint8)[...] = 0xA5
+        for g, w in zip(got, want):
+            same(g, w, with_keep)
+
+
+def test_windows_are_split_on_demand_and_taken_rows_follow():
+    (w,), recs = designed((50,), 3)
+    keys, bx, sc, kp = block(w, 50, np.arange(50))
+    got = from_finished(Finished(keys, bx, sc, np.zeros((1, 3, 2), np.int64), True, kp[:50]))
+    assert got._windows is None                           # (Model.detect never pays for them)
+    at = np.flatnonzero(w[5])
+    for part in (got.take(at), (got.windows(), got.take(at))[1]):      # before and after the split
+        same(part, tuple(a[at] for a in w), False)
+    # a caller that wants boxes and scores alone does not even have the keys copied
+    fin = Finished(keys, bx, sc, np.zeros((1, 3, 2), np.int64), True, kp[:50])
+    for bare in (from_finished(fin, windows=False), from_finished(fin._replace(ordered=False), windows=False),
+                 from_image_result(ImageResult(keys, bx, sc, kp[:50]), windows=False)):
+        assert bare._keys is None and np.array_equal(bare.boxes, w[3]) and np.array_equal(bare.scores, w[4])
+        assert np.array_equal(bare.take(at).scores, w[4][at])
+        with pytest.raises(ValueError):
+            bare.windows()
+    none = Detections.none()
+    same(none, tuple(a[:0] for a in w), False)

@@ -69,7 +69,7 @@ def detect(image, *models, channel_opts=None, response_scale=None, iou_threshold
     if fins is not None:
         # (None in a model's place: its results did not fit this time -- that cascade alone is scanned again, on the pyramid
         # the call left resident)
-        res = [m._collect(eng, d, eng._casc_state(d), True, fin) if fin is not None else None for m, d, fin in zip(models, dms, fins)]
+        res = [m._scan_result(eng, d, eng._casc_state(d), finished=fin) if fin is not None else None for m, d, fin in zip(models, dms, fins)]
         res = [r if r is not None else m.scan_engine(eng, view=v) for r, m, v in zip(res, models, views)]
     else:
         if group is not None:

@@ -425,7 +425,7 @@ class ScanState:
     step: CapturedStep = None        # batch_enqueue's captured step             } PyramidEngine._buffers_moved
     detect_calls: int = 0
     batch_calls: int = 0
-    n_loc: int = None                # plan.n_loc of the cascade's window (Model._collect)
+    n_loc: int = None                # plan.n_loc of the cascade's window (Model._assemble)
     final: FinalBuffers = None
     nms: NmsBuffers = None
 
@@ -1328,6 +1328,13 @@ class PyramidEngine:
             nat.check(self.lib.wb_boxes_launch(nat.stream_ptr(), nat.ptr(det_sorted), n, nat.ptr(inv_d), dm.m, dm.n,
                                                nat.ptr(boxes), nat.ptr(scores)), "wb_boxes_launch")
         return boxes, scores
+
+    def ordered_host(self, dm, total):
+        """The `total` records fetch() left on the device (self.packed), put in the reference's order there, with their
+        boxes and scores (wb_boxes_launch), as host arrays: (records int32 [total, 4], boxes, scores)."""
+        det = sort_records(self.packed[1:1 + total])
+        boxes, scores = self.boxes(det, dm)
+        return det.cpu().numpy(), boxes.cpu().numpy(), scores.cpu().numpy()
 
     def inv_scales(self):
         """float32(1.0 / scale) per level: the factor get_boxes multiplies with (reference model.py:147)."""

@@ -5,6 +5,7 @@ and the zlib+protobuf ``.pb`` format.  The dense cascade scan runs in csrc/wb_ca
 """
 import os
 import zlib
+from typing import NamedTuple
 
 import numpy as np
 from google.protobuf.message import DecodeError
@@ -13,17 +14,20 @@ from . import _native as nat
 from . import channels as _channels
 from . import engine as _engine
 from . import model_pb2
-from .boxes import Boxes, concatenate, nms_keep_mask, non_max_suppression
+from .boxes import Boxes, nms_keep_mask
 from .channels import channel_pyramid
 from .compare import channel_tensor
-from .readback import host_boxes, key_positions, split_keys
+from .readback import Detections, from_finished, from_image_result, from_ordered, from_packed
+from .stream import Schedule
 from .training import DTree, _REBINDS
 
 # above this many detections per call the compaction, ordering and boxes stay on the GPU
 _HOST_POST_MAX = 1 << 16
-_HOST_POST_BATCH = 2048          # detect_stream's batches: more detections than this are ordered on the device
-# detect_stream's batches: split by image and ordered by wb_det_order_batch_launch (tests and WB_NO_ORDER_BATCH switch it off)
+_HOST_POST_BATCH = 2048          # a batch: more detections than this are ordered on the device
+# a batch: split by image and ordered by wb_det_order_batch_launch (tests and WB_NO_ORDER_BATCH switch it off) ...
 _ORDER_BATCH = os.environ.get("WB_NO_ORDER_BATCH") is None
+_ORDER_BATCH_MAX = 256           # ... up to this many images (the read-back block is fixed-size)
+_torch = None                    # torch, from the first detect_stream call on (imported late: reading a .pb needs none)
 
 
 def symbol_name(s):
@@ -61,18 +65,82 @@ def _nms_args(iou_threshold, score_threshold):
     return iou_threshold, score_threshold
 
 
-def _apply_nms(res, nms, keep=None):
-    """The rows of a detect_raw result that non-maximum suppression keeps (keep: the flags the device left behind the
-    scan; None: the complete result goes through boxes.nms_keep_mask, on the GPU as well)."""
+def _suppress(res, nms):
+    """The detections of one image's complete result that non-maximum suppression keeps: by the flags the device left
+    behind the scan; without them the result goes through boxes.nms_keep_mask, on the GPU as well."""
     if nms is None:
         return res
-    if keep is None:
-        keep = nms_keep_mask(res["boxes"], res["scores"], nms[0], nms[1])
-    at = np.flatnonzero(keep)
-    for k in ("boxes", "scores", "level", "r", "c", "image"):
-        if k in res:
-            res[k] = res[k][at]
-    return res
+    keep = res.keep if res.keep is not None else nms_keep_mask(res.boxes, res.scores, nms[0], nms[1])
+    return res.take(np.flatnonzero(keep))
+
+
+def _orders_batch(eng):
+    """Whether a batch on `eng` is split by image and ordered by wb_det_order_batch_launch."""
+    return _ORDER_BATCH and eng.batch <= _ORDER_BATCH_MAX
+
+
+def _as_boxes(res):
+    out = Boxes(res.boxes)
+    out.set_field("scores", res.scores)
+    return out
+
+
+def _raw(res, alive, scales):
+    """The dict detect_raw returns."""
+    level, r, c = res.windows()
+    return dict(boxes=res.boxes, scores=res.scores, level=level, r=r, c=c, alive=alive, scales=list(scales))
+
+
+class _BatchToken(NamedTuple):
+    """What a lane's scan_batch hands to its collect."""
+    stt: object                      # the scan state
+    ordered: bool                    # order_batch_enqueue ran behind the scan
+
+
+class _Lane(NamedTuple):
+    """A lane of detect_stream (stream.Schedule has the protocol): an engine and the stream all its work runs on."""
+    engine: object
+    stream: object
+
+    @property
+    def n_levels(self):
+        return self.engine.plan.n_levels
+
+    def scan_image(self, image, dm, nms):
+        with _torch.cuda.stream(self.stream):
+            self.engine.load_images(image)
+            return self.engine.detect_enqueue(dm, nms)
+
+    def load_slot(self, b, image):
+        with _torch.cuda.stream(self.stream):
+            self.engine.load_slot(b, image)
+
+    def scan_batch(self, dm, nms):
+        eng = self.engine
+        with _torch.cuda.stream(self.stream):
+            stt = eng.batch_enqueue(dm)
+            # the batch's results split by image, ordered and on their way to the host right behind the scan
+            return _BatchToken(stt, bool(_orders_batch(eng) and eng.order_batch_enqueue(dm, stt, nms)))
+
+    def collect(self, model, dm, token, count, nms):
+        eng = self.engine
+        if isinstance(token, _BatchToken):
+            with _torch.cuda.stream(self.stream):
+                out, _ = model._assemble(eng, dm, token.stt, count, nms, windows=False, ordered_enqueued=token.ordered)
+        else:
+            fin = eng.detect_collect(dm, token, self.stream, nms=nms)
+            if fin is None:                                   # (more detections than the one read-back holds: further copies)
+                with _torch.cuda.stream(self.stream):
+                    out, _ = model._assemble(eng, dm, eng._casc_state(dm), 1, nms, windows=False, single=True)
+            else:
+                out, _ = model._assemble(eng, dm, eng._casc_state(dm), 1, nms, windows=False, single=True, finished=fin)
+        return [_as_boxes(res) for res in out]
+
+    def wait_upload(self):
+        self.engine.wait_upload()
+
+    def synchronize(self):
+        self.stream.synchronize()
 
 
 class Model:
@@ -83,6 +151,7 @@ class Model:
         self.theta = []
         self._device = None
         self._content = None
+        self._lanes = {}             # detect_stream's lanes: (shape, dtype, channel options, batch) -> [_Lane], two keys at most
         self.reset()
 
     def __getstate__(self):
@@ -195,103 +264,116 @@ class Model:
         on the finished detections, enqueued behind the step's graph replay and in front of the call's one wait (the
         plain step's graph is shared: a new threshold captures nothing); n_loc / n_weak are those of the scan.  None: the
         plain call.  Scores are never NaN for a model the loader accepts."""
-        res = self.detect_raw(image, _full=False, _nms=_nms_args(iou_threshold, score_threshold))
-        out = Boxes(res["boxes"])
-        out.set_field("scores", res["scores"])
-        return out
+        res, _, _ = self._detect_one(image, _nms_args(iou_threshold, score_threshold), windows=False)
+        return _as_boxes(res)
 
-    def detect_raw(self, image, _full=True, _nms=None):
+    def detect_raw(self, image, _nms=None):
         """detect() with everything the parity tests compare: boxes, scores, (level, r, c),
-        alive[level, stage]; updates n_loc / n_weak.  (_full=False: boxes and scores only -- what detect() returns.)"""
+        alive[level, stage]; updates n_loc / n_weak."""
+        return _raw(*self._detect_one(image, _nms))
+
+    def _detect_one(self, image, nms, windows=True):
+        """One image -> (its Detections, alive[L, T], the levels' scales); updates n_loc / n_weak."""
         _channels._validate_image(image, allow_tensor=True)
         shrink, n_per_oct, smooth, spec = _channels.read_opts(self.channel_opts, allow_callable=True)
         if spec is None:
             if not isinstance(image, np.ndarray):
                 image = image.cpu().numpy()                 # (a caller's own channel function takes host arrays)
-            return _apply_nms(self._detect_raw_levelwise(image), _nms)
+            res, alive, scales = self._detect_levelwise(image)
+            return _suppress(res, nms), alive, scales
         m, n, Cc = self.shape
         assert Cc == spec.n_channels, f"Invalid number of channels. Expected {Cc} given {spec.n_channels}."
         H, W = (int(x) for x in image.shape)
         dm = self.device_cascade()
         eng = _engine.get_engine(H, W, _engine.array_dtype(image), shrink, n_per_oct, smooth, 1, channels=spec)
-        T = len(self)
         if eng.plan.n_levels == 0:
-            return dict(boxes=np.empty((0, 4), "f"), scores=np.empty(0, "f"), level=np.empty(0, np.int32),
-                        r=np.empty(0, np.int64), c=np.empty(0, np.int64), alive=np.zeros((0, T), np.int64),
-                        scales=[])
+            return Detections.none(), np.zeros((0, len(self)), np.int64), []
         eng.load_images(image)
         # one memset + octaves + channels (straight to this cascade's threshold ranks when it has rank tables) + cascade
         # + boxes and sort keys + the read-back: one hipGraph replay from the second call on
-        fin = eng.detect_run(dm, _nms)
-        return self._collect(eng, dm, eng._casc_state(dm), _full, fin, _nms)
+        fin = eng.detect_run(dm, nms)
+        (res,), alive = self._assemble(eng, dm, eng._casc_state(dm), 1, nms, windows=windows, single=True, finished=fin)
+        return res, alive[0], eng.plan.scales
 
-    def _detect_raw_levelwise(self, image):
-        """detect_raw for a channel function without a kernel: the reference's own loop (model.py:171-177) -- one level at
+    def _detect_levelwise(self, image):
+        """_detect_one for a channel function without a kernel: the reference's own loop (model.py:171-177) -- one level at
         a time from the generator (the caller's function runs between the GPU steps), each scanned on the GPU."""
         T = len(self)
-        parts, alive, scales = [], [], []
+        level, r, c, scores, boxes, alive, scales = [], [], [], [], [], [], []
         for lv, (chns, scale) in enumerate(self.channels(image)):
             rs, cs, hs, al = self.predict_on_image_stats(chns)
             alive.append(al)
             scales.append(scale)
             if rs.size:
-                parts.append((np.full(rs.size, lv, np.int32), rs, cs, hs, self.get_boxes(rs, cs, scale).get()))
-        cat = lambda k, dt: np.concatenate([p[k] for p in parts]).astype(dt, copy=False) if parts else np.empty(0, dt)
-        return dict(boxes=np.concatenate([p[4] for p in parts]) if parts else np.empty((0, 4), "f"), scores=cat(3, np.float32),
-                    level=cat(0, np.int32), r=cat(1, np.int64), c=cat(2, np.int64),
-                    alive=np.stack(alive) if alive else np.zeros((0, T), np.int64), scales=scales)
+                level.append(np.full(rs.size, lv, np.int32))
+                r.append(rs)
+                c.append(cs)
+                scores.append(hs)
+                boxes.append(self.get_boxes(rs, cs, scale).get())
+        cat = lambda parts, dt: np.concatenate(parts).astype(dt, copy=False) if parts else np.empty(0, dt)
+        res = Detections(np.concatenate(boxes) if boxes else np.empty((0, 4), "f"), cat(scores, np.float32),
+                         windows=(cat(level, np.int32), cat(r, np.int64), cat(c, np.int64)))
+        return res, np.stack(alive) if alive else np.zeros((0, T), np.int64), scales
 
     def scan_engine(self, eng, view=None):
         """Run this cascade over the channel pyramid already resident in `eng` (channels computed
         by the caller: several models can share one pyramid, reference __init__.py:120-124).
         view: this model's member view of a RankGroup whose threshold ranks `eng` holds (scan those instead of the
-        float32 channels).  Returns the same dict as detect_raw and updates n_loc / n_weak."""
+        float32 channels).  Returns the same dict as detect_raw and updates n_loc / n_weak.  The result is image 0's: of an
+        engine that holds a batch, the other images' records are left out."""
         m, n, Cc = self.shape
         assert Cc == eng.spec.n_channels, f"Invalid number of channels. Expected {Cc} given {eng.spec.n_channels}."
         dm = view if view is not None else self.device_cascade()
-        return self._collect(eng, dm, eng.run_cascade(dm, ranks=view is not None))
+        return self._scan_result(eng, dm, eng.run_cascade(dm, ranks=view is not None), fetch_final=True)
 
-    def _collect(self, eng, dm, stt, full=True, fin=False, nms=None):
-        """Results of the scan `stt` of image 0 of `eng`: the dict detect_raw returns; updates n_loc / n_weak.
-        fin: what eng.detect_run returned for this scan (False: fetch it here).
+    def _scan_result(self, eng, dm, stt, **have):
+        """The dict detect_raw returns, of the scan `stt` of image 0 of `eng` (have: what _assemble is told of it)."""
+        (res,), alive = self._assemble(eng, dm, stt, 1, None, single=True, **have)
+        return _raw(res, alive[0], eng.plan.scales)
+
+    def _assemble(self, eng, dm, stt, count, nms, *, windows=True, single=False, finished=None, fetch_final=False,
+                  ordered_enqueued=False):
+        """The results of the scan `stt` of `eng` with the cascade `dm` (the one that was scanned: detect_stream collects
+        late) -> ([Detections of image b for b < count], alive int64 [B, L, T]); updates n_loc / n_weak.  The slots
+        behind `count` hold earlier images, whose results are dropped; windows=False: boxes and scores are all the caller
+        wants (routes 1 and 2 then leave the sort keys where they are).  Every route has ONE host synchronisation, grows
+        the detection buffer and scans again after an overflow, and leaves copies of its read-back.  The first that applies:
+          1. single -- one image, in the one-image finish block (sort keys, boxes, scores, statistics in one copy:
+             wb_det_finish_sorted_launch): `finished`, what detect_run / detect_collect returned for this scan, or with
+             fetch_final the block fetched here.  Up to PyramidEngine._FETCH_ROWS detections.
+          2. not single -- a batch, split by image, ordered and finished on the device (wb_det_order_batch_launch), one
+             read-back; ordered_enqueued: the launch and the copies are behind the scan already, only the wait is left.  Up
+             to PyramidEngine._ORDER_ROWS detections per image and _ORDER_BATCH_MAX images.
+          3. the packed records (wb_det_pack_launch): few detections (the usual case) are ordered and their boxes formed on
+             the host -- the same float32 arithmetic as boxes_kernel, without three launches and four copies; more than
+             _HOST_POST_MAX (single) / _HOST_POST_BATCH stay on the device for a sort and wb_boxes_launch.
         nms: (iou_threshold, score_threshold or None): only the detections non-maximum suppression keeps -- by the flags
-        the device left with `fin`; the routes without them suppress their complete result (boxes.nms_keep_mask)."""
+        the device left on routes 1 and 2, otherwise of each image's complete result (_suppress)."""
         m, n, Cc = self.shape
-        if fin is False:
-            fin = eng.fetch_final(dm, stt, nms=nms)       # ONE host synchronisation: sort keys, boxes, scores, statistics
-        got = fin if fin is not None else eng.fetch(dm, stt)      # (likewise: packed records + statistics)
-        # (dm: the cascade that was scanned -- detect_stream collects late)
-        res = dict(alive=got.alive[0].reshape(eng.plan.n_levels, dm.n_stages), scales=list(eng.plan.scales))
+        if single and finished is None and fetch_final:
+            finished = eng.fetch_final(dm, stt, nms=nms)
+        ordered = None
+        if not single and _orders_batch(eng):
+            ordered = eng.fetch_ordered_batch(dm, stt, ordered_enqueued, nms)
+        if finished is not None:
+            out, alive = [from_finished(finished, windows)], finished.alive
+        elif ordered is not None:
+            per_image, alive = ordered
+            out = [from_image_result(item, windows) for item in per_image[:count]]
+        else:
+            got = eng.fetch(dm, stt, limit=_HOST_POST_MAX if single else _HOST_POST_BATCH)
+            alive = got.alive
+            if got.records is not None:
+                out = from_packed(got.records, count, m, n, eng.inv_scales(), one_slot=eng.batch == 1)
+            else:
+                out = from_ordered(*eng.ordered_host(dm, got.total), count)
         if stt.n_loc is None:
             stt.n_loc = eng.plan.n_loc(m, n)
-        self.n_loc += stt.n_loc
-        self.n_weak += int(res["alive"].sum())
-        keep = None
-        if fin is not None:
-            # get_boxes and the (level, r, c) keys were formed on the device (wb_det_finish_sorted_launch) and -- up to 4096
-            # detections -- put in the reference's order there: the host copies slices out of the read-back buffer.
-            # Otherwise it sorts the keys -- unique, so any sort kind gives the reference order -- and gathers
-            ks, keep = fin.keys, fin.keep
-            if fin.ordered:
-                res.update(boxes=fin.boxes[:ks.size].copy(), scores=fin.scores[:ks.size].copy())
-            else:
-                ks = np.sort(ks)
-                at = key_positions(ks)
-                res.update(boxes=fin.boxes[at], scores=fin.scores[at])
-                keep = keep[at] if keep is not None else None
-            if full:
-                res["level"], res["r"], res["c"] = split_keys(ks)          # (new arrays, like boxes and scores)
-        elif got.total <= _HOST_POST_MAX:
-            # few detections (the usual case): order and boxes on the host -- the same float32 arithmetic as
-            # boxes_kernel, without three launches and four copies
-            _, res["level"], res["r"], res["c"], res["boxes"], res["scores"] = host_boxes(got.records, m, n, eng.inv_scales())
-        else:
-            det = eng.sorted_detections()
-            boxes, scores = eng.boxes(det, dm)
-            d = det.cpu().numpy().view(nat.DET_DTYPE).reshape(-1)
-            res.update(boxes=boxes.cpu().numpy(), scores=scores.cpu().numpy(), level=d["level"].copy(),
-                       r=d["r"].astype(np.int64), c=d["c"].astype(np.int64))
-        return _apply_nms(res, nms, keep)
+        self.n_loc += count * stt.n_loc
+        self.n_weak += int(alive[:count].sum())
+        if nms is not None:
+            out = [_suppress(res, nms) for res in out]
+        return out, alive
 
     def detect_stream(self, images, lanes=3, batch=1, iou_threshold=None, score_threshold=None):
         """detect() over an iterable of 2-D images, as a generator of Boxes in the iterable's order -- the loop the
@@ -308,7 +390,8 @@ class Model:
         lane's one wait.
         (Measured and left out: the blocking upload on a helper thread -- 0.13 to 0.16 ms per 1080p image against 0.14 to
         0.15 without: what the copy frees, the two threads lose again handing the interpreter lock back and forth.)"""
-        import torch
+        global _torch
+        import torch as _torch
         lanes, K = max(int(lanes), 1), max(int(batch), 1)
         nms = _nms_args(iou_threshold, score_threshold)
         shrink, n_per_oct, smooth, spec = _channels.read_opts(self.channel_opts, allow_callable=True)
@@ -318,135 +401,24 @@ class Model:
             return
         m, n, Cc = self.shape
         assert Cc == spec.n_channels, f"Invalid number of channels. Expected {Cc} given {spec.n_channels}."
-        pool = self.__dict__.setdefault("_lanes", {})        # (H, W, dtype, channel_opts, batch) -> [(engine, stream)]
-        pending = []                                          # [(engine, stream, dm, token, images in it)] oldest first
-        fill = None                                           # the batch being gathered: [key, engine, stream, dm, images in it]
 
-        def finish(item):
-            eng, stream, dm, token, count = item
-            if K == 1:
-                fin = eng.detect_collect(dm, token, stream, nms=nms)
-                if fin is None:                               # (more detections than the one read-back holds: further copies)
-                    with torch.cuda.stream(stream):
-                        res = self._collect(eng, dm, eng._casc_state(dm), False, None, nms)
-                else:
-                    res = self._collect(eng, dm, eng._casc_state(dm), False, fin, nms)
-                out = Boxes(res["boxes"])
-                out.set_field("scores", res["scores"])
-                return [out]
-            with torch.cuda.stream(stream):
-                return self._collect_batch(eng, dm, token[0], count, enqueued=token[1], nms=nms)
-
-        def send(f):
-            _, eng, stream, dm, count = f
-            with torch.cuda.stream(stream):
-                stt = eng.batch_enqueue(dm)
-                # the batch's results split by image, ordered and on their way to the host right behind the scan
-                ordered = _ORDER_BATCH and eng.order_batch_enqueue(dm, stt, nms)
-                pending.append((eng, stream, dm, (stt, ordered), count))
-
-        try:
+        def items():
+            """(what a lane must have been built for, the cascade as it is now, the image) per image"""
             for image in images:
                 _channels._validate_image(image, allow_tensor=True)
-                H, W = (int(x) for x in image.shape)
-                idt = _engine.array_dtype(image)
-                key = (H, W, idt.str, shrink, n_per_oct, smooth, spec.key, K)
-                dm = self.device_cascade()
-                if fill is not None and (fill[0] != key or fill[3] is not dm):
-                    send(fill)                                # (another shape, or the model changed: the batch goes as it is)
-                    fill = None
-                while len(pending) >= lanes:
-                    yield from finish(pending.pop(0))
-                if fill is None:
-                    group = pool.get(key)
-                    if group is None:
-                        if len(pool) >= 2:
-                            pool.pop(next(iter(pool)))
-                        group = pool[key] = []
-                    # the lane this image takes: one no pending image holds (fewer than `lanes` are pending here)
-                    busy = {id(it[0]) for it in pending}
-                    lane = next((ln for ln in group if id(ln[0]) not in busy), None)
-                    if lane is None:
-                        lane = (_engine.PyramidEngine(H, W, idt, shrink, n_per_oct, smooth, K, channels=spec),
-                                torch.cuda.Stream())
-                        group.append(lane)
-                    eng, stream = lane
-                    if eng.plan.n_levels == 0:
-                        while pending:
-                            yield from finish(pending.pop(0))
-                        yield self.detect(image, iou_threshold, score_threshold)
-                        continue
-                    fill = [key, eng, stream, dm, 0]
-                _, eng, stream, _, count = fill
-                with torch.cuda.stream(stream):
-                    if K == 1:
-                        eng.load_images(image)
-                        pending.append((eng, stream, dm, eng.detect_enqueue(dm, nms), 1))
-                        fill = None
-                    else:
-                        eng.load_slot(count, image)
-                        fill[4] = count + 1
-                if fill is not None and fill[4] == K:
-                    send(fill)
-                    fill = None
-                if len(pending) >= lanes:
-                    yield from finish(pending.pop(0))
-                # an image uploaded asynchronously from the caller's page-locked buffer: the copy has left that buffer
-                # before the iterable is asked for its next image (a decoder may write into the same buffer again); by
-                # now the scan is enqueued and an older lane has been collected, so this wait is over before it starts
-                eng.wait_upload()
-            if fill is not None:
-                send(fill)
-                fill = None
-            while pending:
-                yield from finish(pending.pop(0))
-        finally:
-            for item in pending:                              # (the consumer stopped early: let the lanes drain)
-                item[1].synchronize()
-            if fill is not None:
-                fill[2].synchronize()
+                H, W = map(int, image.shape)
+                yield (H, W, _engine.array_dtype(image).str, shrink, n_per_oct, smooth, spec.key, K), self.device_cascade(), image
 
-    def _collect_batch(self, eng, dm, stt, count, enqueued=False, nms=None):
-        """Boxes of images [0, count) of the batch `eng` has just scanned (detect_stream; the slots behind `count` hold
-        earlier images, whose results are dropped).  Split by image, ordered and finished on the device
-        (wb_det_order_batch_launch) with one read-back; an image with more than 4096 detections sends the batch the
-        older way: few detections ordered on the host from the one read-back, otherwise ordered, and their boxes formed,
-        on the device (wb_boxes_launch).  Updates n_loc / n_weak."""
-        m, n, Cc = self.shape
-        # ONE host synchronisation (overflow: grows and scans again); per image a copy of its slices of the one read-back
-        # (enqueued: detect_stream has put the launch and the copies behind the scan already -- only the wait is left)
-        res = eng.fetch_ordered_batch(dm, stt, enqueued, nms) if _ORDER_BATCH else None
-        if res is not None:
-            per_image, alive = res
-            self.n_loc += count * eng.plan.n_loc(m, n)
-            self.n_weak += int(alive[:count].sum())
-            out = []
-            for item in per_image[:count]:
-                boxes, scores = item.boxes, item.scores
-                if nms is not None:                            # (the device's keep flags; None: suppressed now)
-                    kept = _apply_nms(dict(boxes=boxes, scores=scores), nms, item.keep)
-                    boxes, scores = kept["boxes"], kept["scores"]
-                bx = Boxes(boxes.copy())
-                bx.set_field("scores", scores.copy())
-                out.append(bx)
-            return out
-        got = eng.fetch(dm, stt, limit=_HOST_POST_BATCH)          # ONE host synchronisation (overflow: grows and scans again)
-        self.n_loc += count * eng.plan.n_loc(m, n)
-        self.n_weak += int(got.alive[:count].sum())
-        if got.records is not None:
-            d = got.records.view(nat.DET_DTYPE).reshape(-1)
-            image, _, _, _, boxes, scores = host_boxes(d[d["image"] < count], m, n, eng.inv_scales(), with_image=True)
-        else:
-            det = _engine.sort_records(eng.packed[1:1 + got.total])
-            image = det[:, 0].cpu().numpy()
-            boxes, scores = (t.cpu().numpy() for t in eng.boxes(det, dm))
-        cuts = np.searchsorted(image, np.arange(count + 1))
-        out = []
-        for b in range(count):
-            bx = Boxes(boxes[cuts[b]:cuts[b + 1]])
-            bx.set_field("scores", scores[cuts[b]:cuts[b + 1]])
-            out.append(bx if nms is None else non_max_suppression(bx, nms[0], nms[1]))
-        return out
+        def new_lane(key, image):
+            H, W = (int(x) for x in image.shape)
+            return _Lane(_engine.PyramidEngine(H, W, _engine.array_dtype(image), shrink, n_per_oct, smooth, K, channels=spec),
+                         _torch.cuda.Stream())
+
+        pool = getattr(self, "_lanes", None)                  # key -> [_Lane]
+        if pool is None:                                      # (a copy: __getstate__ leaves the lanes behind)
+            pool = self._lanes = {}
+        yield from Schedule(pool, lanes, K, new_lane, lambda image: self.detect(image, iou_threshold, score_threshold),
+                            self, nms).run(items())
 
     def detect_batch(self, images, iou_threshold=None, score_threshold=None):
         """detect() on a batch: `images` is [B,H,W] (ndarray or device tensor) of one shape and dtype;
@@ -454,17 +426,19 @@ class Model:
         content and order as B calls of detect) and updates n_loc / n_weak.
         iou_threshold, score_threshold: as for detect, per image (one wb_nms_finish_launch for the whole batch behind the
         ordering launch, in front of the one wait)."""
-        res = self.detect_batch_raw(images, _nms=_nms_args(iou_threshold, score_threshold))
-        out = []
-        for b in range(res["batch"]):
-            sel = res["image"] == b
-            bx = Boxes(res["boxes"][sel])
-            bx.set_field("scores", res["scores"][sel])
-            out.append(bx)
-        return out
+        out, _, _ = self._detect_batch(images, _nms_args(iou_threshold, score_threshold), windows=False)
+        return [_as_boxes(res) for res in out]
 
     def detect_batch_raw(self, images, _nms=None):
         """All detections of a batch as flat arrays (image, level, r, c, boxes, scores, alive[B,L,T])."""
+        out, alive, scales = self._detect_batch(images, _nms)
+        level, r, c = (np.concatenate(w) for w in zip(*(res.windows() for res in out)))
+        return dict(batch=len(out), image=np.repeat(np.arange(len(out), dtype=np.int32), [res.scores.size for res in out]),
+                    level=level, r=r, c=c, boxes=np.concatenate([res.boxes for res in out]),
+                    scores=np.concatenate([res.scores for res in out]), alive=alive, scales=list(scales))
+
+    def _detect_batch(self, images, nms, windows=True):
+        """A batch -> ([Detections per image], alive[B, L, T], the levels' scales); updates n_loc / n_weak."""
         if getattr(images, "ndim", None) != 3 and (not hasattr(images, "dim") or images.dim() != 3):
             raise ValueError("images must have 3 dimensions [B,H,W]")
         B, H, W = (int(x) for x in images.shape)
@@ -473,47 +447,12 @@ class Model:
         m, n, Cc = self.shape
         assert Cc == spec.n_channels, f"Invalid number of channels. Expected {Cc} given {spec.n_channels}."
         dm = self.device_cascade()
-        T = len(self)
         eng = _engine.get_engine(H, W, dtype, shrink, n_per_oct, smooth, B, channels=spec)
-        L = eng.plan.n_levels
-        if L == 0:
-            return dict(batch=B, image=np.empty(0, np.int32), level=np.empty(0, np.int32), r=np.empty(0, np.int64),
-                        c=np.empty(0, np.int64), boxes=np.empty((0, 4), "f"), scores=np.empty(0, "f"),
-                        alive=np.zeros((B, 0, T), np.int64), scales=[])
+        if eng.plan.n_levels == 0:
+            return [Detections.none() for _ in range(B)], np.zeros((B, 0, len(self)), np.int64), []
         eng.load_images(images)
-        stt = eng.run(dm)
-        # split by image, ordered and finished on the device, one read-back (up to 4096 detections per image and 256
-        # images: the read-back block is fixed-size); otherwise a device sort of all records and wb_boxes_launch
-        res = eng.fetch_ordered_batch(dm, stt, nms=_nms) if (_ORDER_BATCH and B <= 256) else None
-        if res is not None:
-            per_image, alive = res
-            alive = alive.reshape(B, L, T)
-            self.n_loc += B * eng.plan.n_loc(m, n)
-            self.n_weak += int(alive.sum())
-            level, r, c = split_keys(np.concatenate([it.keys for it in per_image]))
-            res = dict(batch=B, image=np.repeat(np.arange(B, dtype=np.int32), [it.keys.size for it in per_image]),
-                       level=level, r=r, c=c, boxes=np.concatenate([it.boxes for it in per_image]),
-                       scores=np.concatenate([it.scores for it in per_image]), alive=alive, scales=list(eng.plan.scales))
-            if _nms is None:
-                return res
-            # (keep None: the device left no flags for this image, it is suppressed now)
-            keep = [it.keep if it.keep is not None else nms_keep_mask(it.boxes, it.scores, _nms[0], _nms[1]) for it in per_image]
-            return _apply_nms(res, _nms, np.concatenate(keep))
-        eng.ensure_capacity(dm)
-        det = eng.sorted_detections()
-        boxes, scores = eng.boxes(det, dm)
-        alive = _engine.alive_host(stt.alive, T).reshape(B, L, T)
-        self.n_loc += B * eng.plan.n_loc(m, n)
-        self.n_weak += int(alive.sum())
-        d = det.cpu().numpy().view(nat.DET_DTYPE).reshape(-1)
-        res = dict(batch=B, image=d["image"].copy(), level=d["level"].copy(), r=d["r"].astype(np.int64),
-                   c=d["c"].astype(np.int64), boxes=boxes.cpu().numpy(), scores=scores.cpu().numpy(), alive=alive,
-                   scales=list(eng.plan.scales))
-        if _nms is not None:                                   # (image by image: the records are ordered by image)
-            cuts = np.searchsorted(res["image"], np.arange(B + 1))
-            keep = [nms_keep_mask(res["boxes"][a:b], res["scores"][a:b], _nms[0], _nms[1]) for a, b in zip(cuts[:-1], cuts[1:])]
-            res = _apply_nms(res, _nms, np.concatenate(keep))
-        return res
+        out, alive = self._assemble(eng, dm, eng.run(dm), B, nms, windows=windows)
+        return out, alive, eng.plan.scales
 
     def predict(self, X):
         """The cascade on samples X[N, m, n, C] -> (H, mask): H[i] is the response accumulated in stage

@@ -1,5 +1,6 @@
 """A scan's results on their way from the device to ``Boxes``: the byte layout of a finish block, the sort key's bit
-fields, the host's own ordering and box arithmetic, and what the engine's read-back methods return.  NumPy only.
+fields, the host's own ordering and box arithmetic, what the engine's read-back methods return, and the one form --
+Detections -- that every one of them is turned into.  NumPy only.
 
 A finish block of `rows` records, as wb_det_finish_sorted_launch (one image) and wb_det_order_batch_launch (one block
 per image, back to back behind a 16-byte prefix) write it:  16-byte header | 8 * rows keys | 16 * rows boxes | 4 * rows
@@ -84,3 +85,74 @@ def host_boxes(records, m, n, inv_scales, with_image=False):
     np.multiply((r + m).astype(np.float32), inv, out=boxes[:, 3])
     return (d["image"][order].astype(np.int64) if with_image else None, level.astype(np.int32), r, c, boxes,
             d["score"][order])
+
+
+class Detections:
+    """One image's detections in the reference's order (level, r, c): boxes float32 [n, 4] (XYXY), scores float32 [n],
+    keep: the flags non-maximum suppression left on the device (bool [n]) or None.  The windows stay as they came -- sort
+    keys or (level, r, c) -- and are split on demand; a converter told windows=False leaves them out altogether (Model.detect
+    never asks: it pays neither the split nor the copy of the keys).  Owns its arrays: what the converters below take from
+    a page-locked read-back buffer, they copy."""
+    __slots__ = ("boxes", "scores", "keep", "_keys", "_windows")
+
+    def __init__(self, boxes, scores, keep=None, keys=None, windows=None):
+        self.boxes, self.scores, self.keep, self._keys, self._windows = boxes, scores, keep, keys, windows
+
+    @classmethod
+    def none(cls):
+        return cls(np.empty((0, 4), np.float32), np.empty(0, np.float32), keys=np.empty(0, np.uint64))
+
+    def windows(self):
+        """(level int32 [n], r int64 [n], c int64 [n])"""
+        if self._windows is None:
+            if self._keys is None:
+                raise ValueError("these detections were converted without their windows")
+            self._windows = split_keys(self._keys)
+        return self._windows
+
+    def take(self, at):
+        """The detections at rows `at`."""
+        return Detections(self.boxes[at], self.scores[at], None, None if self._keys is None else self._keys[at],
+                          None if self._windows is None else tuple(a[at] for a in self._windows))
+
+
+def from_finished(fin, windows=True):
+    """A Finished: slice copies when the device ordered it; otherwise the keys sorted here -- unique, so any sort kind
+    gives the reference's order -- and boxes, scores and keep gathered by the keys' positions."""
+    ks, keep = fin.keys, fin.keep
+    if fin.ordered:
+        return Detections(fin.boxes[:ks.size].copy(), fin.scores[:ks.size].copy(), None if keep is None else keep.copy(),
+                          ks.copy() if windows else None)
+    ks = np.sort(ks)
+    at = key_positions(ks)
+    return Detections(fin.boxes[at], fin.scores[at], keep[at] if keep is not None else None, ks if windows else None)
+
+
+def from_image_result(item, windows=True):
+    """An ImageResult (in order already)."""
+    return Detections(item.boxes.copy(), item.scores.copy(), None if item.keep is None else item.keep.copy(),
+                      item.keys.copy() if windows else None)
+
+
+def _cut(count, image, level, r, c, boxes, scores):
+    """Arrays ordered by (image, level, r, c) -> [Detections of image b for b < count]."""
+    cuts = np.searchsorted(image, np.arange(count + 1))
+    return [Detections(boxes[a:b], scores[a:b], windows=(level[a:b], r[a:b], c[a:b])) for a, b in zip(cuts[:-1], cuts[1:])]
+
+
+def from_packed(records, count, m, n, inv_scales, one_slot=False):
+    """Packed records in shard order (Packed.records) -> [Detections per image < count], ordered and their boxes formed
+    on the host (host_boxes); records of a slot >= count -- an earlier batch's -- are dropped.  one_slot: the engine
+    holds one image, every record is its (no image column to sort by or to cut at)."""
+    if one_slot:
+        _, level, r, c, boxes, scores = host_boxes(records, m, n, inv_scales)
+        return [Detections(boxes, scores, windows=(level, r, c))]
+    d = records.view(DET_DTYPE).reshape(-1)
+    return _cut(count, *host_boxes(d[d["image"] < count], m, n, inv_scales, with_image=True))
+
+
+def from_ordered(records, boxes, scores, count):
+    """Records the device put in order (by image, level, r, c: int32 [k, 4]) with their boxes and scores, as host arrays
+    of their own -> [Detections per image < count]."""
+    d = records.view(DET_DTYPE).reshape(-1)
+    return _cut(count, d["image"], d["level"].astype(np.int32), d["r"].astype(np.int64), d["c"].astype(np.int64), boxes, scores)
