@@ -32,14 +32,14 @@
 //     chunks of 64 and the rest retire;
 //   * stage-parallel tail: once a wave is down to a handful of windows (about 1e-3 of the
 //     windows of the benchmark cascade reach stage 32, with ~100 stages to go) the roles flip:
-//     one window at a time, 64 stages AT ONCE, one stage per lane (per-lane stage records,
+//     four windows at a time, 16 stages of each AT ONCE, one stage per lane (per-lane stage records,
 //     gathers from the same LDS tile); the fp32 accumulation and the rejection tests are then
-//     replayed in stage order (a DPP wave_shr:1 ripple: lane i ends up with ((h+p_0)+p_1)+...+p_i,
-//     exactly the reference's running sum) -- so a nearly empty wave no longer walks 100 stages serially
-//     while the workgroup's LDS tile sits idle;
-//   * the windows alive after the last stage stay in the wave's queue; one thread reserves room
-//     for the whole workgroup with ONE atomic on one of WB_DET_SHARDS counters and the waves
-//     copy their records out.
+//     replayed in stage order (a DPP row_shr:1 ripple inside each 16-lane row: lane i of a row ends up
+//     with ((h+p_0)+p_1)+...+p_i, exactly the reference's running sum) -- so a nearly empty wave no
+//     longer walks 100 stages serially while the workgroup's LDS tile sits idle;
+//   * the windows alive after the last dense stage stay in the wave's queue and every wave that holds
+//     some reserves their output slots with ONE atomic on one of WB_DET_SHARDS counters; a window that
+//     passes the last stage in the tail is appended right there.
 //
 // Scores are accumulated in fp32 strictly in stage order and compared with `>=`, so they are
 // bit-identical to the reference's `hs += ...; mask = hs >= theta`.

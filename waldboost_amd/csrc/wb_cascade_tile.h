@@ -92,9 +92,6 @@ __host__ __device__ constexpr size_t wb_lds_stab_off(int eb, int C, int rows, in
 // every lambda of the kernel body is inlined by decree: left to its cost model the compiler made a real function of
 // run_segments in a 1024-stage depth-3 build, with the captured state handed over through scratch memory
 #define WB_INLINE_LAMBDA __attribute__((always_inline))
-#ifndef WB_TAIL_W
-#define WB_TAIL_W 2          // windows the stage-parallel tail walks side by side
-#endif
 #ifndef WB_TAIL_ALL
 #define WB_TAIL_ALL 1        // tail: gather every node's feature up front (eval_all)
 #endif
@@ -968,11 +965,11 @@ __device__ __forceinline__ void cascade_tile_body(const CascArgs &a, const int32
     WB_STAMP(4);
     if (a.dbg & 16) return;
 
-    // ---- stage-parallel tail: lane i evaluates stage rs + i of a window (two windows side by side)
-    // this lane's record for stage rs + lane (the LDS mirror, or HBM when the table is too large for it)
-    auto lane_stage = [&](int rs) WB_INLINE_LAMBDA {
+    // ---- stage-parallel tail: lane l evaluates stage rs + (l & 15) of window l >> 4 -- four windows (the four 16-lane DPP
+    //      rows) through 16 stages per pass
+    // this lane's record for stage t (the LDS mirror, or HBM when the table is too large for it)
+    auto lane_stage = [&](int t) WB_INLINE_LAMBDA {
         Stage<D> st;
-        const int t = rs + lane;
         const int tt = t < T ? t : T - 1;
         int32_t rec[SD];
         if (BAKED ? WB_JIT_LDS_STAGES != 0 : a.lds_stages != 0) {
@@ -991,162 +988,87 @@ __device__ __forceinline__ void cascade_tile_body(const CascArgs &a, const int32
         st.load(rec);
         return st;
     };
-    // W windows (origins pos[], scores h[] on entering stage rs) through the stages rs .. rs + nvalid - 1, one stage per
-    // lane: rej[w] = a stage rejected it; else h[w] = its score behind the last of them.  entered += the number of
-    // these windows that entered stage rs + lane.  A window's chain -- gathers, leaf select, the ripple -- is all
-    // latency: two independent chains interleave in the same issue slots.
-    auto pass = [&](auto w_tag, const Stage<D> &st, int nvalid, const int *pos, float *h, bool *rej, uint32_t &entered) WB_INLINE_LAMBDA {
-        constexpr int W = decltype(w_tag)::value;
-        float pk[W], hk[W];
-#pragma unroll
-        for (int w = 0; w < W; ++w) {
-            const int wbase = ((pos[w] >> 6) * pitch + (pos[w] & 63)) * px_stride;
+    // The entries list[i .. i + 3] (those below n; .x = position, .y = the score on entering stage rs0) through ALL their
+    // remaining stages, counted in hist; a window that passes the last stage is appended to the output right here (one
+    // atomic each: they are rare).
+    // A pass replays the scores in stage order: lane k of a row accumulates p_0 .. p_k one after the other -- the same
+    // additions in the same order as the reference's running `hs +=` -- so it ends up with the score the rejection test
+    // of stage rs + k sees.  The ripple runs inside the row: DPP row_shr:1, lane k takes lane k - 1's running sum and adds
+    // its own p; after step j lanes 0 .. j are final and later steps recompute the same value, so 15 steps settle the 16
+    // lanes.  The row's first lane folds the incoming score into its addend (0 + x == x exactly), so the value shifted in
+    // there can be the DPP zero (bound_ctrl) and each step is ONE v_add_f32 for four windows.  (Until round 19 one window
+    // took the whole wave: 64 stages a pass, a 63-step ripple, one instruction per window-stage against a quarter.)
+    // What a row has of its own -- the window, its score, the stage it has reached -- is a per-lane value, the same in
+    // the row's 16 lanes; a row whose window is rejected stands still while its partners go on.
+    auto finish_rows = [&](const uint2 *list, int i, int n, int rs0) WB_INLINE_LAMBDA {
+        const int k = lane & 15, idx = i + (lane >> 4);
+        bool live = idx < n;                                  // an empty row repeats entry i and counts nowhere
+        const uint2 e = list[live ? idx : i];
+        const int pos = (int)e.x;
+        int rs = rs0;
+        float h = __uint_as_float(e.y);
+        const int wbase = ((pos >> 6) * pitch + (pos & 63)) * px_stride;
+        bool won = false;
+        while (__ballot(live) != 0ull) {
+            const int nvalid = T - rs < 16 ? T - rs : 16;     // (a short last pass)
+            const Stage<D> st = lane_stage(rs + k);
             const float p = WB_TAIL_ALL ? st.template eval_all<EB>(tile, wbase) : st.template eval<EB>(tile, wbase);
-            // Replay in stage order: lane k accumulates p_0 .. p_k one after the other -- the same
-            // additions in the same order as the reference's running `hs +=` -- so it ends up
-            // with the score the rejection test of stage rs+k sees.
-            // (ripple through the wave with DPP wave_shr:1 -- lane k takes lane k-1's running sum
-            // and adds its own p; after step j lanes 0..j are final and later steps recompute the
-            // same value, so 63 steps settle every lane)
-            // Lane 0 folds the incoming score into its addend (0 + x == x exactly), so the shifted-in
-            // value of the out-of-range lane can be the DPP zero (bound_ctrl) and each step is ONE
-            // v_add_f32 with a wave_shr:1 source.
-            pk[w] = lane == 0 ? h[w] + p : p;
-            hk[w] = pk[w];
-        }
-        // Most windows are rejected within a few stages, so the ripple runs in blocks of 8 steps and stops
-        // at the first block whose settled lanes hold a rejection: the lowest such lane is the first
-        // rejecting stage (every earlier stage is settled and passed).  (A window that is done keeps rippling
-        // beside its partner: its settled lanes recompute the same sums, its verdict is frozen.)
-        unsigned long long rmask[W];
-        bool done[W];
+            const float pk = k == 0 ? h + p : p;
+            float hk = pk;
 #pragma unroll
-        for (int w = 0; w < W; ++w) {
-            rmask[w] = 0ull;
-            done[w] = false;
-        }
-        for (int settled = 1;;) {                            // lanes [0, settled) hold their final sums
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-#pragma unroll
-                for (int w = 0; w < W; ++w) {
-                    int prev = __builtin_amdgcn_update_dpp(0, __float_as_int(hk[w]), 0x138 /* wave_shr:1 */, 0xf, 0xf, true);
-                    hk[w] = __int_as_float(prev) + pk[w];
-                }
+            for (int j = 0; j < 15; ++j) {
+                const int prev = __builtin_amdgcn_update_dpp(0, __float_as_int(hk), 0x111 /* row_shr:1 */, 0xf, 0xf, true);
+                hk = __int_as_float(prev) + pk;
             }
-            settled += 8;
-            const int upto = settled < nvalid ? settled : nvalid;
-            bool all = true;
-#pragma unroll
-            for (int w = 0; w < W; ++w) {
-                if (!done[w]) {
-                    rmask[w] = __ballot((lane < upto) && (st.theta != -INFINITY) && !(hk[w] >= st.theta));
-                    done[w] = rmask[w] || settled >= nvalid;
-                }
-                all = all && done[w];
-            }
-            if (all) break;
+            // one ballot per pass; a lane takes its own row's 16 bits from its 32-bit half of the mask (no 64-bit shift
+            // by a lane-varying amount): the lowest set bit is the row's first rejecting stage
+            const unsigned long long rmask = __ballot(live && k < nvalid && (st.theta != -INFINITY) && !(hk >= st.theta));
+            const uint32_t half = lane < 32 ? (uint32_t)rmask : (uint32_t)(rmask >> 32);
+            const int first = __builtin_ctz(((half >> (lane & 16)) & 0xFFFFu) | 0x10000u);      // 16: none
+            const int last = first < nvalid ? first : nvalid - 1;                               // last stage entered
+            if (live && k <= last) atomicAdd(&hist[rs + k], 1u);         // (LDS takes the four rows' duplicates)
+            // the outgoing score is the row's lane nvalid - 1 (a row that is done keeps what it had: a detection's score)
+            const float h_out = __int_as_float(__builtin_amdgcn_ds_bpermute(((lane & 48) + nvalid - 1) * 4, __float_as_int(hk)));
+            const bool passed = live && first == 16;
+            h = passed ? h_out : h;
+            rs = passed ? rs + 16 : rs;
+            won = won || (passed && rs >= T);
+            live = passed && rs < T;
         }
-#pragma unroll
-        for (int w = 0; w < W; ++w) {
-            const int last = rmask[w] ? (int)__builtin_ctzll(rmask[w]) : nvalid - 1;   // last stage entered
-            entered += lane <= last ? 1u : 0u;                                         // (lanes >= nvalid never count: last < nvalid)
-            rej[w] = rmask[w] != 0ull;
-            h[w] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(hk[w]), nvalid - 1));
+        if (won && k == 0) {
+            const uint32_t shard = shard_of((pos >> 6) / RPW);        // (the shard of the window's own rows)
+            const uint32_t slot = atomicAdd(a.det_count + shard, 1u);
+            if (slot < a.det_cap) {
+                WbDet d;
+                d.image = b;
+                d.level = tile_d.level;
+                d.r = (uint16_t)(r0 + (pos >> 6));
+                d.c = (uint16_t)(c0 + (pos & 63));
+                d.score = h;
+                a.det[(size_t)shard * a.det_cap + slot] = d;
+            }
         }
     };
     // The ripple is a chain of dependent vector instructions: on a SIMD that seven other waves keep busy it advances one
-    // step per round of the issue arbiter -- a 64-stage pass then takes thousands of cycles while the rest of the
-    // workgroup waits at the final barrier.  Raised priority puts the chain's next instruction in front (it issues few).
+    // step per round of the issue arbiter -- a pass then takes thousands of cycles while the workgroup holds its LDS.
+    // Raised priority puts the chain's next instruction in front (it issues few).
     __builtin_amdgcn_s_setprio(WB_TAIL_PRIO);
     if (scatter) {
-        // The workgroup's few survivors sit in ONE list: every wave claims the next two entries (an LDS ticket) and
-        // takes them through ALL remaining stages, then claims again -- the waves finish within one window of each other
+        // The workgroup's few survivors sit in ONE list: every wave claims the next four entries (an LDS ticket) and
+        // takes them through ALL remaining stages, then claims again -- the waves finish within one claim of each other
         // whatever the survivors cost (dealt out in fixed shares, the wave with the longest-lived windows kept the other
-        // seven waiting at the final barrier for a fifth of the workgroup's lifetime).  A window that passes the last
-        // stage is appended to the output right here (one atomic each: they are rare).
+        // seven waiting at the final barrier for a fifth of the workgroup's lifetime).
         for (;;) {
             uint32_t i0 = 0;
-            if (lane == 0) i0 = atomicAdd(ticket, 2u);
+            if (lane == 0) i0 = atomicAdd(ticket, 4u);
             const int i = __builtin_amdgcn_readfirstlane((int)i0);
             if (i >= dyn_total) break;
-            const bool two = i + 1 < dyn_total;
-            int pos[2];
-            float h[2];
-            bool alive[2] = {true, two};
-#pragma unroll
-            for (int w = 0; w < 2; ++w) {
-                const uint2 e = dyn_list[two || w == 0 ? i + w : i];     // same entry in every lane
-                pos[w] = __builtin_amdgcn_readfirstlane((int)e.x);
-                h[w] = __uint_as_float(e.y);
-            }
-            for (int rs = t_begin; rs < T && (alive[0] || alive[1]); rs += 64) {
-                const int nvalid = T - rs < 64 ? T - rs : 64;
-                const Stage<D> st = lane_stage(rs);
-                uint32_t entered_t = 0;
-                bool rej[2] = {false, false};
-                if (alive[0] && alive[1]) {
-                    pass(WbInt<2>{}, st, nvalid, pos, h, rej, entered_t);
-                } else {
-                    const int k = alive[0] ? 0 : 1;
-                    pass(WbInt<1>{}, st, nvalid, pos + k, h + k, rej + k, entered_t);
-                }
-                if (entered_t) atomicAdd(&hist[rs + lane], entered_t);
-                alive[0] = alive[0] && !rej[0];
-                alive[1] = alive[1] && !rej[1];
-            }
-#pragma unroll
-            for (int w = 0; w < 2; ++w) {
-                if (!alive[w]) continue;                              // wave-uniform
-                if (lane == 0) {
-                    const uint32_t shard = shard_of((pos[w] >> 6) / RPW);         // (the shard of the window's own rows)
-                    const uint32_t slot = atomicAdd(a.det_count + shard, 1u);
-                    if (slot < a.det_cap) {
-                        WbDet d;
-                        d.image = b;
-                        d.level = tile_d.level;
-                        d.r = (uint16_t)(r0 + (pos[w] >> 6));
-                        d.c = (uint16_t)(c0 + (pos[w] & 63));
-                        d.score = h[w];
-                        a.det[(size_t)shard * a.det_cap + slot] = d;
-                    }
-                }
-            }
+            finish_rows(dyn_list, i, dyn_total, t_begin);
         }
-    } else {
-        // a wave's own queue (it left the segments with a few windows): pass by pass, the survivors re-packed in place
-        for (int rs = t_begin; rs < T && n_q > 0; rs += 64) {
-            const int nvalid = T - rs < 64 ? T - rs : 64;
-            const Stage<D> st = lane_stage(rs);
-            int n_out = 0;
-            uint32_t entered_t = 0;                              // windows that entered stage rs + lane in this pass
-            auto windows = [&](auto w_tag, int i) WB_INLINE_LAMBDA {
-                constexpr int W = decltype(w_tag)::value;
-                int pos[W];
-                float h[W];
-                bool rej[W];
-#pragma unroll
-                for (int w = 0; w < W; ++w) {
-                    const uint2 e = queue[i + w];                    // same entry in every lane
-                    pos[w] = __builtin_amdgcn_readfirstlane((int)e.x);
-                    h[w] = __uint_as_float(e.y);
-                }
-                pass(w_tag, st, nvalid, pos, h, rej, entered_t);
-#pragma unroll
-                for (int w = 0; w < W; ++w) {
-                    if (rej[w]) continue;
-                    if (lane == 0) queue[n_out] = make_uint2((uint32_t)pos[w], __float_as_uint(h[w]));   // n_out <= i + w: entries read above
-                    ++n_out;
-                }
-            };
-            int i = 0;
-            if constexpr (WB_TAIL_W == 2)
-                for (; i + 1 < n_q; i += 2) windows(WbInt<2>{}, i);
-            for (; WB_TAIL_W != 2 && i + 1 < n_q; ++i) windows(WbInt<1>{}, i);
-            if (i < n_q) windows(WbInt<1>{}, i);
-            if (entered_t) atomicAdd(&hist[rs + lane], entered_t);
-            n_q = n_out;
-        }
+    } else if (t_begin < T) {
+        // a wave's own queue (it left the segments with a few windows), four windows at a time
+        for (int i = 0; i < n_q; i += 4) finish_rows(queue, i, n_q, t_begin);
+        n_q = 0;
     }
 
     __builtin_amdgcn_s_setprio(0);

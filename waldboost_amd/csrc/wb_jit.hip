@@ -165,7 +165,7 @@ int compile(const std::string &src, const char *arch, std::vector<char> &code, s
         return WB_ERR_HIP;
     }
     const std::string a = std::string("--offload-arch=") + arch;
-    std::vector<std::string> extra;                          // diagnostic: WB_JIT_DEFS="-DWB_TAIL_W=1 -D..." (A/B builds)
+    std::vector<std::string> extra;                          // diagnostic: WB_JIT_DEFS="-DWB_TAIL_PRIO=0 -D..." (A/B builds)
     if (const char *e = getenv("WB_JIT_DEFS")) {
         std::string cur;
         for (const char *c = e;; ++c) {
