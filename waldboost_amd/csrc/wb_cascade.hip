@@ -535,7 +535,8 @@ extern "C" int wb_tree_eval_launch(void *stream, const void *X, int x_dtype, int
                "wb_tree_eval_launch: null pointer");
     WB_REQUIRE(u > 0 && v > 0 && C > 0 && n_nodes > 0 && n_nodes <= 127, "wb_tree_eval_launch: bad shape");
     WB_REQUIRE(x_dtype == WB_DTYPE_F32 || x_dtype == WB_DTYPE_U8, "wb_tree_eval_launch: channel dtype %d (float32 or uint8)", x_dtype);
-    int64_t blocks = (n_pos + 255) / 256;
+    const int64_t blocks = (n_pos + 255) / 256;
+    WB_REQUIRE(blocks <= 0x7fffffff, "wb_tree_eval_launch: too many windows for one launch");
     hipLaunchKernelGGL(tree_eval_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, X,
                        (int)(x_dtype == WB_DTYPE_U8), u, v, C, rs, cs, n_pos, feature, threshold, left, right, prediction, n_nodes, out);
     WB_HIP_CHECK(hipGetLastError());
