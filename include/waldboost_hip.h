@@ -823,6 +823,50 @@ int wb_verify_train_step(void *stream, const void *X, int x_dtype, const float *
                          int32_t *t, const WbVerifyTrainHyper *hyper, void *scratch, size_t scratch_bytes, float *loss_out,
                          float *grads_out);
 
+/* Box regression: a linear map from a window's channel values to four box offsets (the reference computes the target,
+ * samples.py:152-157 get_regression_target, and never uses it).  DESIGN.md 4.15 has the rule, tests/regress_reference.py
+ * states it in NumPy.  New symbols of ABI 8 (the version number did not change: nothing that existed did).
+ *
+ * wb_gram_launch: S += A^T A for A = [X | 1 | T], n_rows x P, P = D + 5, in float64 -- the streaming normal equations.
+ *   X        dev [n_rows][D], x_dtype WB_DTYPE_U8 or WB_DTYPE_F32 (4-byte aligned), widened exactly
+ *   T        dev double [n_rows][4];  S dev double [P][P], read and updated; symmetric on entry (its upper triangle is
+ *            what is read; every entry is written)
+ *   scratch  dev, 8-byte aligned, wb_gram_scratch_bytes(n_rows, D) bytes; its content on entry does not matter
+ * The contraction runs on v_mfma_f64_16x16x4_f64, tile pairs ti <= tj only.  Determinism is part of the contract and there
+ * are no floating-point atomics: rows are cut into chunks of WB_GRAM_CHUNK, whatever the grid; every (tile, chunk) partial
+ * goes to scratch; a second launch adds a tile's partials in ascending chunk order, adds that sum to S and writes the
+ * mirrored entry with the same bits.  So the result depends on the inputs and the sequence of calls alone, is bitwise
+ * symmetric and the same from run to run.  Rows past n_rows count as zeros.  Inside a chunk the order of the adds is the
+ * instruction's: a result lies within (n_rows + 8) * 2^-52 * (|A|^T |A|) of the exact one, and is exact while the
+ * integers stay below 2^53.
+ * n_rows == 0: WB_OK without a launch.  P > WB_GRAM_MAX_P, more than 2^26 rows or another x_dtype: WB_ERR_UNSUPPORTED.
+ * Null or misaligned pointers, negative sizes, D < 1, a short scratch: WB_ERR_INVALID.  Two launches, no host synchronisation.
+ *
+ * wb_regress_predict_launch: pred[i][k] = sum_j X[i][j] * Wb[j][k] + Wb[D][k] on crops X [n][m][nn][C] (x_dtype as above),
+ *   D = m * nn * C, feature j = (r * nn + c) * C + ch; Wb dev double [D + 1][4] (the last row is the intercept), pred dev
+ *   double [n][4].  One wave per window, in a fixed order: lane l of 64 keeps four float64 partials from 0 and adds
+ *   x[j] * Wb[j][k] for j = l, l + 64, ... ascending (product and sum rounded separately); then for s = 32, 16, 8, 4, 2, 1:
+ *   p[l] = p[l] + p[l ^ s]; pred[k] = p[0][k] + Wb[D][k].
+ * wb_regress_apply_launch: the same on windows read where they lie in the pyramid -- buf, dtype, img_stride, n_images,
+ *   levels, n_levels, C and the error word exactly as for wb_mine_gather_launch; det dev WbDet [n_det], 16-byte aligned;
+ *   inv_scale dev float [n_levels] as for wb_boxes_launch; inv64 dev double [n_levels] = 1.0 / scale, computed on the host.
+ *   boxes dev float [n_det][4]: float32(float64(box) - pred * inv64[level]), box = float32 [c, r, c+nn, r+m] *
+ *   inv_scale[level]; pred dev double [n_det][4] or NULL.  A record whose image or level is out of range, whose window
+ *   leaves its level or whose level leaves the image's stride sets err[0] = 1 and gets its unrefined box (of the level
+ *   clamped into range) and a zero pred: nothing outside n_images * img_stride elements is read.  No crop is materialised.
+ * n == 0: nothing is launched (apply clears err).  More than 2^26 windows or another dtype: WB_ERR_UNSUPPORTED.  Null or
+ * misaligned pointers and negative sizes: WB_ERR_INVALID.  One launch (apply: and one memset), no host synchronisation. */
+#define WB_GRAM_CHUNK 256
+#define WB_GRAM_MAX_P 2048
+int wb_gram_scratch_bytes(int64_t n_rows, int D, size_t *bytes);
+int wb_gram_launch(void *stream, const void *X, int x_dtype, const double *T, int64_t n_rows, int D, double *S, void *scratch,
+                   size_t scratch_bytes);
+int wb_regress_predict_launch(void *stream, const void *X, int x_dtype, int64_t n, int m, int nn, int C, const double *Wb,
+                              double *pred);
+int wb_regress_apply_launch(void *stream, const void *buf, int dtype, int64_t img_stride, int n_images, const WbMineLevel *levels,
+                            int n_levels, int C, const WbDet *det, int64_t n_det, int m, int nn, const double *Wb,
+                            const float *inv_scale, const double *inv64, double *pred, float *boxes, uint32_t *err);
+
 /* Device self-test: the uint8 fast path of the orientation projection (fp32 arithmetic that is
  * proven equal to the reference's fp64 formula for integer gradients) is compared with the fp64
  * formula for every (gx, gy) in [-1020, 1020]^2; *mismatches (dev uint32, zeroed by the caller)

@@ -6,7 +6,7 @@ Keeps the reference surface for that path (reference waldboost/__init__.py:50-72
 All compute runs in hand-written HIP kernels (csrc/) through the C ABI in
 include/waldboost_hip.h; there is no CPU fallback.
 """
-from . import calibration, channels, fpga, model_pb2, samples, testing, verification
+from . import calibration, channels, fpga, model_pb2, regression, samples, testing, verification
 from .boxes import Boxes, concatenate, match_boxes, non_max_suppression
 from .calibration import calibrate, prune_instances
 from .model import Model
@@ -131,5 +131,5 @@ def train(model, training_images, learner=None, pool=None, length=64, theta_sche
 
 default_channel_opts = dict(shrink=2, n_per_oct=8, smooth=1, channels=channels.grad_hist)
 
-__all__ = ["Model", "DTree", "Boxes", "concatenate", "non_max_suppression", "match_boxes", "SamplePool", "DeviceSamplePool", "channels", "fpga", "samples", "testing", "verification", "calibration", "calibrate", "prune_instances", "detect", "load", "load_model", "save", "save_model",
+__all__ = ["Model", "DTree", "Boxes", "concatenate", "non_max_suppression", "match_boxes", "SamplePool", "DeviceSamplePool", "channels", "fpga", "samples", "testing", "verification", "calibration", "regression", "calibrate", "prune_instances", "detect", "load", "load_model", "save", "save_model",
            "default_channel_opts", "train", "Learner", "BasicRejectionSchedule"]

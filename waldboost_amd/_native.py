@@ -45,6 +45,8 @@ CART_SPLIT_DTYPE = np.dtype([("feature", "<i4"), ("n_left", "<i4"), ("lo", "<f4"
 assert CART_SPLIT_DTYPE.itemsize == 40
 WB_CART_MAX_SAMPLES = 65536
 WB_CART_MAX_FEATURES = 65536
+WB_GRAM_CHUNK = 256
+WB_GRAM_MAX_P = 2048
 
 
 class WbModelInfo(C.Structure):
@@ -143,6 +145,11 @@ SYMBOLS = {
     "wb_verify_train_scratch_bytes": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int64, C.POINTER(C.c_size_t)]),
     "wb_verify_train_step": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int64, _P, C.c_int64, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P,
                                        _P, _P, C.c_size_t, _P, _P]),
+    "wb_gram_scratch_bytes": (C.c_int, [C.c_int64, C.c_int, C.POINTER(C.c_size_t)]),
+    "wb_gram_launch": (C.c_int, [_P, _P, C.c_int, _P, C.c_int64, C.c_int, _P, _P, C.c_size_t]),
+    "wb_regress_predict_launch": (C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "wb_regress_apply_launch": (C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int, _P, C.c_int, C.c_int, _P, C.c_int64, C.c_int, C.c_int, _P,
+                                          _P, _P, _P, _P, _P]),
 }
 
 _lib = None
