@@ -54,6 +54,9 @@
  *   no reference counterpart (its thetas are fitted during training only, training.py fit_rejection_threshold): the
  *        running score of a sample after every stage and the pruning minimum, for threshold calibration
  *        -> wb_samples_trace_launch, wb_calib_min_launch
+ *   no reference counterpart (the reference stops at non_max_suppression): the boxes NMS kept, each merged with the live
+ *        boxes of its cluster and counted
+ *        -> wb_vote_launch
  */
 #ifndef WALDBOOST_HIP_H
 #define WALDBOOST_HIP_H
@@ -571,6 +574,40 @@ int wb_nms_finish_launch(void *stream, const void *fin, uint32_t out_capacity, i
 int wb_match_launch(void *stream, const double *dt /* [n_dt][4] */, const int32_t *dt_image /* [n_dt] */,
                     const double *gt /* [n_gt][4] */, const int32_t *gt_off /* [n_images + 1] */,
                     int64_t n_dt, int64_t n_gt, int n_images, double *best /* [n_dt] */, int32_t *owner /* [n_dt] */);
+
+/* Box voting: every box that non-maximum suppression kept becomes the weighted mean of the boxes of its cluster, and the
+ * cluster is counted (Viola-Jones's merge of overlapping detections; OpenCV's minNeighbors).  DESIGN.md 4.16 has the rule,
+ * tests/vote_reference.py states it in NumPy.  New symbol of ABI 8 (the version number did not change: nothing that existed did).
+ *   boxes    dev float32 [n][4] XYXY, 16-byte aligned;  scores dev float32 [n], no NaN;  group dev int32 [n] or NULL (one group)
+ *   keep     dev uint8 [n] as wb_nms_launch wrote it (any non-zero byte: kept)
+ *   merged   dev float32 [n][4], 16-byte aligned, not overlapping boxes;  votes dev int32 [n]
+ *   * a box is LIVE unless use_score_threshold != 0 and `not (score >= score_threshold)` -- the boxes NMS dropped first;
+ *   * for a kept box k, box j is a VOTER when j == k (always, even for a box of no area, whose iou with itself is 0), or when
+ *     j is live, group[j] == group[k] and iou(box_k, box_j) >= vote_iou (a double);
+ *   * iou exactly as for wb_nms_launch / wb_match_launch: float64 on the float32 coordinates, every operation rounded on
+ *     its own, the divide correctly rounded;
+ *   * weights WB_VOTE_UNIFORM: w_j = 1.0;  WB_VOTE_SCORE: w_j = float64(score_j) - float64(score_threshold), >= 0 for every
+ *     live box; the mode needs use_score_threshold, and a box that is not live never votes except for itself;
+ *   * the order of the sums is fixed and part of the contract (it does not depend on the launch geometry, on chunking or on
+ *     the run): lane l of 64 visits the candidates j = l, l + 64, l + 128, ... ascending and for each voter computes
+ *     sw = sw + w and, for each of the four coordinates, sc[i] = sc[i] + (w * float64(x_ji)) -- the product rounded first,
+ *     then the sum, no fused multiply-add; the 64 partials of each of the five doubles and of the integer vote count are
+ *     combined by a butterfly: for s = 1, 2, 4, 8, 16, 32: p = p + p[lane ^ s];
+ *   * merged[k][i] = float32(sc[i] / sw) when sw > 0 (the divide correctly rounded, the cast round-to-nearest-even); when sw
+ *     is not > 0 (every voter exactly at the threshold) box k's own coordinates;  votes[k] = the number of voters, >= 1;
+ *   * the row of a box that is not kept holds its own box and votes = 0.  Every row is written.
+ * Cost: K * n float64 IoU tests, K the number of kept boxes.  One wave per box, candidates staged through LDS 256 at a time
+ * and shared by a workgroup's four waves.
+ * n == 0 launches nothing (WB_OK, pointers not looked at); n > 2^26 is WB_ERR_UNSUPPORTED; null pointers (group may be
+ * NULL), misaligned pointers, a negative n, a NaN or negative vote_iou, a NaN score_threshold in use, an unknown weights
+ * code and WB_VOTE_SCORE without a threshold are WB_ERR_INVALID, refused before any HIP call.  One launch, no atomics, no
+ * scratch, no host synchronisation. */
+#define WB_VOTE_UNIFORM 0
+#define WB_VOTE_SCORE 1
+int wb_vote_launch(void *stream, const float *boxes, const float *scores, const int32_t *group,
+                   const uint8_t *keep, int64_t n, double vote_iou, int weights,
+                   int use_score_threshold, float score_threshold,
+                   float *merged, int32_t *votes);
 
 /* Hard-negative mining of a scanned batch: label, choose and crop on the device (reference samples.py:46-216 label_boxes,
  * select_candidates, gather_samples; DESIGN.md 4.12 has the rule, tests/mine_reference.py states it in NumPy).

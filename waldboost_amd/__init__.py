@@ -7,7 +7,7 @@ All compute runs in hand-written HIP kernels (csrc/) through the C ABI in
 include/waldboost_hip.h; there is no CPU fallback.
 """
 from . import calibration, channels, fpga, model_pb2, regression, samples, testing, verification
-from .boxes import Boxes, concatenate, match_boxes, non_max_suppression
+from .boxes import Boxes, concatenate, match_boxes, merge_detections, non_max_suppression
 from .calibration import calibrate, prune_instances
 from .model import Model
 from .samples import DeviceSamplePool, SamplePool
@@ -25,7 +25,8 @@ def save_model(model, filename):
 
 save = save_model
 
-def detect(image, *models, channel_opts=None, response_scale=None, iou_threshold=None, score_threshold=None, separate=False):
+def detect(image, *models, channel_opts=None, response_scale=None, iou_threshold=None, score_threshold=None, separate=False,
+           vote_iou=None, vote_weights="uniform", min_votes=1):
     """Detect objects with several models sharing one channel pyramid (reference
     waldboost/__init__.py:75-130): returns Boxes with 'scores' (multiplied by response_scale[k]) and
     'label' (index of the model that fired).  Order: pyramid level, then model, then row-major
@@ -34,13 +35,18 @@ def detect(image, *models, channel_opts=None, response_scale=None, iou_threshold
     iou_threshold, score_threshold, separate: non-maximum suppression of that result (the reference's detection script,
     scripts/waldboost-detect.py:36; semantics: non_max_suppression), on the scaled scores; separate=True: boxes of
     different models never suppress each other ('label' is the group), False: all boxes are one group.  None: no
-    suppression."""
+    suppression.
+    vote_iou (needs an iou_threshold), vote_weights, min_votes: box voting -- merge_detections of the complete, unsuppressed
+    result with these thresholds and the same groups (separate=True: boxes of different models never vote for each other):
+    every kept box becomes the mean of its cluster and gets a 'votes' field, kept boxes with fewer than min_votes voters are
+    left out.  That is a second device round trip after the read-back.  None: exactly the call without it."""
     import numpy as np
     from . import engine as _engine
-    from .model import _nms_args
+    from .model import _nms_args, _vote_args
     if not models:
         raise ValueError("detect needs at least one model")
     nms = _nms_args(iou_threshold, score_threshold)
+    vote = _vote_args(nms, vote_iou, vote_weights, min_votes)
     channel_opts = channel_opts or models[0].channel_opts
     if response_scale is None:
         response_scale = [1] * len(models)
@@ -89,7 +95,9 @@ def detect(image, *models, channel_opts=None, response_scale=None, iou_threshold
     out = Boxes(boxes.reshape(-1, 4).astype(np.float32, copy=False))
     out.set_field("scores", scores.astype(np.float32, copy=False))
     out.set_field("label", label[order])
-    if nms is not None:
+    if vote is not None:
+        out = merge_detections(out, group=out.get_field("label") if separate else None, **vote)
+    elif nms is not None:
         out = non_max_suppression(out, nms[0], nms[1], group=out.get_field("label") if separate else None)
     return out
 
@@ -131,5 +139,5 @@ def train(model, training_images, learner=None, pool=None, length=64, theta_sche
 
 default_channel_opts = dict(shrink=2, n_per_oct=8, smooth=1, channels=channels.grad_hist)
 
-__all__ = ["Model", "DTree", "Boxes", "concatenate", "non_max_suppression", "match_boxes", "SamplePool", "DeviceSamplePool", "channels", "fpga", "samples", "testing", "verification", "calibration", "regression", "calibrate", "prune_instances", "detect", "load", "load_model", "save", "save_model",
+__all__ = ["Model", "DTree", "Boxes", "concatenate", "non_max_suppression", "merge_detections", "match_boxes", "SamplePool", "DeviceSamplePool", "channels", "fpga", "samples", "testing", "verification", "calibration", "regression", "calibrate", "prune_instances", "detect", "load", "load_model", "save", "save_model",
            "default_channel_opts", "train", "Learner", "BasicRejectionSchedule"]

@@ -47,6 +47,7 @@ WB_CART_MAX_SAMPLES = 65536
 WB_CART_MAX_FEATURES = 65536
 WB_GRAM_CHUNK = 256
 WB_GRAM_MAX_P = 2048
+WB_VOTE_UNIFORM, WB_VOTE_SCORE = 0, 1
 
 
 class WbModelInfo(C.Structure):
@@ -123,6 +124,7 @@ SYMBOLS = {
     "wb_nms_finish_scratch_bytes": (C.c_int, [C.c_uint32, C.c_int, C.POINTER(C.c_size_t)]),
     "wb_nms_finish_launch": (C.c_int, [_P, _P, C.c_uint32, C.c_int, C.c_double, C.c_int, C.c_float, _P, C.c_size_t, _P]),
     "wb_match_launch": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int, _P, _P]),
+    "wb_vote_launch": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_double, C.c_int, C.c_int, C.c_float, _P, _P]),
     "wb_mine_scratch_bytes": (C.c_int, [C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
     "wb_mine_select_launch": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_int64, _P, C.c_int, C.c_double,
                                         C.c_double, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_uint32, _P, C.c_size_t, _P, C.c_int64, _P]),

@@ -178,12 +178,8 @@ def match_boxes(dt_boxes, gt_boxes_per_image, dt_image=None):
 _NMS_RANK_MAX = 1 << 16      # most boxes wb_nms_launch orders itself (a quadratic pass); above: torch.sort + wb_nms_ordered_launch
 
 
-def nms_keep_mask(boxes, scores, iou_threshold=0.5, score_threshold=None, group=None):
-    """Keep flags (bool [N], input order) of greedy non-maximum suppression, computed on the GPU (wb_nms_launch): the
-    arrays are uploaded, the flags read back.  See non_max_suppression for the semantics.  More than 2**16 boxes are put
-    in visiting order by a stable torch.sort on the device and go through wb_nms_ordered_launch: every N a detect call
-    can return (2**26) is accepted; the cost grows with N * N (include/waldboost_hip.h has the figures)."""
-    from . import _native as nat
+def _nms_inputs(boxes, scores, iou_threshold, score_threshold, group):
+    """The checked arguments of an NMS call: (boxes float32 [n][4], scores float32 [n], iou_threshold, group int32 [n] or None)."""
     boxes = np.ascontiguousarray(boxes, np.float32).reshape(-1, 4)
     scores = np.ascontiguousarray(scores, np.float32).reshape(-1)
     n = scores.size
@@ -199,29 +195,48 @@ def nms_keep_mask(boxes, scores, iou_threshold=0.5, score_threshold=None, group=
         if group.size != n:
             raise ValueError(f"{group.size} group entries, {n} boxes")
         group = np.unique(group, return_inverse=True)[1].astype(np.int32).reshape(-1)     # (any dtype: equality is all that counts)
-    if n == 0:
-        return np.zeros(0, bool)
+    return boxes, scores, iou_threshold, group
+
+
+def _nms_enqueue(lib, dev, p_boxes, d_scores, p_group, n, iou_threshold, score_threshold):
+    """Greedy NMS of n > 0 boxes that lie on the device already (p_boxes, p_group: device pointers, the group's may be
+    null; d_scores: a float32 tensor), enqueued on the current stream: the device bytes n_keep (uint32) | keep flags [n]."""
     import ctypes as C
     import torch
-    lib = nat.load()
-    dev = nat.require_gpu()
+    from . import _native as nat
     need = C.c_size_t()
     nat.check(lib.wb_nms_scratch_bytes(n, C.byref(need)), "wb_nms_scratch_bytes")
-    d_boxes = torch.from_numpy(boxes).to(dev)
-    d_scores = torch.from_numpy(scores).to(dev)
-    d_group = torch.from_numpy(group).to(dev) if group is not None else None
     scratch = torch.empty(need.value, dtype=torch.uint8, device=dev)
     out = torch.empty(4 + n, dtype=torch.uint8, device=dev)           # n_keep | keep flags: one read-back
     tail = (n, iou_threshold, 0 if score_threshold is None else 1, 0.0 if score_threshold is None else float(np.float32(score_threshold)),
             nat.ptr(scratch), scratch.numel(), C.c_void_p(out.data_ptr() + 4), nat.ptr(out))
     if n <= _NMS_RANK_MAX:
-        nat.check(lib.wb_nms_launch(nat.stream_ptr(), nat.ptr(d_boxes), nat.ptr(d_scores), nat.ptr(d_group), *tail), "wb_nms_launch")
+        nat.check(lib.wb_nms_launch(nat.stream_ptr(), p_boxes, nat.ptr(d_scores), p_group, *tail), "wb_nms_launch")
     else:
         # descending, the two zeros one value (-(s + 0) is -0.0 for both), equal scores in input order
         order = torch.sort(-(d_scores + 0.0), stable=True).indices.to(torch.int32)
-        nat.check(lib.wb_nms_ordered_launch(nat.stream_ptr(), nat.ptr(d_boxes), nat.ptr(d_scores), nat.ptr(d_group), nat.ptr(order), *tail),
+        nat.check(lib.wb_nms_ordered_launch(nat.stream_ptr(), p_boxes, nat.ptr(d_scores), p_group, nat.ptr(order), *tail),
                   "wb_nms_ordered_launch")
-    h = out.cpu().numpy()
+    return out
+
+
+def nms_keep_mask(boxes, scores, iou_threshold=0.5, score_threshold=None, group=None):
+    """Keep flags (bool [N], input order) of greedy non-maximum suppression, computed on the GPU (wb_nms_launch): the
+    arrays are uploaded, the flags read back.  See non_max_suppression for the semantics.  More than 2**16 boxes are put
+    in visiting order by a stable torch.sort on the device and go through wb_nms_ordered_launch: every N a detect call
+    can return (2**26) is accepted; the cost grows with N * N (include/waldboost_hip.h has the figures)."""
+    from . import _native as nat
+    boxes, scores, iou_threshold, group = _nms_inputs(boxes, scores, iou_threshold, score_threshold, group)
+    n = scores.size
+    if n == 0:
+        return np.zeros(0, bool)
+    import torch
+    lib = nat.load()
+    dev = nat.require_gpu()
+    d_boxes = torch.from_numpy(boxes).to(dev)
+    d_scores = torch.from_numpy(scores).to(dev)
+    d_group = torch.from_numpy(group).to(dev) if group is not None else None
+    h = _nms_enqueue(lib, dev, nat.ptr(d_boxes), d_scores, nat.ptr(d_group), n, iou_threshold, score_threshold).cpu().numpy()
     keep = h[4:].astype(bool)
     assert int(h[:4].view(np.uint32)[0]) == int(keep.sum())
     return keep
@@ -245,3 +260,129 @@ def non_max_suppression(boxes, iou_threshold=0.5, score_threshold=None, group=No
         return boxes[np.zeros(0, np.intp)]
     keep = nms_keep_mask(boxes.get(), boxes.get_field("scores"), iou_threshold, score_threshold, group)
     return boxes[np.flatnonzero(keep)]
+
+
+VOTE_WEIGHTS = ("uniform", "score")      # WB_VOTE_UNIFORM, WB_VOTE_SCORE
+
+
+def _vote_inputs(boxes, scores, vote_iou, weights, score_threshold, min_votes=1):
+    """The checked arguments of a voting call: (vote_iou, weights code, float32 score_threshold or None, min_votes)."""
+    vote_iou = float(vote_iou)
+    if not vote_iou >= 0.0:
+        raise ValueError("vote_iou must be a number >= 0")
+    if weights not in VOTE_WEIGHTS:
+        raise ValueError(f"weights must be one of {VOTE_WEIGHTS}, not {weights!r}")
+    if score_threshold is not None:
+        score_threshold = float(np.float32(score_threshold))
+        if score_threshold != score_threshold:
+            raise ValueError("score_threshold is NaN")
+    elif weights == "score":
+        raise ValueError('"score" weights are measured from the score threshold: give a score_threshold')
+    if not np.isfinite(boxes).all():
+        raise ValueError("box voting: coordinates must be finite")
+    if np.isnan(scores).any():
+        raise ValueError("box voting: scores must not be NaN")
+    if int(min_votes) != min_votes or min_votes < 0:
+        raise ValueError("min_votes must be an integer >= 0")
+    return vote_iou, VOTE_WEIGHTS.index(weights), score_threshold, int(min_votes)
+
+
+def _vote_enqueue(lib, d_boxes, d_scores, d_group, d_keep, n, vote_iou, code, score_threshold, d_merged, d_votes):
+    """wb_vote_launch on device pointers (ctypes), on the current stream."""
+    from . import _native as nat
+    nat.check(lib.wb_vote_launch(nat.stream_ptr(), d_boxes, d_scores, d_group, d_keep, n, vote_iou, code, 0 if score_threshold is None else 1,
+                                 0.0 if score_threshold is None else score_threshold, d_merged, d_votes), "wb_vote_launch")
+
+
+def _upload_boxes(dev, boxes, scores, group, keep=None):
+    """One upload of boxes | scores | group | keep (the absent ones left out): (the device bytes, ctypes pointers by name)."""
+    import ctypes as C
+    import torch
+    parts = dict(boxes=boxes.reshape(-1), scores=scores)
+    if group is not None:
+        parts["group"] = group
+    if keep is not None:
+        parts["keep"] = keep
+    blob = torch.from_numpy(np.concatenate([p.view(np.uint8) for p in parts.values()])).to(dev)
+    offs = np.cumsum([0] + [p.nbytes for p in parts.values()])
+    at = {k: C.c_void_p(blob.data_ptr() + int(o)) for k, o in zip(parts, offs)}
+    at.setdefault("group", C.c_void_p(0))
+    return blob, at, {k: int(o) for k, o in zip(parts, offs)}
+
+
+def vote_boxes(boxes, scores, keep, vote_iou=0.5, weights="uniform", score_threshold=None, group=None):
+    """Box voting: (merged float32 [N][4], votes int32 [N]).  Every box that `keep` (uint8 / bool [N], as nms_keep_mask
+    answers) marks becomes the weighted mean of its VOTERS and `votes` counts them; a row that is not kept holds its own box
+    and 0 votes.
+
+    A box is live unless ``not (score >= float32(score_threshold))`` -- the boxes NMS dropped first.  Box j votes for the
+    kept box k when j is k itself (always), or when j is live, of k's group and ``iou(box_k, box_j) >= vote_iou`` (`iou`
+    being this module's float64 function).  weights: "uniform", every voter counts 1; "score", a voter counts
+    ``float64(score) - float64(float32(score_threshold))`` (needs a score_threshold).  The sums are float64 in a fixed order
+    (include/waldboost_hip.h, wb_vote_launch; tests/vote_reference.py states the whole rule in NumPy), so the result is the
+    same bits on every run.  When the weights sum to 0 (every voter exactly at the threshold) a kept box stays as it is.
+
+    Runs on the GPU (wb_vote_launch: K * N IoU tests for K kept boxes): one upload, one launch, one read-back; no CPU
+    fallback.  Coordinates must be finite, scores not NaN (ValueError, like every bad argument, before the device is
+    touched).  An empty input returns empty arrays without touching the device."""
+    from . import _native as nat
+    boxes, scores, _, group = _nms_inputs(boxes, scores, 0.0, score_threshold, group)
+    n = scores.size
+    keep = np.ascontiguousarray(np.asarray(keep).reshape(-1) != 0, np.uint8)
+    if keep.size != n:
+        raise ValueError(f"{keep.size} keep flags, {n} boxes")
+    vote_iou, code, score_threshold, _ = _vote_inputs(boxes, scores, vote_iou, weights, score_threshold)
+    if n == 0:
+        return np.zeros((0, 4), np.float32), np.zeros(0, np.int32)
+    import ctypes as C
+    import torch
+    lib = nat.load()
+    dev = nat.require_gpu()
+    blob, at, _ = _upload_boxes(dev, boxes, scores, group, keep)
+    out = torch.empty(20 * n, dtype=torch.uint8, device=dev)          # merged | votes: one read-back
+    _vote_enqueue(lib, at["boxes"], at["scores"], at["group"], at["keep"], n, vote_iou, code, score_threshold, nat.ptr(out),
+                  C.c_void_p(out.data_ptr() + 16 * n))
+    h = out.cpu().numpy()
+    return h[:16 * n].view(np.float32).reshape(n, 4).copy(), h[16 * n:].view(np.int32).copy()
+
+
+def merge_detections(boxes, iou_threshold=0.5, score_threshold=None, group=None, vote_iou=0.5, weights="uniform", min_votes=1):
+    """Greedy non-maximum suppression of a Boxes with a 'scores' field, exactly as non_max_suppression does it, and then box
+    voting (vote_boxes has the rule): every kept box is replaced by the weighted mean of the boxes of its cluster -- itself
+    and the live boxes of its group with ``iou >= vote_iou`` to it -- so the suppressed windows still say where the object is.
+
+    Returns the kept boxes in input order, every field sliced; the coordinates are the merged ones; 'scores' is unchanged (it
+    is the score of the cluster's mode); a new int32 field 'votes' counts each box's voters (>= 1).  Kept boxes with
+    ``votes < min_votes`` are left out (an isolated firing is more often a false alarm than a cluster is); NMS is NOT run
+    again after that, so a box such a kept box had suppressed does not come back.
+
+    Runs on the GPU: one upload, the NMS launches and wb_vote_launch on the same device arrays, one read-back; no CPU
+    fallback.  Bad arguments raise ValueError before the device is touched.  An empty Boxes is returned as an empty Boxes
+    (with a 'votes' field) without touching the device."""
+    from . import _native as nat
+    if not boxes.has_field("scores"):
+        raise ValueError("merge_detections needs a 'scores' field")
+    b, s, iou_threshold, g = _nms_inputs(boxes.get(), boxes.get_field("scores"), iou_threshold, score_threshold, group)
+    vote_iou, code, score_threshold, min_votes = _vote_inputs(b, s, vote_iou, weights, score_threshold, min_votes)
+    n = s.size
+    if n == 0:
+        out = boxes[np.zeros(0, np.intp)]
+        out.set_field("votes", np.zeros(0, np.int32))
+        return out
+    import ctypes as C
+    import torch
+    lib = nat.load()
+    dev = nat.require_gpu()
+    blob, at, offs = _upload_boxes(dev, b, s, g)
+    d_scores = blob[offs["scores"]:offs["scores"] + 4 * n].view(torch.float32)            # (what the sort of the long path reads)
+    flags = _nms_enqueue(lib, dev, at["boxes"], d_scores, at["group"], n, iou_threshold, score_threshold)
+    out = torch.empty(20 * n, dtype=torch.uint8, device=dev)
+    _vote_enqueue(lib, at["boxes"], at["scores"], at["group"], C.c_void_p(flags.data_ptr() + 4), n, vote_iou, code, score_threshold,
+                  nat.ptr(out), C.c_void_p(out.data_ptr() + 16 * n))
+    h = torch.cat([out, flags[4:]]).cpu().numpy()                     # merged | votes | keep flags: one read-back
+    merged, votes, keep = h[:16 * n].view(np.float32).reshape(n, 4), h[16 * n:20 * n].view(np.int32), h[20 * n:].astype(bool)
+    idx = np.flatnonzero(keep & (votes >= min_votes))
+    res = boxes[idx]
+    res = Boxes(merged[idx].copy(), **{k: res.get_field(k) for k in res.fields()})
+    res.set_field("votes", votes[idx].copy())
+    return res

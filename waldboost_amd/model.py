@@ -14,7 +14,7 @@ from . import _native as nat
 from . import channels as _channels
 from . import engine as _engine
 from . import model_pb2
-from .boxes import Boxes, nms_keep_mask
+from .boxes import VOTE_WEIGHTS, Boxes, merge_detections, nms_keep_mask
 from .channels import channel_pyramid
 from .compare import channel_tensor
 from .readback import Detections, from_finished, from_image_result, from_ordered, from_packed
@@ -63,6 +63,25 @@ def _nms_args(iou_threshold, score_threshold):
         if score_threshold != score_threshold:
             raise ValueError("score_threshold is NaN")
     return iou_threshold, score_threshold
+
+
+def _vote_args(nms, vote_iou, vote_weights, min_votes):
+    """The keywords of merge_detections for a detect call with vote_iou=, or None for a call without (the other two are
+    not looked at then).  Voting merges the clusters NMS reduces to one box each: it needs an iou_threshold."""
+    if vote_iou is None:
+        return None
+    if nms is None:
+        raise ValueError("vote_iou merges what non-maximum suppression keeps: give an iou_threshold too")
+    vote_iou = float(vote_iou)
+    if not vote_iou >= 0.0:
+        raise ValueError("vote_iou must be a number >= 0")
+    if vote_weights not in VOTE_WEIGHTS:
+        raise ValueError(f"vote_weights must be one of {VOTE_WEIGHTS}, not {vote_weights!r}")
+    if vote_weights == "score" and nms[1] is None:
+        raise ValueError('"score" vote weights are measured from the score threshold: give a score_threshold')
+    if int(min_votes) != min_votes or min_votes < 0:
+        raise ValueError("min_votes must be an integer >= 0")
+    return dict(iou_threshold=nms[0], score_threshold=nms[1], vote_iou=vote_iou, weights=vote_weights, min_votes=int(min_votes))
 
 
 def _suppress(res, nms):
@@ -256,16 +275,22 @@ class Model:
         return d["r"].astype(np.int64), d["c"].astype(np.int64), d["score"].copy(), alive
 
     # ---- whole-image detection (reference model.py:149-179)
-    def detect(self, image, iou_threshold=None, score_threshold=None) -> Boxes:
+    def detect(self, image, iou_threshold=None, score_threshold=None, vote_iou=None, vote_weights="uniform", min_votes=1) -> Boxes:
         """Detect objects in a 2-D image; returns Boxes with a 'scores' field, levels in pyramid
         order and windows in row-major order within a level, like the reference.
         iou_threshold: greedy non-maximum suppression of the result (boxes.non_max_suppression has the semantics;
         score_threshold drops boxes below it first): the kept detections, still in that order.  It runs on the device
         on the finished detections, enqueued behind the step's graph replay and in front of the call's one wait (the
         plain step's graph is shared: a new threshold captures nothing); n_loc / n_weak are those of the scan.  None: the
-        plain call.  Scores are never NaN for a model the loader accepts."""
-        res, _, _ = self._detect_one(image, _nms_args(iou_threshold, score_threshold), windows=False)
-        return _as_boxes(res)
+        plain call.  Scores are never NaN for a model the loader accepts.
+        vote_iou (needs an iou_threshold), vote_weights, min_votes: box voting -- boxes.merge_detections of the call's
+        complete, unsuppressed result with these thresholds: every kept box becomes the mean of its cluster and gets a 'votes'
+        field; kept boxes with fewer than min_votes voters are left out.  That is a second device round trip (an upload, NMS
+        and the vote kernel, a read-back) after the scan's read-back.  None: exactly the call without it."""
+        nms = _nms_args(iou_threshold, score_threshold)
+        vote = _vote_args(nms, vote_iou, vote_weights, min_votes)
+        res, _, _ = self._detect_one(image, None if vote else nms, windows=False)
+        return merge_detections(_as_boxes(res), **vote) if vote else _as_boxes(res)
 
     def detect_raw(self, image, _nms=None):
         """detect() with everything the parity tests compare: boxes, scores, (level, r, c),

@@ -260,20 +260,25 @@ def fit(model, images, min_iou=0.5, max_candidates=100, l2=1e-2, batch=8, seed=0
     return acc.solve(l2)
 
 
-def detect_and_refine(image, model, regressor, iou_threshold=None, score_threshold=None):
+def detect_and_refine(image, model, regressor, iou_threshold=None, score_threshold=None, vote_iou=None, vote_weights="uniform", min_votes=1):
     """Detections of `model` on `image` with their boxes refined by `regressor`: Boxes with 'scores', in Model.detect's
     order (levels in pyramid order, row-major inside a level).  The scan is verification.detect_and_verify's route (float or
     uint8 channels, not rank bytes); the scan's records go up in one upload and wb_regress_apply_launch reads every window
     where it lies in the resident pyramid.  Scores are untouched.  iou_threshold / score_threshold: non-maximum suppression
     (non_max_suppression's semantics) AFTER refinement, on the refined boxes.  Two host waits: the scan's read-back and the
-    refined boxes.  n_loc / n_weak advance as in a scan."""
+    refined boxes.  n_loc / n_weak advance as in a scan.
+    vote_iou (needs an iou_threshold), vote_weights, min_votes: box voting on the REFINED boxes -- boxes.merge_detections of
+    the complete refined result with these thresholds: every kept box becomes the mean of its cluster and gets a 'votes'
+    field, kept boxes with fewer than min_votes voters are left out.  That is one more device round trip after the refined
+    boxes' read-back.  None: exactly the call without it."""
     import torch
     from . import channels as _channels
     from . import engine as _engine
-    from .boxes import Boxes, non_max_suppression
-    from .model import _nms_args
+    from .boxes import Boxes, merge_detections, non_max_suppression
+    from .model import _nms_args, _vote_args
     from .samples import level_table
     nms = _nms_args(iou_threshold, score_threshold)
+    vote = _vote_args(nms, vote_iou, vote_weights, min_votes)
     if not isinstance(regressor, BoxRegressor):
         raise TypeError(f"detect_and_refine takes a BoxRegressor, got {type(regressor).__name__}")
     if tuple(int(x) for x in model.shape) != regressor.input_shape:
@@ -285,6 +290,8 @@ def detect_and_refine(image, model, regressor, iou_threshold=None, score_thresho
     if spec.dtype == np.uint8:
         _channels._require_u8(image, spec.key)
     empty = Boxes(np.zeros((0, 4), np.float32), scores=np.zeros(0, np.float32))
+    if vote is not None:
+        empty.set_field("votes", np.zeros(0, np.int32))
     eng = _engine.get_engine(image.shape[0], image.shape[1], image.dtype, shrink, n_per_oct, smooth, 1, channels=spec)
     if eng.plan.n_levels == 0:
         return empty
@@ -315,6 +322,8 @@ def detect_and_refine(image, model, regressor, iou_threshold=None, score_thresho
     if int(host[-1]):
         raise RuntimeError("detect_and_refine: a detection's window lies outside its pyramid level")
     out = Boxes(host[:-1].view(np.float32).reshape(N, 4).copy(), scores=np.ascontiguousarray(found["scores"], np.float32))
-    if nms is not None:
+    if vote is not None:
+        out = merge_detections(out, **vote)
+    elif nms is not None:
         out = non_max_suppression(out, nms[0], nms[1])
     return out
