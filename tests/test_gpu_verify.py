@@ -96,6 +96,39 @@ def test_detect_and_verify_on_uint8_channels():
     assert _check_detect_and_verify(M, img) == np.uint8
 
 
+@pytest.mark.parametrize("name", ["mixed", "grad_hist_4_u1"])
+def test_the_three_calls_behind_one_scan_front_report_the_same_detections(name):
+    """detect_and_verify, detect_and_refine (a regressor of zero weights moves no box; no NMS) and get_samples_from_image
+    (no ground truth, uncapped: every window is yielded) scan through Model.scan_resident: the same boxes and scores, bit
+    for bit and in one order, the same n_loc / n_weak; an image too small for any level is each call's empty value."""
+    from waldboost_amd import regression
+    from waldboost_amd.samples import get_samples_from_image
+    M = wb.load(os.path.join(GOLDEN, name + "_d2_T24.pb"))
+    img = np.load(os.path.join(GOLDEN, name + "_200x264.npz"))["image"]
+    reg = regression.BoxRegressor(M.shape, np.zeros((int(np.prod(M.shape)), 4)), np.zeros(4))
+    calls = {"verify": lambda im: ver.detect_and_verify(im, M, random_verifier(tuple(M.shape), seed=11))[0],
+             "refine": lambda im: regression.detect_and_refine(im, M, reg),
+             "samples": lambda im: wb.concatenate(list(get_samples_from_image(M, im, None, max_fp_candidates=10 ** 9)), ["scores"])}
+    M.reset()
+    want = M.detect_raw(img)
+    counts = (M.n_loc, M.n_weak)
+    assert want["scores"].size >= 3 and counts[0] > 0
+    u32 = lambda a: np.ascontiguousarray(a, np.float32).view(np.uint32)
+    for what, call in calls.items():
+        M.reset()
+        got = call(img)
+        assert (M.n_loc, M.n_weak) == counts, what
+        boxes = got if what == "verify" else got.get()
+        assert boxes.dtype == np.float32 and np.array_equal(u32(boxes), u32(want["boxes"])), what
+        if what != "verify":                                                    # (the verifier's scores are its own)
+            assert np.array_equal(u32(got.get_field("scores")), u32(want["scores"])), what
+        M.reset()
+        tiny = call(np.zeros((8, 8), np.uint8))
+        assert len(tiny) == 0 and (M.n_loc, M.n_weak) == (0, 0), what
+    assert calls["refine"](np.zeros((8, 8), np.uint8)).fields() == ["scores"]
+    assert list(get_samples_from_image(M, np.zeros((8, 8), np.uint8), None)) == []
+
+
 def test_detect_and_verify_without_detections_and_with_the_wrong_shape():
     M = wb.load(os.path.join(GOLDEN, "mixed_d2_T24.pb"))
     img = np.load(os.path.join(GOLDEN, "mixed_200x264.npz"))["image"]

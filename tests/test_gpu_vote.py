@@ -61,6 +61,27 @@ def test_model_detect_with_vote_iou_is_the_statement_on_its_plain_result():
     assert seen >= 200 and clusters >= 1
 
 
+@pytest.mark.parametrize("rank_max", [None, 0], ids=["ranked", "ordered"])
+def test_merge_detections_is_nms_keep_mask_then_vote_boxes_then_min_votes(rank_max, monkeypatch):
+    """The three public functions share one device body: merging is the two steps and the filter, bit for bit and field for
+    field -- also when the boxes go through torch.sort + wb_nms_ordered_launch (_NMS_RANK_MAX 0)."""
+    import vote_designs as vd
+    from waldboost_amd import boxes as B
+    if rank_max is not None:
+        monkeypatch.setattr(B, "_NMS_RANK_MAX", rank_max)
+    d = next(x for x in vd.all_designs() if x.name == "sprinkle-n129-score-thr-groups")   # 44 kept, 30 with a second vote
+    bx = wb.Boxes(d.boxes, scores=d.scores, label=d.group.astype(np.int64), index=np.arange(d.n))
+    for min_votes in (1, 2):
+        got = B.merge_detections(bx, d.nms_t, d.score_t, d.group, d.vote_iou, d.weights, min_votes)
+        keep = B.nms_keep_mask(d.boxes, d.scores, d.nms_t, d.score_t, d.group)
+        assert keep.dtype == bool and np.array_equal(keep, d.keep != 0)
+        merged, votes = B.vote_boxes(d.boxes, d.scores, keep, d.vote_iou, d.weights, d.score_t, d.group)
+        idx = np.flatnonzero(keep & (votes >= min_votes))
+        assert 0 < idx.size and (min_votes == 1 or idx.size < keep.sum())
+        assert got.fields() == ["scores", "label", "index", "votes"] and np.array_equal(got.get_field("index"), idx)
+        assert same(got, wb.Boxes(merged[idx], scores=d.scores[idx], label=bx.get_field("label")[idx], votes=votes[idx]), ("scores", "label", "votes"))
+
+
 def test_multi_model_detect_votes_inside_the_label_when_separate():
     A = wb.load(os.path.join(GOLDEN, "mixed_d2_T24.pb"))
     B = wb.load(os.path.join(GOLDEN, "models", "cfg2_d2_T128.pb"))

@@ -64,6 +64,47 @@ def test_vote_boxes_and_merge_detections_check_their_arguments_before_the_device
         wbb.merge_detections(wb.Boxes(f([0, 0, np.inf, 1], A), scores=s))
 
 
+def _suppression_entry_points():
+    """name -> (the call, taking boxes.suppression's keyword names, and which of them it takes)."""
+    image = np.zeros((64, 64), np.uint8)
+    M = wb.Model((8, 8, 4), wb.default_channel_opts)
+    reg = regression.BoxRegressor((8, 8, 4), np.zeros((256, 4)), np.zeros(4))
+    b, s, k = f(A, A), np.array([1, 2], "f"), [0, 1]
+    bx = wb.Boxes(b, scores=s)
+    nms = {"iou_threshold", "score_threshold"}
+    voting = nms | {"vote_iou", "weights", "min_votes"}
+    detect_kw = lambda kw: {"vote_weights" if key == "weights" else key: v for key, v in kw.items()}
+    return {"non_max_suppression": (lambda **kw: wbb.non_max_suppression(bx, **kw), nms),
+            "nms_keep_mask": (lambda **kw: wbb.nms_keep_mask(b, s, **kw), nms),
+            "vote_boxes": (lambda **kw: wbb.vote_boxes(b, s, k, **kw), {"score_threshold", "vote_iou", "weights"}),
+            "merge_detections": (lambda **kw: wbb.merge_detections(bx, **kw), voting),
+            "Model.detect": (lambda **kw: M.detect(image, **detect_kw(kw)), voting),
+            "Model.detect_batch": (lambda **kw: M.detect_batch(image[None], **kw), nms),
+            "Model.detect_stream": (lambda **kw: next(M.detect_stream([image], **kw)), nms),
+            "waldboost_amd.detect": (lambda **kw: wb.detect(image, M, **detect_kw(kw)), voting),
+            "detect_and_refine": (lambda **kw: regression.detect_and_refine(image, M, reg, **detect_kw(kw)), voting)}
+
+
+@pytest.mark.parametrize("key,value,takers", [("iou_threshold", -1.0, 8), ("iou_threshold", float("nan"), 8), ("score_threshold", float("nan"), 9),
+                                              ("vote_iou", -0.5, 5), ("weights", "best", 5), ("min_votes", 1.5, 4)])
+def test_every_entry_point_refuses_a_bad_scalar_in_the_same_words(key, value, takers):
+    """One statement of the suppression arguments (boxes.suppression): whichever call is given the bad value says the same,
+    and says it before the device is touched (this test needs no GPU)."""
+    said = {}
+    for name, (call, takes) in _suppression_entry_points().items():
+        if key not in takes:
+            continue
+        kw = dict(iou_threshold=0.3, vote_iou=0.5) if key in ("weights", "min_votes") else dict(iou_threshold=0.3)
+        kw[key] = value
+        with pytest.raises(ValueError) as e:
+            call(**{k: v for k, v in kw.items() if k in takes})
+        said[name] = str(e.value)
+    assert len(said) == takers and len(set(said.values())) == 1, said
+    with pytest.raises(ValueError) as e:
+        wbb.suppression(**dict(dict(iou_threshold=0.3, vote_iou=0.5), **{key: value}))
+    assert str(e.value) in said.values()
+
+
 def test_an_empty_input_never_touches_the_device():
     m, v = wbb.vote_boxes(np.zeros((0, 4), "f"), np.zeros(0, "f"), np.zeros(0, np.uint8), weights="score", score_threshold=0.0)
     assert m.shape == (0, 4) and m.dtype == np.float32 and v.shape == (0,) and v.dtype == np.int32

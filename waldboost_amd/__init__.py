@@ -42,11 +42,10 @@ def detect(image, *models, channel_opts=None, response_scale=None, iou_threshold
     left out.  That is a second device round trip after the read-back.  None: exactly the call without it."""
     import numpy as np
     from . import engine as _engine
-    from .model import _nms_args, _vote_args
+    from .boxes import finish, suppression
     if not models:
         raise ValueError("detect needs at least one model")
-    nms = _nms_args(iou_threshold, score_threshold)
-    vote = _vote_args(nms, vote_iou, vote_weights, min_votes)
+    how = suppression(iou_threshold, score_threshold, vote_iou, vote_weights, min_votes)
     channel_opts = channel_opts or models[0].channel_opts
     if response_scale is None:
         response_scale = [1] * len(models)
@@ -95,11 +94,7 @@ def detect(image, *models, channel_opts=None, response_scale=None, iou_threshold
     out = Boxes(boxes.reshape(-1, 4).astype(np.float32, copy=False))
     out.set_field("scores", scores.astype(np.float32, copy=False))
     out.set_field("label", label[order])
-    if vote is not None:
-        out = merge_detections(out, group=out.get_field("label") if separate else None, **vote)
-    elif nms is not None:
-        out = non_max_suppression(out, nms[0], nms[1], group=out.get_field("label") if separate else None)
-    return out
+    return finish(out, how, group=out.get_field("label") if separate else None)
 
 
 def train(model, training_images, learner=None, pool=None, length=64, theta_schedule=BasicRejectionSchedule(), callbacks=[],

@@ -5,6 +5,7 @@ built (``python -c 'import __graft_entry__ as g; g.build()'`` or ``make -C
 waldboost_amd/csrc``) every compute entry point raises ``RuntimeError``.
 """
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -217,3 +218,71 @@ def stream_ptr():
 def ptr(t):
     """Device pointer of a torch tensor (or None)."""
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+
+
+def _spec(part):
+    """(shape, dtype) of a Block part: a NumPy array, or the (shape, dtype) of an output."""
+    if isinstance(part, np.ndarray):
+        return part.shape, part.dtype
+    shape, dtype = part
+    return shape if isinstance(shape, tuple) else (int(shape),), np.dtype(dtype)
+
+
+def block_layout(**parts):
+    """({name: byte offset}, total bytes) of arrays packed back to back in the order given -- a Block's layout.  A part is
+    a NumPy array (an upload) or a (shape, dtype) spec (an output).  Part `name` must land on a multiple of min(16, the bytes
+    of one of its rows), a row being everything behind the first axis: what the kernels' float4 / double / int loads need
+    and the launch functions refuse to go without.  Nothing is padded: an order that breaks the rule is an AssertionError
+    that names the part.  A part without bytes lies anywhere and moves nothing."""
+    offsets, at = {}, 0
+    for name, part in parts.items():
+        shape, dtype = _spec(part)
+        row = math.prod(shape[1:]) * dtype.itemsize
+        assert shape[0] * row == 0 or at % min(16, row) == 0, \
+            f"block part {name!r} ({dtype} rows of {row} bytes) at byte {at} is not {min(16, row)}-byte aligned: order the parts by row size"
+        offsets[name] = at
+        at += shape[0] * row
+    return offsets, at
+
+
+class Block:
+    """Several typed arrays in ONE device allocation (block_layout), so that they travel in one copy: `upload` sends host
+    arrays up, `empty` reserves outputs that `host` brings down together.  ptr[name]: the part's device pointer, a
+    ctypes.c_void_p (ptr.get(name) of an absent optional part is None, the null pointer to ctypes); tensor(name): a typed
+    torch view into the block; host(): ONE .cpu() -> {name: typed, shaped NumPy view of the copy} (copy what outlives it)."""
+
+    def __init__(self, dev, parts, upload):
+        import torch
+        self.parts = parts
+        self.offsets, self.nbytes = block_layout(**parts)
+        if upload:
+            flat = [a.reshape(-1) for a in parts.values()]                                  # (a copy where `a` is not contiguous)
+            self.blob = torch.from_numpy(np.concatenate([p.view(np.uint8) for p in flat])).to(dev)
+        else:
+            self.blob = torch.empty(self.nbytes, dtype=torch.uint8, device=dev)
+        base = self.blob.data_ptr()
+        self.ptr = {k: C.c_void_p(base + o) for k, o in self.offsets.items()}
+
+    @classmethod
+    def upload(cls, dev, **arrays):
+        return cls(dev, arrays, True)
+
+    @classmethod
+    def empty(cls, dev, **specs):
+        return cls(dev, specs, False)
+
+    def _part(self, flat, name):
+        """(the bytes of part `name` in `flat`, the blob or a copy of it; its shape; its dtype)"""
+        shape, dtype = _spec(self.parts[name])
+        at = self.offsets[name]
+        return flat[at:at + math.prod(shape) * dtype.itemsize], shape, dtype
+
+    def tensor(self, name):
+        """Part `name` as a torch view (a structured dtype: its rows as bytes, uint8 [rows, itemsize])."""
+        import torch
+        b, shape, dtype = self._part(self.blob, name)
+        return b.view(-1, dtype.itemsize) if dtype.names else b.view(getattr(torch, dtype.name)).reshape(shape)
+
+    def host(self):
+        h = self.blob.cpu().numpy()
+        return {k: b.view(dtype).reshape(shape) for k, (b, shape, dtype) in ((k, self._part(h, k)) for k in self.parts)}

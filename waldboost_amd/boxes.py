@@ -5,6 +5,8 @@
 the docstring example at model.py:166-171) use are provided.  Parity at this boundary is
 unpinned upstream.
 """
+from typing import NamedTuple
+
 import numpy as np
 
 
@@ -157,89 +159,174 @@ def match_boxes(dt_boxes, gt_boxes_per_image, dt_image=None):
     n_gt = int(off[-1])
     if n_gt >= 1 << 31:
         raise ValueError("match_boxes: at most 2**31 - 1 ground-truth boxes")
-    import ctypes as C
-    import torch
     from . import _native as nat
     lib = nat.load()
     dev = nat.require_gpu()
-    # one upload: detections | ground truth | dt_image | gt_off (the doubles first: everything stays aligned)
-    parts = [dt.reshape(-1).view(np.uint8)] + [g.reshape(-1).view(np.uint8) for g in gt]
-    parts += [image.view(np.uint8), off.astype(np.int32).view(np.uint8)]
-    d_in = torch.from_numpy(np.concatenate(parts)).to(dev)
-    d_out = torch.empty(12 * n, dtype=torch.uint8, device=dev)         # best | owner: one read-back
-    at = lambda t, o: C.c_void_p(t.data_ptr() + o)
-    o_gt, o_img = 32 * n, 32 * (n + n_gt)
-    nat.check(lib.wb_match_launch(nat.stream_ptr(), at(d_in, 0), at(d_in, o_img), at(d_in, o_gt), at(d_in, o_img + 4 * n), n, n_gt,
-                                  len(gt), at(d_out, 0), at(d_out, 8 * n)), "wb_match_launch")
-    h = d_out.cpu().numpy()
-    return h[:8 * n].view(np.float64).copy(), h[8 * n:].view(np.int32).copy()
+    inp = nat.Block.upload(dev, dt=dt, gt=np.concatenate(gt), image=image, gt_off=off.astype(np.int32))
+    out = nat.Block.empty(dev, best=(n, np.float64), owner=(n, np.int32))
+    nat.check(lib.wb_match_launch(nat.stream_ptr(), inp.ptr["dt"], inp.ptr["image"], inp.ptr["gt"], inp.ptr["gt_off"], n, n_gt, len(gt),
+                                  out.ptr["best"], out.ptr["owner"]), "wb_match_launch")
+    h = out.host()
+    return h["best"].copy(), h["owner"].copy()
 
 
 _NMS_RANK_MAX = 1 << 16      # most boxes wb_nms_launch orders itself (a quadratic pass); above: torch.sort + wb_nms_ordered_launch
+VOTE_WEIGHTS = ("uniform", "score")      # WB_VOTE_UNIFORM, WB_VOTE_SCORE
 
 
-def _nms_inputs(boxes, scores, iou_threshold, score_threshold, group):
-    """The checked arguments of an NMS call: (boxes float32 [n][4], scores float32 [n], iou_threshold, group int32 [n] or None)."""
+class Suppression(NamedTuple):
+    """The checked scalar arguments of non-maximum suppression and box voting; `suppression` makes it."""
+    iou_threshold: float
+    score_threshold: float = None        # a float32 value as a Python float; None: no box is dropped by its score
+    vote: tuple = None                   # (vote_iou, index into VOTE_WEIGHTS, min_votes); None: no box voting
+
+    @property
+    def threshold_args(self):
+        """(use_score_threshold, score_threshold) as the launch functions take them."""
+        return (0, 0.0) if self.score_threshold is None else (1, self.score_threshold)
+
+
+def suppression(iou_threshold, score_threshold=None, vote_iou=None, weights="uniform", min_votes=1):
+    """The Suppression of these arguments -- every rule about them is here and nowhere else -- or None for iou_threshold
+    None: the plain detect call, which takes neither of the other thresholds.  vote_iou None: no voting (`weights` and
+    `min_votes` are not looked at then).  ValueError for anything else that is not a suppression."""
+    if iou_threshold is None:
+        if score_threshold is not None:
+            raise ValueError("score_threshold is part of non-maximum suppression: give an iou_threshold too (1.0 suppresses nothing)")
+        if vote_iou is not None:
+            raise ValueError("vote_iou merges what non-maximum suppression keeps: give an iou_threshold too")
+        return None
+    iou_threshold = float(iou_threshold)
+    if not iou_threshold >= 0.0:
+        raise ValueError("iou_threshold must be a number >= 0")
+    if score_threshold is not None:
+        score_threshold = float(np.float32(score_threshold))
+        if score_threshold != score_threshold:
+            raise ValueError("score_threshold is NaN")
+    if vote_iou is None:
+        return Suppression(iou_threshold, score_threshold)
+    vote_iou = float(vote_iou)
+    if not vote_iou >= 0.0:
+        raise ValueError("vote_iou must be a number >= 0")
+    if weights not in VOTE_WEIGHTS:
+        raise ValueError(f"vote weights must be one of {VOTE_WEIGHTS}, not {weights!r}")
+    if weights == "score" and score_threshold is None:
+        raise ValueError('"score" vote weights are measured from the score threshold: give a score_threshold')
+    if int(min_votes) != min_votes or min_votes < 0:
+        raise ValueError("min_votes must be an integer >= 0")
+    return Suppression(iou_threshold, score_threshold, (vote_iou, VOTE_WEIGHTS.index(weights), int(min_votes)))
+
+
+def _checked_arrays(boxes, scores, group, voting=False):
+    """The checked arrays of a suppression: (boxes float32 [n][4], scores float32 [n], group int32 [n] or None)."""
     boxes = np.ascontiguousarray(boxes, np.float32).reshape(-1, 4)
     scores = np.ascontiguousarray(scores, np.float32).reshape(-1)
     n = scores.size
     if boxes.shape[0] != n:
         raise ValueError(f"{boxes.shape[0]} boxes, {n} scores")
-    iou_threshold = float(iou_threshold)
-    if not iou_threshold >= 0.0:
-        raise ValueError("iou_threshold must be a number >= 0")
-    if score_threshold is not None and np.isnan(np.float32(score_threshold)):
-        raise ValueError("score_threshold is NaN")
     if group is not None:
         group = np.asarray(group).reshape(-1)
         if group.size != n:
             raise ValueError(f"{group.size} group entries, {n} boxes")
         group = np.unique(group, return_inverse=True)[1].astype(np.int32).reshape(-1)     # (any dtype: equality is all that counts)
-    return boxes, scores, iou_threshold, group
+    if voting and not np.isfinite(boxes).all():
+        raise ValueError("box voting: coordinates must be finite")
+    if voting and np.isnan(scores).any():
+        raise ValueError("box voting: scores must not be NaN")
+    return boxes, scores, group
 
 
-def _nms_enqueue(lib, dev, p_boxes, d_scores, p_group, n, iou_threshold, score_threshold):
-    """Greedy NMS of n > 0 boxes that lie on the device already (p_boxes, p_group: device pointers, the group's may be
-    null; d_scores: a float32 tensor), enqueued on the current stream: the device bytes n_keep (uint32) | keep flags [n]."""
-    import ctypes as C
-    import torch
-    from . import _native as nat
-    need = C.c_size_t()
-    nat.check(lib.wb_nms_scratch_bytes(n, C.byref(need)), "wb_nms_scratch_bytes")
-    scratch = torch.empty(need.value, dtype=torch.uint8, device=dev)
-    out = torch.empty(4 + n, dtype=torch.uint8, device=dev)           # n_keep | keep flags: one read-back
-    tail = (n, iou_threshold, 0 if score_threshold is None else 1, 0.0 if score_threshold is None else float(np.float32(score_threshold)),
-            nat.ptr(scratch), scratch.numel(), C.c_void_p(out.data_ptr() + 4), nat.ptr(out))
-    if n <= _NMS_RANK_MAX:
-        nat.check(lib.wb_nms_launch(nat.stream_ptr(), p_boxes, nat.ptr(d_scores), p_group, *tail), "wb_nms_launch")
-    else:
-        # descending, the two zeros one value (-(s + 0) is -0.0 for both), equal scores in input order
-        order = torch.sort(-(d_scores + 0.0), stable=True).indices.to(torch.int32)
-        nat.check(lib.wb_nms_ordered_launch(nat.stream_ptr(), p_boxes, nat.ptr(d_scores), p_group, nat.ptr(order), *tail),
-                  "wb_nms_ordered_launch")
-    return out
+class _DeviceBoxes:
+    """n > 0 checked boxes on the device -- ONE upload of boxes | scores | group | keep, the absent ones left out -- with the
+    launches that work on them and the ONE block their results come back in: merged | votes with `vote`, then n_keep | keep
+    unless the keep flags were given."""
+
+    def __init__(self, boxes, scores, group, keep=None, vote=False):
+        from . import _native as nat
+        self.lib, self.dev, self.n, n = nat.load(), nat.require_gpu(), scores.size, scores.size
+        given = dict(boxes=boxes, scores=scores, group=group, keep=keep)
+        self.inp = nat.Block.upload(self.dev, **{k: v for k, v in given.items() if v is not None})
+        specs = dict(merged=((n, 4), np.float32), votes=(n, np.int32)) if vote else {}
+        if keep is None:
+            specs.update(n_keep=(1, np.uint32), keep=(n, np.uint8))
+        self.out = nat.Block.empty(self.dev, **specs)
+
+    def nms(self, how):
+        """Greedy NMS into out's n_keep and keep, enqueued on the current stream."""
+        import ctypes as C
+        import torch
+        from . import _native as nat
+        at, n = self.inp.ptr, self.n
+        need = C.c_size_t()
+        nat.check(self.lib.wb_nms_scratch_bytes(n, C.byref(need)), "wb_nms_scratch_bytes")
+        scratch = torch.empty(need.value, dtype=torch.uint8, device=self.dev)
+        tail = (n, how.iou_threshold, *how.threshold_args, nat.ptr(scratch), scratch.numel(), self.out.ptr["keep"], self.out.ptr["n_keep"])
+        if n <= _NMS_RANK_MAX:
+            nat.check(self.lib.wb_nms_launch(nat.stream_ptr(), at["boxes"], at["scores"], at.get("group"), *tail), "wb_nms_launch")
+        else:
+            # descending, the two zeros one value (-(s + 0) is -0.0 for both), equal scores in input order
+            order = torch.sort(-(self.inp.tensor("scores") + 0.0), stable=True).indices.to(torch.int32)
+            nat.check(self.lib.wb_nms_ordered_launch(nat.stream_ptr(), at["boxes"], at["scores"], at.get("group"), nat.ptr(order), *tail),
+                      "wb_nms_ordered_launch")
+
+    def vote(self, how):
+        """wb_vote_launch into out's merged and votes, on the keep flags that were given or that nms left, on the current stream."""
+        from . import _native as nat
+        at, out, (vote_iou, code, _) = self.inp.ptr, self.out.ptr, how.vote
+        nat.check(self.lib.wb_vote_launch(nat.stream_ptr(), at["boxes"], at["scores"], at.get("group"), at.get("keep", out.get("keep")), self.n,
+                                          vote_iou, code, *how.threshold_args, out["merged"], out["votes"]), "wb_vote_launch")
+
+    def flags(self, h):
+        """The keep flags (bool [n]) of the read-back `h` of out."""
+        keep = h["keep"].astype(bool)
+        assert int(h["n_keep"][0]) == int(keep.sum())
+        return keep
+
+
+def _keep_mask(boxes, scores, how, group=None):
+    """nms_keep_mask of a Suppression."""
+    boxes, scores, group = _checked_arrays(boxes, scores, group)
+    if scores.size == 0:
+        return np.zeros(0, bool)
+    d = _DeviceBoxes(boxes, scores, group)
+    d.nms(how)
+    return d.flags(d.out.host())
 
 
 def nms_keep_mask(boxes, scores, iou_threshold=0.5, score_threshold=None, group=None):
     """Keep flags (bool [N], input order) of greedy non-maximum suppression, computed on the GPU (wb_nms_launch): the
-    arrays are uploaded, the flags read back.  See non_max_suppression for the semantics.  More than 2**16 boxes are put
-    in visiting order by a stable torch.sort on the device and go through wb_nms_ordered_launch: every N a detect call
-    can return (2**26) is accepted; the cost grows with N * N (include/waldboost_hip.h has the figures)."""
-    from . import _native as nat
-    boxes, scores, iou_threshold, group = _nms_inputs(boxes, scores, iou_threshold, score_threshold, group)
-    n = scores.size
-    if n == 0:
-        return np.zeros(0, bool)
-    import torch
-    lib = nat.load()
-    dev = nat.require_gpu()
-    d_boxes = torch.from_numpy(boxes).to(dev)
-    d_scores = torch.from_numpy(scores).to(dev)
-    d_group = torch.from_numpy(group).to(dev) if group is not None else None
-    h = _nms_enqueue(lib, dev, nat.ptr(d_boxes), d_scores, nat.ptr(d_group), n, iou_threshold, score_threshold).cpu().numpy()
-    keep = h[4:].astype(bool)
-    assert int(h[:4].view(np.uint32)[0]) == int(keep.sum())
-    return keep
+    arrays go up in one upload, the flags come back in one read-back.  See non_max_suppression for the semantics.  More than
+    2**16 boxes are put in visiting order by a stable torch.sort on the device and go through wb_nms_ordered_launch: every N
+    a detect call can return (2**26) is accepted; the cost grows with N * N (include/waldboost_hip.h has the figures)."""
+    return _keep_mask(boxes, scores, suppression(float(iou_threshold), score_threshold), group)
+
+
+def finish(boxes, how, group=None):
+    """The tail of every detect call and the body of non_max_suppression and merge_detections: the Boxes `boxes` (with
+    'scores') after the Suppression `how` -- None: `boxes` itself; without a vote: what non_max_suppression returns; with
+    one: what merge_detections returns.  One upload, the launches on the same device arrays, one read-back."""
+    if how is None:
+        return boxes
+    if not boxes.has_field("scores"):
+        raise ValueError("suppression needs a 'scores' field")
+    voting = how.vote is not None
+    b, s, g = _checked_arrays(boxes.get(), boxes.get_field("scores"), group, voting)
+    if s.size == 0:
+        out = boxes[np.zeros(0, np.intp)]
+        if voting:
+            out.set_field("votes", np.zeros(0, np.int32))
+        return out
+    d = _DeviceBoxes(b, s, g, vote=voting)
+    d.nms(how)
+    if not voting:
+        return boxes[np.flatnonzero(d.flags(d.out.host()))]
+    d.vote(how)
+    h = d.out.host()
+    idx = np.flatnonzero(d.flags(h) & (h["votes"] >= how.vote[-1]))             # (min_votes)
+    kept = boxes[idx]
+    out = Boxes(h["merged"][idx], **{k: kept.get_field(k) for k in kept.fields()})
+    out.set_field("votes", h["votes"][idx])
+    return out
 
 
 def non_max_suppression(boxes, iou_threshold=0.5, score_threshold=None, group=None):
@@ -254,60 +341,7 @@ def non_max_suppression(boxes, iou_threshold=0.5, score_threshold=None, group=No
 
     Runs on the GPU (wb_nms_launch; above 2**16 boxes torch.sort + wb_nms_ordered_launch); like everything in this package it has no CPU fallback and
     raises NativeError without a GPU.  An empty Boxes is returned as an empty Boxes without touching the device."""
-    if not boxes.has_field("scores"):
-        raise ValueError("non_max_suppression needs a 'scores' field")
-    if len(boxes) == 0:
-        return boxes[np.zeros(0, np.intp)]
-    keep = nms_keep_mask(boxes.get(), boxes.get_field("scores"), iou_threshold, score_threshold, group)
-    return boxes[np.flatnonzero(keep)]
-
-
-VOTE_WEIGHTS = ("uniform", "score")      # WB_VOTE_UNIFORM, WB_VOTE_SCORE
-
-
-def _vote_inputs(boxes, scores, vote_iou, weights, score_threshold, min_votes=1):
-    """The checked arguments of a voting call: (vote_iou, weights code, float32 score_threshold or None, min_votes)."""
-    vote_iou = float(vote_iou)
-    if not vote_iou >= 0.0:
-        raise ValueError("vote_iou must be a number >= 0")
-    if weights not in VOTE_WEIGHTS:
-        raise ValueError(f"weights must be one of {VOTE_WEIGHTS}, not {weights!r}")
-    if score_threshold is not None:
-        score_threshold = float(np.float32(score_threshold))
-        if score_threshold != score_threshold:
-            raise ValueError("score_threshold is NaN")
-    elif weights == "score":
-        raise ValueError('"score" weights are measured from the score threshold: give a score_threshold')
-    if not np.isfinite(boxes).all():
-        raise ValueError("box voting: coordinates must be finite")
-    if np.isnan(scores).any():
-        raise ValueError("box voting: scores must not be NaN")
-    if int(min_votes) != min_votes or min_votes < 0:
-        raise ValueError("min_votes must be an integer >= 0")
-    return vote_iou, VOTE_WEIGHTS.index(weights), score_threshold, int(min_votes)
-
-
-def _vote_enqueue(lib, d_boxes, d_scores, d_group, d_keep, n, vote_iou, code, score_threshold, d_merged, d_votes):
-    """wb_vote_launch on device pointers (ctypes), on the current stream."""
-    from . import _native as nat
-    nat.check(lib.wb_vote_launch(nat.stream_ptr(), d_boxes, d_scores, d_group, d_keep, n, vote_iou, code, 0 if score_threshold is None else 1,
-                                 0.0 if score_threshold is None else score_threshold, d_merged, d_votes), "wb_vote_launch")
-
-
-def _upload_boxes(dev, boxes, scores, group, keep=None):
-    """One upload of boxes | scores | group | keep (the absent ones left out): (the device bytes, ctypes pointers by name)."""
-    import ctypes as C
-    import torch
-    parts = dict(boxes=boxes.reshape(-1), scores=scores)
-    if group is not None:
-        parts["group"] = group
-    if keep is not None:
-        parts["keep"] = keep
-    blob = torch.from_numpy(np.concatenate([p.view(np.uint8) for p in parts.values()])).to(dev)
-    offs = np.cumsum([0] + [p.nbytes for p in parts.values()])
-    at = {k: C.c_void_p(blob.data_ptr() + int(o)) for k, o in zip(parts, offs)}
-    at.setdefault("group", C.c_void_p(0))
-    return blob, at, {k: int(o) for k, o in zip(parts, offs)}
+    return finish(boxes, suppression(float(iou_threshold), score_threshold), group)
 
 
 def vote_boxes(boxes, scores, keep, vote_iou=0.5, weights="uniform", score_threshold=None, group=None):
@@ -325,25 +359,17 @@ def vote_boxes(boxes, scores, keep, vote_iou=0.5, weights="uniform", score_thres
     Runs on the GPU (wb_vote_launch: K * N IoU tests for K kept boxes): one upload, one launch, one read-back; no CPU
     fallback.  Coordinates must be finite, scores not NaN (ValueError, like every bad argument, before the device is
     touched).  An empty input returns empty arrays without touching the device."""
-    from . import _native as nat
-    boxes, scores, _, group = _nms_inputs(boxes, scores, 0.0, score_threshold, group)
-    n = scores.size
+    how = suppression(0.0, score_threshold, vote_iou, weights)
+    boxes, scores, group = _checked_arrays(boxes, scores, group, voting=True)
     keep = np.ascontiguousarray(np.asarray(keep).reshape(-1) != 0, np.uint8)
-    if keep.size != n:
-        raise ValueError(f"{keep.size} keep flags, {n} boxes")
-    vote_iou, code, score_threshold, _ = _vote_inputs(boxes, scores, vote_iou, weights, score_threshold)
-    if n == 0:
+    if keep.size != scores.size:
+        raise ValueError(f"{keep.size} keep flags, {scores.size} boxes")
+    if scores.size == 0:
         return np.zeros((0, 4), np.float32), np.zeros(0, np.int32)
-    import ctypes as C
-    import torch
-    lib = nat.load()
-    dev = nat.require_gpu()
-    blob, at, _ = _upload_boxes(dev, boxes, scores, group, keep)
-    out = torch.empty(20 * n, dtype=torch.uint8, device=dev)          # merged | votes: one read-back
-    _vote_enqueue(lib, at["boxes"], at["scores"], at["group"], at["keep"], n, vote_iou, code, score_threshold, nat.ptr(out),
-                  C.c_void_p(out.data_ptr() + 16 * n))
-    h = out.cpu().numpy()
-    return h[:16 * n].view(np.float32).reshape(n, 4).copy(), h[16 * n:].view(np.int32).copy()
+    d = _DeviceBoxes(boxes, scores, group, keep, vote=True)
+    d.vote(how)
+    h = d.out.host()
+    return h["merged"].copy(), h["votes"].copy()
 
 
 def merge_detections(boxes, iou_threshold=0.5, score_threshold=None, group=None, vote_iou=0.5, weights="uniform", min_votes=1):
@@ -356,33 +382,7 @@ def merge_detections(boxes, iou_threshold=0.5, score_threshold=None, group=None,
     ``votes < min_votes`` are left out (an isolated firing is more often a false alarm than a cluster is); NMS is NOT run
     again after that, so a box such a kept box had suppressed does not come back.
 
-    Runs on the GPU: one upload, the NMS launches and wb_vote_launch on the same device arrays, one read-back; no CPU
-    fallback.  Bad arguments raise ValueError before the device is touched.  An empty Boxes is returned as an empty Boxes
-    (with a 'votes' field) without touching the device."""
-    from . import _native as nat
-    if not boxes.has_field("scores"):
-        raise ValueError("merge_detections needs a 'scores' field")
-    b, s, iou_threshold, g = _nms_inputs(boxes.get(), boxes.get_field("scores"), iou_threshold, score_threshold, group)
-    vote_iou, code, score_threshold, min_votes = _vote_inputs(b, s, vote_iou, weights, score_threshold, min_votes)
-    n = s.size
-    if n == 0:
-        out = boxes[np.zeros(0, np.intp)]
-        out.set_field("votes", np.zeros(0, np.int32))
-        return out
-    import ctypes as C
-    import torch
-    lib = nat.load()
-    dev = nat.require_gpu()
-    blob, at, offs = _upload_boxes(dev, b, s, g)
-    d_scores = blob[offs["scores"]:offs["scores"] + 4 * n].view(torch.float32)            # (what the sort of the long path reads)
-    flags = _nms_enqueue(lib, dev, at["boxes"], d_scores, at["group"], n, iou_threshold, score_threshold)
-    out = torch.empty(20 * n, dtype=torch.uint8, device=dev)
-    _vote_enqueue(lib, at["boxes"], at["scores"], at["group"], C.c_void_p(flags.data_ptr() + 4), n, vote_iou, code, score_threshold,
-                  nat.ptr(out), C.c_void_p(out.data_ptr() + 16 * n))
-    h = torch.cat([out, flags[4:]]).cpu().numpy()                     # merged | votes | keep flags: one read-back
-    merged, votes, keep = h[:16 * n].view(np.float32).reshape(n, 4), h[16 * n:20 * n].view(np.int32), h[20 * n:].astype(bool)
-    idx = np.flatnonzero(keep & (votes >= min_votes))
-    res = boxes[idx]
-    res = Boxes(merged[idx].copy(), **{k: res.get_field(k) for k in res.fields()})
-    res.set_field("votes", votes[idx].copy())
-    return res
+    Runs on the GPU: one upload, the NMS launches and wb_vote_launch on the same device arrays, one read-back of flags, boxes
+    and votes out of one block; no CPU fallback.  Bad arguments raise ValueError before the device is touched.  An empty Boxes
+    is returned as an empty Boxes (with a 'votes' field) without touching the device."""
+    return finish(boxes, suppression(float(iou_threshold), score_threshold, vote_iou, weights, min_votes), group)

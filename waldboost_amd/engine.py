@@ -1011,7 +1011,7 @@ class PyramidEngine:
         into page-locked memory, in the current stream, behind the launch that wrote the blocks (no synchronisation).
         Its result block, that block's page-locked copy and its scratch are kept in `holder` (a scan state, the batch's
         order buffers).  Nothing when the rows do not fit the launch: the caller then suppresses the complete result with
-        boxes.nms_keep_mask.  nms: (iou_threshold, score_threshold or None)."""
+        boxes.nms_keep_mask.  nms: a boxes.Suppression."""
         import torch
         if rows < 4 or rows % 4:
             return
@@ -1023,11 +1023,8 @@ class PyramidEngine:
             nb = holder.nms = NmsBuffers(rows, n_images, torch.empty(need.value, dtype=torch.uint8, device=self.dev),
                                          torch.empty(n_images * (16 + rows), dtype=torch.uint8, device=self.dev),
                                          h_res, h_res.numpy().reshape(n_images, 16 + rows))
-        iou_t, score_t = nms
-        nat.check(self.lib.wb_nms_finish_launch(nat.stream_ptr(), C.c_void_p(fin_ptr), rows, n_images, float(iou_t),
-                                                0 if score_t is None else 1, 0.0 if score_t is None else float(score_t),
-                                                nat.ptr(nb.scratch), nb.scratch.numel(), nat.ptr(nb.res)),
-                  "wb_nms_finish_launch")
+        nat.check(self.lib.wb_nms_finish_launch(nat.stream_ptr(), C.c_void_p(fin_ptr), rows, n_images, nms.iou_threshold, *nms.threshold_args,
+                                                nat.ptr(nb.scratch), nb.scratch.numel(), nat.ptr(nb.res)), "wb_nms_finish_launch")
         nb.h_res.copy_(nb.res, non_blocking=True)
 
     @staticmethod
@@ -1052,7 +1049,7 @@ class PyramidEngine:
         enqueued: the launch and the copies are already in the stream (detect_run's graph replay).
         stream: that stream, when it is not the current one -- then only the wait happens here, and False is returned
         if more than a wait is needed (the caller comes back on that stream).
-        nms: (iou_threshold, score_threshold or None) -- non-maximum suppression ran (enqueued) or runs (not enqueued)
+        nms: a boxes.Suppression -- non-maximum suppression ran (enqueued) or runs (not enqueued)
         on the finish buffer behind the launch that wrote it, a scan repeated after an overflow included; the result's
         `keep` then holds its flags."""
         if not self._final_ready():
@@ -1184,7 +1181,7 @@ class PyramidEngine:
         wb_det_finish_sorted_launch (which also carries alive[] behind the scores), the ONE read-back copy -- and its one synchronisation; from the second call with the
         same cascade on it is replayed as ONE hipGraph (one enqueue instead of seven, no gaps between the kernels).
         Returns what fetch_final returns: a readback.Finished, or None (then: use fetch()).
-        nms: (iou_threshold, score_threshold or None) -- the same step, eager or replayed, then wb_nms_finish_launch and the
+        nms: a boxes.Suppression -- the same step, eager or replayed, then wb_nms_finish_launch and the
         copy of its keep flags enqueued behind it, in front of the one wait: the plain step's graph is shared, a new
         threshold captures nothing."""
         return self.detect_collect(dm, self.detect_enqueue(dm, nms), nms=nms)

@@ -14,7 +14,7 @@ from . import _native as nat
 from . import channels as _channels
 from . import engine as _engine
 from . import model_pb2
-from .boxes import VOTE_WEIGHTS, Boxes, merge_detections, nms_keep_mask
+from .boxes import Boxes, _keep_mask, finish, suppression
 from .channels import channel_pyramid
 from .compare import channel_tensor
 from .readback import Detections, from_finished, from_image_result, from_ordered, from_packed
@@ -48,48 +48,12 @@ def symbol_from_name(name: str):
                          f"(known: {sorted(_channels.CHANNEL_FUNCS)})") from None
 
 
-def _nms_args(iou_threshold, score_threshold):
-    """(iou_threshold, score_threshold or None) of a detect call, or None for the plain call."""
-    if iou_threshold is None:
-        if score_threshold is not None:
-            raise ValueError("score_threshold is part of non-maximum suppression: give an iou_threshold too "
-                             "(1.0 suppresses nothing)")
-        return None
-    iou_threshold = float(iou_threshold)
-    if not iou_threshold >= 0.0:
-        raise ValueError("iou_threshold must be a number >= 0")
-    if score_threshold is not None:
-        score_threshold = float(np.float32(score_threshold))
-        if score_threshold != score_threshold:
-            raise ValueError("score_threshold is NaN")
-    return iou_threshold, score_threshold
-
-
-def _vote_args(nms, vote_iou, vote_weights, min_votes):
-    """The keywords of merge_detections for a detect call with vote_iou=, or None for a call without (the other two are
-    not looked at then).  Voting merges the clusters NMS reduces to one box each: it needs an iou_threshold."""
-    if vote_iou is None:
-        return None
-    if nms is None:
-        raise ValueError("vote_iou merges what non-maximum suppression keeps: give an iou_threshold too")
-    vote_iou = float(vote_iou)
-    if not vote_iou >= 0.0:
-        raise ValueError("vote_iou must be a number >= 0")
-    if vote_weights not in VOTE_WEIGHTS:
-        raise ValueError(f"vote_weights must be one of {VOTE_WEIGHTS}, not {vote_weights!r}")
-    if vote_weights == "score" and nms[1] is None:
-        raise ValueError('"score" vote weights are measured from the score threshold: give a score_threshold')
-    if int(min_votes) != min_votes or min_votes < 0:
-        raise ValueError("min_votes must be an integer >= 0")
-    return dict(iou_threshold=nms[0], score_threshold=nms[1], vote_iou=vote_iou, weights=vote_weights, min_votes=int(min_votes))
-
-
 def _suppress(res, nms):
     """The detections of one image's complete result that non-maximum suppression keeps: by the flags the device left
     behind the scan; without them the result goes through boxes.nms_keep_mask, on the GPU as well."""
     if nms is None:
         return res
-    keep = res.keep if res.keep is not None else nms_keep_mask(res.boxes, res.scores, nms[0], nms[1])
+    keep = res.keep if res.keep is not None else _keep_mask(res.boxes, res.scores, nms)
     return res.take(np.flatnonzero(keep))
 
 
@@ -287,15 +251,15 @@ class Model:
         complete, unsuppressed result with these thresholds: every kept box becomes the mean of its cluster and gets a 'votes'
         field; kept boxes with fewer than min_votes voters are left out.  That is a second device round trip (an upload, NMS
         and the vote kernel, a read-back) after the scan's read-back.  None: exactly the call without it."""
-        nms = _nms_args(iou_threshold, score_threshold)
-        vote = _vote_args(nms, vote_iou, vote_weights, min_votes)
-        res, _, _ = self._detect_one(image, None if vote else nms, windows=False)
-        return merge_detections(_as_boxes(res), **vote) if vote else _as_boxes(res)
+        how = suppression(iou_threshold, score_threshold, vote_iou, vote_weights, min_votes)
+        voting = how is not None and how.vote is not None
+        res, _, _ = self._detect_one(image, None if voting else how, windows=False)
+        return finish(_as_boxes(res), how if voting else None)
 
     def detect_raw(self, image, _nms=None):
         """detect() with everything the parity tests compare: boxes, scores, (level, r, c),
         alive[level, stage]; updates n_loc / n_weak."""
-        return _raw(*self._detect_one(image, _nms))
+        return _raw(*self._detect_one(image, _nms and suppression(*_nms)))
 
     def _detect_one(self, image, nms, windows=True):
         """One image -> (its Detections, alive[L, T], the levels' scales); updates n_loc / n_weak."""
@@ -351,6 +315,22 @@ class Model:
         dm = view if view is not None else self.device_cascade()
         return self._scan_result(eng, dm, eng.run_cascade(dm, ranks=view is not None), fetch_final=True)
 
+    def scan_resident(self, image):
+        """Scan one host image and leave its pyramid resident: (eng, found) -- the engine that holds the channels and
+        scan_engine's dict of it -- or None when the image is too small for any level.  The scan reads the float or uint8
+        channels, not rank bytes: what the callers go on to crop, verify or regress from.  One host wait, the scan's
+        read-back; n_loc / n_weak advance as in a scan."""
+        _channels._validate_image(image)
+        shrink, n_per_oct, smooth, spec = _channels.read_opts(self.channel_opts)
+        if spec.dtype == np.uint8:
+            _channels._require_u8(image, spec.key)
+        eng = _engine.get_engine(image.shape[0], image.shape[1], image.dtype, shrink, n_per_oct, smooth, 1, channels=spec)
+        if eng.plan.n_levels == 0:
+            return None
+        eng.load_images(image)
+        eng.run_channels()
+        return eng, self.scan_engine(eng)                    # every level in one launch group
+
     def _scan_result(self, eng, dm, stt, **have):
         """The dict detect_raw returns, of the scan `stt` of image 0 of `eng` (have: what _assemble is told of it)."""
         (res,), alive = self._assemble(eng, dm, stt, 1, None, single=True, **have)
@@ -372,7 +352,7 @@ class Model:
           3. the packed records (wb_det_pack_launch): few detections (the usual case) are ordered and their boxes formed on
              the host -- the same float32 arithmetic as boxes_kernel, without three launches and four copies; more than
              _HOST_POST_MAX (single) / _HOST_POST_BATCH stay on the device for a sort and wb_boxes_launch.
-        nms: (iou_threshold, score_threshold or None): only the detections non-maximum suppression keeps -- by the flags
+        nms: a boxes.Suppression: only the detections non-maximum suppression keeps -- by the flags
         the device left on routes 1 and 2, otherwise of each image's complete result (_suppress)."""
         m, n, Cc = self.shape
         if single and finished is None and fetch_final:
@@ -418,7 +398,7 @@ class Model:
         global _torch
         import torch as _torch
         lanes, K = max(int(lanes), 1), max(int(batch), 1)
-        nms = _nms_args(iou_threshold, score_threshold)
+        nms = suppression(iou_threshold, score_threshold)
         shrink, n_per_oct, smooth, spec = _channels.read_opts(self.channel_opts, allow_callable=True)
         if spec is None:                      # (a caller's own channel function runs on the host between the GPU steps)
             for image in images:
@@ -451,12 +431,12 @@ class Model:
         content and order as B calls of detect) and updates n_loc / n_weak.
         iou_threshold, score_threshold: as for detect, per image (one wb_nms_finish_launch for the whole batch behind the
         ordering launch, in front of the one wait)."""
-        out, _, _ = self._detect_batch(images, _nms_args(iou_threshold, score_threshold), windows=False)
+        out, _, _ = self._detect_batch(images, suppression(iou_threshold, score_threshold), windows=False)
         return [_as_boxes(res) for res in out]
 
     def detect_batch_raw(self, images, _nms=None):
         """All detections of a batch as flat arrays (image, level, r, c, boxes, scores, alive[B,L,T])."""
-        out, alive, scales = self._detect_batch(images, _nms)
+        out, alive, scales = self._detect_batch(images, _nms and suppression(*_nms))
         level, r, c = (np.concatenate(w) for w in zip(*(res.windows() for res in out)))
         return dict(batch=len(out), image=np.repeat(np.arange(len(out), dtype=np.int32), [res.scores.size for res in out]),
                     level=level, r=r, c=c, boxes=np.concatenate([res.boxes for res in out]),

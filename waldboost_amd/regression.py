@@ -262,68 +262,46 @@ def fit(model, images, min_iou=0.5, max_candidates=100, l2=1e-2, batch=8, seed=0
 
 def detect_and_refine(image, model, regressor, iou_threshold=None, score_threshold=None, vote_iou=None, vote_weights="uniform", min_votes=1):
     """Detections of `model` on `image` with their boxes refined by `regressor`: Boxes with 'scores', in Model.detect's
-    order (levels in pyramid order, row-major inside a level).  The scan is verification.detect_and_verify's route (float or
-    uint8 channels, not rank bytes); the scan's records go up in one upload and wb_regress_apply_launch reads every window
-    where it lies in the resident pyramid.  Scores are untouched.  iou_threshold / score_threshold: non-maximum suppression
-    (non_max_suppression's semantics) AFTER refinement, on the refined boxes.  Two host waits: the scan's read-back and the
-    refined boxes.  n_loc / n_weak advance as in a scan.
+    order (levels in pyramid order, row-major inside a level).  The scan is Model.scan_resident (float or uint8 channels, not
+    rank bytes); the scan's records go up in one upload (the level table | the records | 1 / scale in float64 | in float32)
+    and wb_regress_apply_launch reads every window where it lies in the resident pyramid.  Scores are untouched.
+    iou_threshold / score_threshold: non-maximum suppression (non_max_suppression's semantics) AFTER refinement, on the
+    refined boxes (boxes.finish: one more upload and read-back).  Without them two host waits: the scan's read-back and the
+    refined boxes with the error word, out of one block.  n_loc / n_weak advance as in a scan.
     vote_iou (needs an iou_threshold), vote_weights, min_votes: box voting on the REFINED boxes -- boxes.merge_detections of
     the complete refined result with these thresholds: every kept box becomes the mean of its cluster and gets a 'votes'
     field, kept boxes with fewer than min_votes voters are left out.  That is one more device round trip after the refined
-    boxes' read-back.  None: exactly the call without it."""
-    import torch
+    boxes' read-back, the same one that suppression alone makes.  None: exactly the call without it."""
     from . import channels as _channels
-    from . import engine as _engine
-    from .boxes import Boxes, merge_detections, non_max_suppression
-    from .model import _nms_args, _vote_args
+    from .boxes import Boxes, finish, suppression
     from .samples import level_table
-    nms = _nms_args(iou_threshold, score_threshold)
-    vote = _vote_args(nms, vote_iou, vote_weights, min_votes)
+    how = suppression(iou_threshold, score_threshold, vote_iou, vote_weights, min_votes)
     if not isinstance(regressor, BoxRegressor):
         raise TypeError(f"detect_and_refine takes a BoxRegressor, got {type(regressor).__name__}")
     if tuple(int(x) for x in model.shape) != regressor.input_shape:
         raise ValueError(f"the model's window shape {tuple(model.shape)} is not the regressor's input_shape {regressor.input_shape}")
-    _channels._validate_image(image)
-    shrink, n_per_oct, smooth, spec = _channels.read_opts(model.channel_opts)
-    if regressor.dtype is not None and regressor.dtype != np.dtype(spec.dtype):
-        raise ValueError(f"the regressor was fitted on {regressor.dtype} channels, the model's are {np.dtype(spec.dtype)}")
-    if spec.dtype == np.uint8:
-        _channels._require_u8(image, spec.key)
-    empty = Boxes(np.zeros((0, 4), np.float32), scores=np.zeros(0, np.float32))
-    if vote is not None:
-        empty.set_field("votes", np.zeros(0, np.int32))
-    eng = _engine.get_engine(image.shape[0], image.shape[1], image.dtype, shrink, n_per_oct, smooth, 1, channels=spec)
-    if eng.plan.n_levels == 0:
-        return empty
-    eng.load_images(image)
-    eng.run_channels()
-    found = model.scan_engine(eng)                          # wait 1: detections, in (level, r, c) order
+    chn_dtype = np.dtype(_channels.read_opts(model.channel_opts)[3].dtype)
+    if regressor.dtype is not None and regressor.dtype != chn_dtype:
+        raise ValueError(f"the regressor was fitted on {regressor.dtype} channels, the model's are {chn_dtype}")
+    scanned = model.scan_resident(image)                    # wait 1: detections, in (level, r, c) order
+    if scanned is None or scanned[1]["scores"].size == 0:
+        return finish(Boxes(np.zeros((0, 4), np.float32), scores=np.zeros(0, np.float32)), how)
+    eng, found = scanned
     N = int(found["scores"].size)
-    if N == 0:
-        return empty
     lib = nat.load()
     dev = nat.require_gpu()
     m, n, Cc = regressor.input_shape
-    L = eng.plan.n_levels
-    # one upload: the level table | the records | 1 / scale in float64 | in float32 (16-byte items first: all aligned)
     det = np.zeros(N, nat.DET_DTYPE)
     det["level"], det["r"], det["c"], det["score"] = found["level"], found["r"], found["c"], found["scores"]
-    parts = dict(table=level_table(eng), det=det, inv64=np.array([1.0 / float(s) for s in eng.plan.scales], np.float64),
-                 inv_scale=np.ascontiguousarray(eng.inv_scales(), np.float32))
-    offs = np.cumsum([0] + [p.nbytes for p in parts.values()])
-    blob = torch.from_numpy(np.concatenate([p.view(np.uint8) for p in parts.values()])).to(dev)
-    at = {k: C.c_void_p(blob.data_ptr() + int(o)) for k, o in zip(parts, offs)}
-    boxes = torch.empty((N, 4), dtype=torch.float32, device=dev)
-    err = torch.zeros(1, dtype=torch.int32, device=dev)
-    nat.check(lib.wb_regress_apply_launch(nat.stream_ptr(), nat.ptr(eng.chn), eng.spec.wb_dtype, eng.chn_stride, 1, at["table"], L, Cc,
-                                          at["det"], N, m, n, nat.ptr(regressor.weights_on(dev)), at["inv_scale"], at["inv64"], None,
-                                          nat.ptr(boxes), nat.ptr(err)), "wb_regress_apply_launch")
-    host = torch.cat([boxes.reshape(-1).view(torch.int32), err]).cpu().numpy()          # wait 2
-    if int(host[-1]):
+    inp = nat.Block.upload(dev, table=level_table(eng), det=det, inv64=np.array([1.0 / float(s) for s in eng.plan.scales], np.float64),
+                           inv_scale=np.ascontiguousarray(eng.inv_scales(), np.float32))
+    out = nat.Block.empty(dev, boxes=((N, 4), np.float32), err=(1, np.int32))
+    out.tensor("err").zero_()
+    nat.check(lib.wb_regress_apply_launch(nat.stream_ptr(), nat.ptr(eng.chn), eng.spec.wb_dtype, eng.chn_stride, 1, inp.ptr["table"],
+                                          eng.plan.n_levels, Cc, inp.ptr["det"], N, m, n, nat.ptr(regressor.weights_on(dev)),
+                                          inp.ptr["inv_scale"], inp.ptr["inv64"], None, out.ptr["boxes"], out.ptr["err"]),
+              "wb_regress_apply_launch")
+    host = out.host()                                       # wait 2
+    if int(host["err"][0]):
         raise RuntimeError("detect_and_refine: a detection's window lies outside its pyramid level")
-    out = Boxes(host[:-1].view(np.float32).reshape(N, 4).copy(), scores=np.ascontiguousarray(found["scores"], np.float32))
-    if vote is not None:
-        out = merge_detections(out, **vote)
-    elif nms is not None:
-        out = non_max_suppression(out, nms[0], nms[1])
-    return out
+    return finish(Boxes(host["boxes"].copy(), scores=np.ascontiguousarray(found["scores"], np.float32)), how)

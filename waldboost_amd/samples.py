@@ -125,18 +125,10 @@ def get_regression_target(dt_boxes, gt_boxes):
 def get_samples_from_image(model, image, gt_boxes, tp=True, fp=True, **kwargs):
     """Generator over the pyramid levels that hold selected detections of `model` on `image`: Boxes
     with 'scores', 'row', 'col', 'instance_id', 'tp_label' and 'samples' (their (m, n, C) crops)."""
-    from . import channels as _channels
-    from . import engine as _engine
-    _channels._validate_image(image)
-    shrink, n_per_oct, smooth, spec = _channels.read_opts(model.channel_opts)
-    if spec.dtype == np.uint8:
-        _channels._require_u8(image, spec.key)
-    eng = _engine.get_engine(image.shape[0], image.shape[1], image.dtype, shrink, n_per_oct, smooth, 1, channels=spec)
-    if eng.plan.n_levels == 0:
+    scanned = model.scan_resident(image)
+    if scanned is None:
         return
-    eng.load_images(image)
-    eng.run_channels()
-    found = model.scan_engine(eng)                       # every level in one launch group
+    eng, found = scanned
     wanted = []
     if tp:
         wanted.append(SampleLabel.TRUE_POSITIVE)
@@ -337,15 +329,11 @@ class LabelledBatch:
         self.inv = np.ascontiguousarray(self.eng.inv_scales(), np.float32)
 
     def upload(self, **more):
-        """The one upload: gt | table | gt_off | `more` (the caller's own 4-byte arrays) | inv_scale | ignore (the doubles
-        first: all aligned), as ptr[name]."""
-        import ctypes as C
-        import torch
+        """The one upload (nat.Block): gt | table | gt_off | `more` (the caller's own 4-byte arrays) | inv_scale | ignore, as
+        ptr[name]."""
         assert hasattr(self, "table"), "LabelledBatch.upload comes after run_channels"
-        parts = dict(gt=self.gt.reshape(-1), table=self.table, gt_off=self.gt_off, **more, inv_scale=self.inv, ignore=self.ignore)
-        offs = np.cumsum([0] + [p.nbytes for p in parts.values()])
-        self.blob = torch.from_numpy(np.concatenate([p.view(np.uint8) for p in parts.values()])).to(self.dev)
-        self.ptr = {k: C.c_void_p(self.blob.data_ptr() + int(o)) for k, o in zip(parts, offs)}
+        self.block = nat.Block.upload(self.dev, gt=self.gt, table=self.table, gt_off=self.gt_off, **more, inv_scale=self.inv, ignore=self.ignore)
+        self.ptr = self.block.ptr
 
     def mined(self, rows):
         """The labelled rows (device int32 [N, 8], N >= 1) as a MinedSamples in (image, level, r, c) order -- order_rows,

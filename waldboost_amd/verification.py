@@ -455,31 +455,21 @@ def train(M, X0, H0, X1, H1, epochs=10, batch_size=64, steps=1000, *, lr=1e-4, s
 def detect_and_verify(image, model, verifier):
     """Detections of `model` on `image`, re-scored by `verifier` (reference verification.py:85-105): (bbs, scores), a
     float32 (N, 4) array and a float32 (N,) array in Model.detect's order (levels in pyramid order, row-major inside a
-    level); ([], []) when nothing is detected.  The scan is samples.get_samples_from_image's route (float channels, not
+    level); ([], []) when nothing is detected.  The scan is Model.scan_resident (float or uint8 channels, not
     rank bytes); the crops are gathered from the resident pyramid and stay on the device.  One upload (the window origins
     and scores) and two host waits: the scan's read-back and the scores.  n_loc / n_weak advance as in a scan."""
     import torch
-    from . import channels as _channels
-    from . import engine as _engine
     if tuple(int(x) for x in model.shape) != verifier.input_shape:
         raise ValueError(f"the model's window shape {tuple(model.shape)} is not the verifier's input_shape {verifier.input_shape}")
-    _channels._validate_image(image)
-    shrink, n_per_oct, smooth, spec = _channels.read_opts(model.channel_opts)
-    if spec.dtype == np.uint8:
-        _channels._require_u8(image, spec.key)
-    eng = _engine.get_engine(image.shape[0], image.shape[1], image.dtype, shrink, n_per_oct, smooth, 1, channels=spec)
-    if eng.plan.n_levels == 0:
+    scanned = model.scan_resident(image)                    # wait 1: detections, in (level, r, c) order
+    if scanned is None or scanned[1]["scores"].size == 0:
         return [], []
-    eng.load_images(image)
-    eng.run_channels()
-    found = model.scan_engine(eng)                          # wait 1: detections, in (level, r, c) order
+    eng, found = scanned
     N = int(found["scores"].size)
-    if N == 0:
-        return [], []
     lib = nat.load()
     dev = nat.require_gpu()
     m, n, Cc = verifier.input_shape
-    tdt, wdt = (torch.uint8, nat.WB_DTYPE_U8) if spec.dtype == np.uint8 else (torch.float32, nat.WB_DTYPE_F32)
+    tdt, wdt = eng.chn.dtype, eng.spec.wb_dtype
     # rows, columns and score bits in one upload
     host = np.stack([found["r"].astype(np.int32), found["c"].astype(np.int32),
                      np.ascontiguousarray(found["scores"], np.float32).view(np.int32)])
