@@ -1,5 +1,5 @@
 """What the two tree learners share on the host (``training.DTree.fit``: CART on float32, csrc/wb_cart.hip;
-``fpga.DTree.fit``: information gain on uint8 histograms, csrc/wb_fit.hip): the tensor test, the weight check, the staging
+``fpga.DTree.fit``: information gain on uint8 histograms, csrc/wb_fit.hip): the weight check, the staging
 of the samples on the device and ``grow``, the level-by-level growth loop.  ``grow`` knows nothing of either learner, of
 torch or of the native library; a learner hands it four callables:
 
@@ -15,11 +15,9 @@ torch or of the native library; a learner hands it four callables:
 """
 import numpy as np
 
+from ._native import is_tensor
+
 MAX_DEPTH = 4           # a level holds at most WB_FIT_MAX_OPEN = 8 open nodes: depths 0 .. 3 are split
-
-
-def is_tensor(x):
-    return type(x).__module__.startswith("torch")
 
 
 def check_weights(W, n, name):

@@ -3,6 +3,19 @@
 There is no CPU fallback anywhere in this package: if the HIP library has not been
 built (``python -c 'import __graft_entry__ as g; g.build()'`` or ``make -C
 waldboost_amd/csrc``) every compute entry point raises ``RuntimeError``.
+
+How the package calls the library:
+
+* ``call(name, *args)``: ``SYMBOLS[name]`` called and checked under that one name; ``launch(name, *args)``: the same with
+  torch's current stream as the first argument.  A torch tensor is passed as its data pointer, ``None`` as the null
+  pointer; ints, floats, ``c_void_p``, ``Block.ptr[...]``, ``C.byref(...)`` and ctypes arrays go to ctypes as they are.
+  Host NumPy arrays are not converted: the call site writes ``.ctypes.data_as(...)`` and keeps the array alive.
+* ``query(name, *args)``: the int a ``*_scratch_bytes`` / ``*_floats`` function writes through its last pointer.
+* ``Scratch``: one grow-only byte buffer per device for the callers that keep a scratch across calls.
+* ``window_tensor(X, dev)`` / ``window_codes(x)``: float32 or uint8 channel windows staged for a launch, with their
+  ``WB_DTYPE_*`` code; ``dtype_name`` and ``is_tensor`` are the two tests behind them.
+* ``check``, ``ptr``, ``stream_ptr``, ``load``, ``last_error``: the pieces, for a site that reads a return code itself and
+  for hand-written calls in tests and tools.
 """
 import ctypes as C
 import math
@@ -218,6 +231,80 @@ def stream_ptr():
 def ptr(t):
     """Device pointer of a torch tensor (or None)."""
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+
+
+def is_tensor(x):
+    return type(x).__module__.startswith("torch")
+
+
+def dtype_name(x):
+    """The dtype of an array or a tensor as NumPy names it ('None' for what has none); a dtype, NumPy's or torch's, names itself."""
+    return str(getattr(x, "dtype", x if is_tensor(x) or isinstance(x, np.dtype) else None)).replace("torch.", "")
+
+
+def as_arg(a):
+    """What `call` hands to ctypes for argument `a`: a tensor's data pointer (a view's: where the view starts); anything
+    else as it is -- None is ctypes' null pointer.  A host NumPy array is not taken here: the caller passes its pointer
+    and answers for its lifetime and contiguity."""
+    return C.c_void_p(a.data_ptr()) if is_tensor(a) else a
+
+
+def _argtypes(name):
+    if name not in SYMBOLS:
+        raise AttributeError(f"{name} is not a symbol of include/waldboost_hip.h")
+    return SYMBOLS[name][1]
+
+
+def call(name, *args):
+    """lib.<name>(*args) with tensors passed as their device pointers (as_arg), checked under that same name."""
+    _argtypes(name)
+    check(getattr(load(), name)(*map(as_arg, args)), name)
+
+
+def launch(name, *args):
+    """`call` of an entry point whose first parameter is the stream: on torch's current one."""
+    call(name, stream_ptr(), *args)
+
+
+def query(name, *args):
+    """The size that `name` writes through its last parameter (*_scratch_bytes: size_t, *_floats: int64), as an int."""
+    out = _argtypes(name)[-1]._type_()
+    call(name, *args, C.byref(out))
+    return int(out.value)
+
+
+class Scratch:
+    """One grow-only byte buffer per device, for launches that are ordered on one stream: on(dev, nbytes) is a uint8
+    tensor of at least max(nbytes, 16) bytes -- the one of the call before when that is large enough, whatever it held."""
+
+    def __init__(self):
+        self._held = {}
+
+    def on(self, dev, nbytes):
+        import torch
+        have = self._held.get(dev)
+        if have is None or have.numel() < nbytes:
+            have = self._held[dev] = torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=dev)
+        return have
+
+
+def window_codes(x):
+    """(torch dtype, WB_DTYPE_* code) of channel windows `x` (ndarray, tensor or their dtype), which the sample kernels take
+    as float32 or uint8; None for any other dtype."""
+    import torch
+    return {"uint8": (torch.uint8, WB_DTYPE_U8), "float32": (torch.float32, WB_DTYPE_F32)}.get(dtype_name(x))
+
+
+def window_tensor(X, dev):
+    """Channel windows X, a float32 or uint8 ndarray or tensor, staged for a launch: (contiguous tensor on `dev` in X's own
+    dtype, WB_DTYPE_* code) -- X itself when it is that already; None for any other dtype.  Shapes and finiteness are
+    the caller's to check, and so is the exception that None becomes."""
+    import torch
+    codes = window_codes(X)
+    if codes is None:
+        return None
+    t = X if is_tensor(X) else torch.from_numpy(np.ascontiguousarray(X))
+    return t.to(dev).contiguous(), codes[1]
 
 
 def _spec(part):

@@ -160,12 +160,11 @@ def match_boxes(dt_boxes, gt_boxes_per_image, dt_image=None):
     if n_gt >= 1 << 31:
         raise ValueError("match_boxes: at most 2**31 - 1 ground-truth boxes")
     from . import _native as nat
-    lib = nat.load()
     dev = nat.require_gpu()
     inp = nat.Block.upload(dev, dt=dt, gt=np.concatenate(gt), image=image, gt_off=off.astype(np.int32))
     out = nat.Block.empty(dev, best=(n, np.float64), owner=(n, np.int32))
-    nat.check(lib.wb_match_launch(nat.stream_ptr(), inp.ptr["dt"], inp.ptr["image"], inp.ptr["gt"], inp.ptr["gt_off"], n, n_gt, len(gt),
-                                  out.ptr["best"], out.ptr["owner"]), "wb_match_launch")
+    nat.launch("wb_match_launch", inp.ptr["dt"], inp.ptr["image"], inp.ptr["gt"], inp.ptr["gt_off"], n, n_gt, len(gt), out.ptr["best"],
+               out.ptr["owner"])
     h = out.host()
     return h["best"].copy(), h["owner"].copy()
 
@@ -243,7 +242,7 @@ class _DeviceBoxes:
 
     def __init__(self, boxes, scores, group, keep=None, vote=False):
         from . import _native as nat
-        self.lib, self.dev, self.n, n = nat.load(), nat.require_gpu(), scores.size, scores.size
+        self.dev, self.n, n = nat.require_gpu(), scores.size, scores.size
         given = dict(boxes=boxes, scores=scores, group=group, keep=keep)
         self.inp = nat.Block.upload(self.dev, **{k: v for k, v in given.items() if v is not None})
         specs = dict(merged=((n, 4), np.float32), votes=(n, np.int32)) if vote else {}
@@ -253,28 +252,24 @@ class _DeviceBoxes:
 
     def nms(self, how):
         """Greedy NMS into out's n_keep and keep, enqueued on the current stream."""
-        import ctypes as C
         import torch
         from . import _native as nat
         at, n = self.inp.ptr, self.n
-        need = C.c_size_t()
-        nat.check(self.lib.wb_nms_scratch_bytes(n, C.byref(need)), "wb_nms_scratch_bytes")
-        scratch = torch.empty(need.value, dtype=torch.uint8, device=self.dev)
-        tail = (n, how.iou_threshold, *how.threshold_args, nat.ptr(scratch), scratch.numel(), self.out.ptr["keep"], self.out.ptr["n_keep"])
+        scratch = torch.empty(nat.query("wb_nms_scratch_bytes", n), dtype=torch.uint8, device=self.dev)
+        tail = (n, how.iou_threshold, *how.threshold_args, scratch, scratch.numel(), self.out.ptr["keep"], self.out.ptr["n_keep"])
         if n <= _NMS_RANK_MAX:
-            nat.check(self.lib.wb_nms_launch(nat.stream_ptr(), at["boxes"], at["scores"], at.get("group"), *tail), "wb_nms_launch")
+            nat.launch("wb_nms_launch", at["boxes"], at["scores"], at.get("group"), *tail)
         else:
             # descending, the two zeros one value (-(s + 0) is -0.0 for both), equal scores in input order
             order = torch.sort(-(self.inp.tensor("scores") + 0.0), stable=True).indices.to(torch.int32)
-            nat.check(self.lib.wb_nms_ordered_launch(nat.stream_ptr(), at["boxes"], at["scores"], at.get("group"), nat.ptr(order), *tail),
-                      "wb_nms_ordered_launch")
+            nat.launch("wb_nms_ordered_launch", at["boxes"], at["scores"], at.get("group"), order, *tail)
 
     def vote(self, how):
         """wb_vote_launch into out's merged and votes, on the keep flags that were given or that nms left, on the current stream."""
         from . import _native as nat
         at, out, (vote_iou, code, _) = self.inp.ptr, self.out.ptr, how.vote
-        nat.check(self.lib.wb_vote_launch(nat.stream_ptr(), at["boxes"], at["scores"], at.get("group"), at.get("keep", out.get("keep")), self.n,
-                                          vote_iou, code, *how.threshold_args, out["merged"], out["votes"]), "wb_vote_launch")
+        nat.launch("wb_vote_launch", at["boxes"], at["scores"], at.get("group"), at.get("keep", out.get("keep")), self.n, vote_iou, code,
+                   *how.threshold_args, out["merged"], out["votes"])
 
     def flags(self, h):
         """The keep flags (bool [n]) of the read-back `h` of out."""

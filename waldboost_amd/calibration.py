@@ -57,8 +57,7 @@ def trace_launch(model, X, reject, trace=False, final=False, alive=False):
     out = (torch.empty((T, N), dtype=torch.float32, device=dev) if trace else None,
            torch.empty(N, dtype=torch.float32, device=dev) if final else None,
            torch.empty(T + 1, dtype=torch.int32, device=dev) if alive else None)
-    nat.check(nat.load().wb_samples_trace_launch(nat.stream_ptr(), dm.handle, nat.ptr(Xd), wdt, N, int(bool(reject)),
-                                                 nat.ptr(out[0]), nat.ptr(out[1]), nat.ptr(out[2])), "wb_samples_trace_launch")
+    nat.launch("wb_samples_trace_launch", dm.handle, Xd, wdt, N, int(bool(reject)), *out)
     return out
 
 
@@ -183,8 +182,7 @@ def calibrate(model, positives, recall=0.99, margin=0.0, inplace=True):
         raise ValueError("a final score is not finite: the running scores cannot be ordered")
     stage_min = torch.empty(T, dtype=torch.float32, device=Xd.device)
     n_ret = torch.empty(1, dtype=torch.int32, device=Xd.device)
-    nat.check(nat.load().wb_calib_min_launch(nat.stream_ptr(), model.device_cascade().handle, nat.ptr(Xd), wdt, N,
-                                             C.c_float(floor), nat.ptr(stage_min), nat.ptr(n_ret)), "wb_calib_min_launch")
+    nat.launch("wb_calib_min_launch", model.device_cascade().handle, Xd, wdt, N, C.c_float(floor), stage_min, n_ret)
     theta, old = _new_thetas(model, stage_min.cpu().numpy(), margin, inplace)
     return Calibration(theta, old, floor, N, int(n_ret.item()))
 
@@ -234,9 +232,8 @@ def instance_windows(model, images, gt_boxes_per_image, min_iou=0.7):
     room = 4096 * B
     while True:
         rows = torch.empty((room, 8), dtype=torch.int32, device=dev)
-        nat.check(b.eng.lib.wb_mip_windows_launch(nat.stream_ptr(), b.table.ctypes.data_as(C.c_void_p), b.inv.ctypes.data_as(C.c_void_p), L,
-                                                  b.m, b.n, b.ptr["gt"], b.ptr["gt_off"], b.ptr["ignore"], b.gt.shape[0], B, min_iou,
-                                                  nat.ptr(rows), room, nat.ptr(n_rows)), "wb_mip_windows_launch")
+        nat.launch("wb_mip_windows_launch", b.table.ctypes.data_as(C.c_void_p), b.inv.ctypes.data_as(C.c_void_p), L, b.m, b.n, b.ptr["gt"],
+                   b.ptr["gt_off"], b.ptr["ignore"], b.gt.shape[0], B, min_iou, rows, room, n_rows)
         N = int(n_rows.item()) & 0xFFFFFFFF
         if N <= room:
             break
@@ -305,15 +302,12 @@ def prune_launch(trace, bag, n_bags, floor):
     T, N = (int(x) for x in trace.shape)
     assert N <= 1 or trace.stride(1) == 1, "the rows of the trace must be contiguous"
     dev = trace.device
-    need = C.c_size_t()
-    nat.check(nat.load().wb_mip_scratch_bytes(n_bags, C.byref(need)), "wb_mip_scratch_bytes")
-    scratch = torch.empty(max(need.value, 4), dtype=torch.uint8, device=dev)
+    scratch = torch.empty(max(nat.query("wb_mip_scratch_bytes", n_bags), 4), dtype=torch.uint8, device=dev)
     theta = torch.empty(T, dtype=torch.float32, device=dev)
     removed_at = torch.empty(N, dtype=torch.int32, device=dev)
     counts = torch.empty(2, dtype=torch.int32, device=dev)
-    nat.check(nat.load().wb_mip_prune_launch(nat.stream_ptr(), nat.ptr(trace), int(trace.stride(0)) if T > 1 else N, T, N, nat.ptr(bag),
-                                             n_bags, C.c_float(floor), nat.ptr(scratch), scratch.numel(), nat.ptr(theta),
-                                             nat.ptr(removed_at), nat.ptr(counts)), "wb_mip_prune_launch")
+    nat.launch("wb_mip_prune_launch", trace, int(trace.stride(0)) if T > 1 else N, T, N, bag, n_bags, C.c_float(floor), scratch,
+               scratch.numel(), theta, removed_at, counts)
     return theta, removed_at, counts
 
 

@@ -15,7 +15,7 @@ class ChannelSpec:
 
     @property
     def wb_dtype(self):
-        return nat.WB_DTYPE_U8 if self.dtype == np.uint8 else nat.WB_DTYPE_F32
+        return nat.window_codes(self.dtype)[1]
 
     def __repr__(self):
         return f"ChannelSpec({self.key})"

@@ -76,8 +76,7 @@ def grad_hist(image, n_bins=4, full=False, bias=0):
     cs_sn = np.concatenate([np.cos(theta[:-1]), np.sin(theta[:-1])]).astype(np.float64)
     d = torch.from_numpy(img).to(dev)
     out = torch.empty((H, W, n_bins), dtype=torch.float64 if wide else torch.float32, device=dev)
-    nat.check(nat.load().wb_grad_hist_launch(nat.stream_ptr(), nat.ptr(d), H, W, n_bins, int(bool(full)), bias_v, int(wide),
-                                             cs_sn.ctypes.data_as(C.POINTER(C.c_double)), nat.ptr(out)), "wb_grad_hist_launch")
+    nat.launch("wb_grad_hist_launch", d, H, W, n_bins, int(bool(full)), bias_v, int(wide), cs_sn.ctypes.data_as(C.POINTER(C.c_double)), out)
     return out.cpu().numpy()
 
 
@@ -108,10 +107,9 @@ def grad_mag(image, norm=5, eps=1e-3):
     d = torch.from_numpy(img).to(dev)
     out = torch.empty((H, W), dtype=torch.float32, device=dev)
     scratch = torch.empty((2, H, W), dtype=torch.float32, device=dev) if taps is not None else None
-    nat.check(nat.load().wb_grad_mag_launch(nat.stream_ptr(), nat.ptr(d), H, W, 0 if taps is None else int(taps.size),
-                                            None if taps is None else taps.ctypes.data_as(C.POINTER(C.c_float)),
-                                            0.0 if taps is None else eps_v, 0 if taps is None else int(wide), nat.ptr(scratch),
-                                            nat.ptr(out)), "wb_grad_mag_launch")
+    nat.launch("wb_grad_mag_launch", d, H, W, 0 if taps is None else int(taps.size),
+               None if taps is None else taps.ctypes.data_as(C.POINTER(C.c_float)), 0.0 if taps is None else eps_v,
+               0 if taps is None else int(wide), scratch, out)
     return out.cpu().numpy()[..., None]
 
 

@@ -17,13 +17,10 @@ reference's.  Elementwise dtype conversion on the device (torch); the cascade it
 import numpy as np
 
 from . import _native as nat
+from ._native import dtype_name
 
 _EXACT_F32 = {"bool", "int8", "int16", "uint16", "float16", "bfloat16"}
 _VIA_F64 = {"float64", "int32", "uint32", "int64", "uint64"}
-
-
-def dtype_name(X):
-    return str(getattr(X, "dtype", None)).replace("torch.", "")
 
 
 def channel_tensor(X, dev):
@@ -32,12 +29,10 @@ def channel_tensor(X, dev):
     name = dtype_name(X)
     if name not in _EXACT_F32 | _VIA_F64 | {"uint8", "float32"}:
         raise TypeError(f"channel array of dtype {name} cannot be compared with float32 thresholds here")
-    t = X if isinstance(X, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(X))
-    t = t.to(dev)
-    if name == "uint8":
-        return t.contiguous(), nat.WB_DTYPE_U8
-    if name == "float32":
-        return t.contiguous(), nat.WB_DTYPE_F32
+    direct = nat.window_tensor(X, dev)
+    if direct is not None:
+        return direct
+    t = (X if nat.is_tensor(X) else torch.from_numpy(np.ascontiguousarray(X))).to(dev)
     if name in _EXACT_F32:
         return t.to(torch.float32).contiguous(), nat.WB_DTYPE_F32
     v = t.to(torch.float64)

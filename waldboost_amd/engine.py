@@ -97,7 +97,7 @@ def image_code(np_dtype):
 def array_dtype(images):
     """NumPy dtype of an image batch given as an ndarray or a torch tensor, checked against the kernels' image types
     (NotImplementedError otherwise -- raised before any launch or collective)."""
-    dt = images.dtype if isinstance(images, np.ndarray) else str(images.dtype).replace("torch.", "")
+    dt = images.dtype if isinstance(images, np.ndarray) else nat.dtype_name(images)
     try:
         dt = np.dtype(dt)
     except TypeError:
@@ -153,8 +153,7 @@ class DeviceCascade:
         th = np.array([theta_as_f32(t) for t in theta], np.float32)
         h = C.c_void_p()
         vp = lambda a: a.ctypes.data_as(C.c_void_p)
-        nat.check(lib.wb_model_create(T, vp(node_off), vp(feature), vp(threshold), vp(left), vp(right), vp(pred),
-                                      vp(th), m, n, Cc, C.byref(h)), "wb_model_create")
+        nat.call("wb_model_create", T, vp(node_off), vp(feature), vp(threshold), vp(left), vp(right), vp(pred), vp(th), m, n, Cc, C.byref(h))
         # whose rank tables this cascade scans: its own (a RankGroup's for a member view).  An opaque token, compared by
         # identity -- never the cascade or the group itself: a self-reference (or view -> group -> views) is a cycle, and
         # a cycle's __del__ (wb_model_destroy / wb_rankgroup_destroy: hipFree) would run whenever the cyclic collector
@@ -170,7 +169,7 @@ class DeviceCascade:
         self._spec_off = False           # use_specialized(False) is in force
         self._form_rows = {}             # form_rows, per channel dtype code
         info = nat.WbModelInfo()
-        nat.check(self._lib.wb_model_info(self.handle, C.byref(info)), "wb_model_info")
+        nat.call("wb_model_info", self.handle, C.byref(info))
         self.n_stages, self.depth = info.n_stages, info.depth
         self.m, self.n, self.C = info.m, info.n, info.C
         self.tile_rows, self.tile_cols, self.lds_bytes = info.tile_rows, info.tile_cols, info.lds_bytes
@@ -197,14 +196,14 @@ class DeviceCascade:
         rows = self._form_rows.get(chn_dtype)
         if rows is None:
             r = C.c_int()
-            nat.check(self._lib.wb_model_form_rows(self.handle, chn_dtype, C.byref(r), None), "wb_model_form_rows")
+            nat.call("wb_model_form_rows", self.handle, chn_dtype, C.byref(r), None)
             rows = self._form_rows[chn_dtype] = r.value
         return rows
 
     def specialized(self):
         """Which byte tiles have a model-specialised kernel loaded: subset of {WB_DTYPE_U8, WB_DTYPE_RANK8, WB_DTYPE_RANK16}."""
         info = nat.WbModelInfo()
-        nat.check(self._lib.wb_model_info(self.handle, C.byref(info)), "wb_model_info")
+        nat.call("wb_model_info", self.handle, C.byref(info))
         return {d for bit, d in ((1, nat.WB_DTYPE_U8), (2, nat.WB_DTYPE_RANK8), (4, nat.WB_DTYPE_RANK16)) if info.specialized & bit}
 
     def specialize(self, chn_dtype=None):
@@ -224,7 +223,7 @@ class DeviceCascade:
 
     def use_specialized(self, enable):
         """The loaded specialised kernels on / off for every later scan of this cascade (off: the generic kernel)."""
-        nat.check(self._lib.wb_model_use_specialized(self.handle, 1 if enable else 0), "wb_model_use_specialized")
+        nat.call("wb_model_use_specialized", self.handle, 1 if enable else 0)
         self._spec_off = not enable
 
     def live_checks_left(self, chn_dtype):
@@ -285,13 +284,13 @@ class RankGroup:
         self.members = list(cascades)                      # (the models must outlive the group)
         arr = (C.c_void_p * len(self.members))(*[dm.handle.value for dm in self.members])
         h = C.c_void_p()
-        nat.check(lib.wb_rankgroup_create(arr, len(self.members), C.byref(h)), "wb_rankgroup_create")
+        nat.call("wb_rankgroup_create", arr, len(self.members), C.byref(h))
         self.handle = h
         self.token = object()              # what the engine's rank buffer is tagged with (DeviceCascade.rank_key)
 
     def view(self, i):
         v = C.c_void_p()
-        nat.check(self._lib.wb_rankgroup_model(self.handle, i, C.byref(v)), "wb_rankgroup_model")
+        nat.call("wb_rankgroup_model", self.handle, i, C.byref(v))
         return DeviceCascade._view(v, self)
 
     def __del__(self):
@@ -679,10 +678,8 @@ class PyramidEngine:
         if p.n_levels == 0 or self.exact_single:
             return
         self._mm_clean = False
-        nat.check(self.lib.wb_octaves_launch_z(nat.stream_ptr(), nat.ptr(self.img), self.wb_dtype, self.batch, p.H, p.W,
-                                               p.H * p.W, nat.ptr(self.oct), p.oct_total, self._oct_off, p.n_oct,
-                                               nat.ptr(self.minmax), nat.ptr(zero), 0 if zero is None else zero.numel()),
-                  "wb_octaves_launch")
+        nat.launch("wb_octaves_launch_z", self.img, self.wb_dtype, self.batch, p.H, p.W, p.H * p.W, self.oct, p.oct_total, self._oct_off,
+                   p.n_oct, self.minmax, zero, 0 if zero is None else zero.numel())
 
     def ensure_clean_keys(self):
         """A captured step holds no memset (run): before it is replayed the octaves' keys must be zero -- they are, unless
@@ -730,16 +727,10 @@ class PyramidEngine:
         into self.rank."""
         p = self.plan
         ranked = rank_dm is not None
-        nat.check(self.lib.wb_channels_launch_x(nat.stream_ptr(), nat.ptr(self.img), p.H * p.W, nat.ptr(self.oct),
-                                                p.oct_total, self.wb_dtype, self.batch, nat.ptr(self.levels),
-                                                p.n_levels, nat.ptr(tiles), n_tiles,
-                                                nat.ptr(self.minmax), max(p.n_oct, 1), nat.ptr(self.taps),
-                                                self.spec.func_id, p.shrink, p.smooth,
-                                                self.cs_sn.ctypes.data_as(C.POINTER(C.c_double)),
-                                                nat.ptr(chn), self.chn_stride, rank_dm.handle if ranked else None,
-                                                nat.ptr(self.rank if ranked else None), self.chn_stride, nat.ptr(patches),
-                                                rank_dm.rank_dtype if ranked else nat.WB_DTYPE_RANK8),
-                  "wb_channels_launch")
+        nat.launch("wb_channels_launch_x", self.img, p.H * p.W, self.oct, p.oct_total, self.wb_dtype, self.batch, self.levels, p.n_levels,
+                   tiles, n_tiles, self.minmax, max(p.n_oct, 1), self.taps, self.spec.func_id, p.shrink, p.smooth,
+                   self.cs_sn.ctypes.data_as(C.POINTER(C.c_double)), chn, self.chn_stride, rank_dm.handle if ranked else None,
+                   self.rank if ranked else None, self.chn_stride, patches, rank_dm.rank_dtype if ranked else nat.WB_DTYPE_RANK8)
 
     def launch_level(self, l):
         """The float/uint8 channels of ONE level of every resident image (after launch_octaves): what a lazy
@@ -771,10 +762,8 @@ class PyramidEngine:
             self._mm_host = (self.epoch, self.minmax[0].cpu().numpy().copy())       # (one read-back per image)
         mm = np.ascontiguousarray(self._mm_host[1][int(lv["oct"])])
         out = torch.empty((nh, nw), dtype=self.tdtype, device=self.dev)
-        nat.check(self.lib.wb_resize_level_launch(nat.stream_ptr(), nat.ptr(self.img), nat.ptr(self.oct), self.wb_dtype,
-                                                  rec.ctypes.data_as(C.c_void_p),
-                                                  mm.ctypes.data_as(C.c_void_p), nat.ptr(self.taps), nat.ptr(out)),
-                  "wb_resize_level_launch")
+        nat.launch("wb_resize_level_launch", self.img, self.oct, self.wb_dtype, rec.ctypes.data_as(C.c_void_p),
+                   mm.ctypes.data_as(C.c_void_p), self.taps, out)
         return out.cpu().numpy().astype(self.dtype, copy=False)
 
     def pool_smooth(self, chns):
@@ -789,8 +778,7 @@ class PyramidEngine:
         out = torch.empty((oh, ow, Cn), dtype=d.dtype, device=self.dev)
         tmp = torch.empty_like(out) if (p.shrink == 2 and p.smooth) else None
         if H and W and Cn:
-            nat.check(self.lib.wb_pool_smooth_launch(nat.stream_ptr(), nat.ptr(d), code, H, W, Cn, p.shrink, p.smooth,
-                                                     nat.ptr(tmp), nat.ptr(out)), "wb_pool_smooth_launch")
+            nat.launch("wb_pool_smooth_launch", d, code, H, W, Cn, p.shrink, p.smooth, tmp, out)
         return out.cpu().numpy()
 
     def _casc_state(self, dm):
@@ -827,15 +815,9 @@ class PyramidEngine:
         dm.note_scan(chn_dtype)
         zk = self.ctrl[: self._mm_words] if zero_keys else None
         tiles, n_tiles = stt.tall.get(dm.form_rows(chn_dtype), (stt.tiles, stt.n_tiles))
-        nat.check(self.lib.wb_cascade_launch_z(nat.stream_ptr(), dm.handle, nat.ptr(self.rank if ranks else self.chn),
-                                               chn_dtype,
-                                               self.chn_stride,
-                                               self.batch, nat.ptr(self.levels), self.plan.n_levels,
-                                               nat.ptr(tiles), n_tiles,
-                                               nat.ptr(self.detb.recs), nat.ptr(self.detb.counts), self.detb.cap,
-                                               nat.ptr(stt.alive if stats else None), nat.ptr(zk),
-                                               0 if zk is None else zk.numel()),
-                  "wb_cascade_launch")
+        nat.launch("wb_cascade_launch_z", dm.handle, self.rank if ranks else self.chn, chn_dtype, self.chn_stride, self.batch, self.levels,
+                   self.plan.n_levels, tiles, n_tiles, self.detb.recs, self.detb.counts, self.detb.cap, stt.alive if stats else None, zk,
+                   0 if zk is None else zk.numel())
         if zero_keys:
             self._mm_clean = True
         return stt
@@ -924,8 +906,7 @@ class PyramidEngine:
             if self.packed is None:
                 self.packed = torch.empty((1 + self.detb.NS * self.detb.cap, 4), dtype=torch.int32, device=self.dev)
             out = self.packed
-        nat.check(self.lib.wb_det_pack_launch(nat.stream_ptr(), nat.ptr(self.detb.recs), nat.ptr(self.detb.counts),
-                                              self.detb.cap, nat.ptr(out), out.shape[0] - 1), "wb_det_pack_launch")
+        nat.launch("wb_det_pack_launch", self.detb.recs, self.detb.counts, self.detb.cap, out, out.shape[0] - 1)
         return out
 
     def fetch(self, dm, stt, limit=None):
@@ -999,11 +980,8 @@ class PyramidEngine:
             fb = stt.final = FinalBuffers(torch.empty(nbytes, dtype=torch.uint8, device=self.dev), host, blk.views(h),
                                           h[blk.nbytes:].view(np.int32).reshape(tuple(stt.alive.shape)))
         # (one workgroup sorts up to 4096 keys in LDS and writes the sections in the reference's order: header[3])
-        nat.check(self.lib.wb_det_finish_sorted_launch(nat.stream_ptr(), nat.ptr(self.detb.recs), nat.ptr(self.detb.counts),
-                                                       self.detb.cap, nat.ptr(self._inv_scales_d), self.plan.n_levels,
-                                                       self._key_dims[1], self._key_dims[2], dm.m, dm.n,
-                                                       nat.ptr(fb.dev), self._FETCH_ROWS, nat.ptr(stt.alive), n_alive),
-                  "wb_det_finish_sorted_launch")
+        nat.launch("wb_det_finish_sorted_launch", self.detb.recs, self.detb.counts, self.detb.cap, self._inv_scales_d, self.plan.n_levels,
+                   self._key_dims[1], self._key_dims[2], dm.m, dm.n, fb.dev, self._FETCH_ROWS, stt.alive, n_alive)
         fb.host.copy_(fb.dev, non_blocking=True)
 
     def _nms_enqueue(self, holder, fin_ptr, rows, n_images, nms):
@@ -1017,14 +995,13 @@ class PyramidEngine:
             return
         nb = holder.nms
         if nb is None or nb.rows != rows or nb.images != n_images:
-            need = C.c_size_t()
-            nat.check(self.lib.wb_nms_finish_scratch_bytes(rows, n_images, C.byref(need)), "wb_nms_finish_scratch_bytes")
+            need = nat.query("wb_nms_finish_scratch_bytes", rows, n_images)
             h_res = torch.empty(n_images * (16 + rows), dtype=torch.uint8).pin_memory()
-            nb = holder.nms = NmsBuffers(rows, n_images, torch.empty(need.value, dtype=torch.uint8, device=self.dev),
+            nb = holder.nms = NmsBuffers(rows, n_images, torch.empty(need, dtype=torch.uint8, device=self.dev),
                                          torch.empty(n_images * (16 + rows), dtype=torch.uint8, device=self.dev),
                                          h_res, h_res.numpy().reshape(n_images, 16 + rows))
-        nat.check(self.lib.wb_nms_finish_launch(nat.stream_ptr(), C.c_void_p(fin_ptr), rows, n_images, nms.iou_threshold, *nms.threshold_args,
-                                                nat.ptr(nb.scratch), nb.scratch.numel(), nat.ptr(nb.res)), "wb_nms_finish_launch")
+        nat.launch("wb_nms_finish_launch", C.c_void_p(fin_ptr), rows, n_images, nms.iou_threshold, *nms.threshold_args, nb.scratch,
+                   nb.scratch.numel(), nb.res)
         nb.h_res.copy_(nb.res, non_blocking=True)
 
     @staticmethod
@@ -1108,11 +1085,8 @@ class PyramidEngine:
         if not self._order_buffers():
             return False
         od, p = self._order, self.plan
-        nat.check(self.lib.wb_det_order_batch_launch(nat.stream_ptr(), nat.ptr(self.detb.recs), nat.ptr(self.detb.counts),
-                                                     self.detb.cap, self.batch, nat.ptr(self._inv_scales_d), p.n_levels,
-                                                     self._key_dims[1], self._key_dims[2], dm.m, dm.n, nat.ptr(od.scratch),
-                                                     od.scratch.numel(), nat.ptr(od.out), self._ORDER_ROWS),
-                  "wb_det_order_batch_launch")
+        nat.launch("wb_det_order_batch_launch", self.detb.recs, self.detb.counts, self.detb.cap, self.batch, self._inv_scales_d, p.n_levels,
+                   self._key_dims[1], self._key_dims[2], dm.m, dm.n, od.scratch, od.scratch.numel(), od.out, self._ORDER_ROWS)
         od.h_out.copy_(od.out, non_blocking=True)
         self._alive_enqueue(stt)
         if nms is not None:                                   # (every image's block suppressed in the same three launches)
@@ -1322,8 +1296,7 @@ class PyramidEngine:
         scores = torch.empty(n, dtype=torch.float32, device=self.dev)
         if n:
             inv_d = torch.from_numpy(self.inv_scales()).to(self.dev)
-            nat.check(self.lib.wb_boxes_launch(nat.stream_ptr(), nat.ptr(det_sorted), n, nat.ptr(inv_d), dm.m, dm.n,
-                                               nat.ptr(boxes), nat.ptr(scores)), "wb_boxes_launch")
+            nat.launch("wb_boxes_launch", det_sorted, n, inv_d, dm.m, dm.n, boxes, scores)
         return boxes, scores
 
     def ordered_host(self, dm, total):

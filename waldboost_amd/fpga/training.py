@@ -30,7 +30,7 @@ from .banks import BankScheduler, PixelBanks
 
 def _check_samples(X, name):
     """(N, sample shape) of an ndarray or tensor (N, m, n, C) of uint8."""
-    dt = str(X.dtype).replace("torch.", "")
+    dt = nat.dtype_name(X)
     if dt != "uint8":
         raise NotImplementedError(f"fpga.DTree.fit: no kernel for {dt} samples ({name}); the split search is built on "
                                   "256-bin histograms of uint8 channels")
@@ -128,12 +128,10 @@ def _level_search(X0, X1, F, Y, q, allowed):
     """The level search of ``fit_detail`` on the GPU (csrc/wb_fit.hip), for ``_grow.grow``: stages the samples and per level
     launches the histograms, the pick over ``allowed[depth]`` and the routing."""
     import torch
-    lib = nat.load()
     dev = nat.require_gpu()
     N = Y.size
     xt, q_d, cls_d, node_d = stage(X0, X1, F, torch.uint8, q, Y, dev)
     allowed_d = {}
-    stream = nat.stream_ptr()
 
     def search(depth, level, opened, child_base):
         n_open, base = len(opened), level[0]["id"]
@@ -142,16 +140,12 @@ def _level_search(X0, X1, F, Y, q, allowed):
         key = id(A)
         if key not in allowed_d:
             allowed_d[key] = torch.from_numpy(A.astype(np.int32)).to(dev)
-        need = C.c_size_t()
-        nat.check(lib.wb_fit_scratch_bytes(A.size, n_open, C.byref(need)), "wb_fit_scratch_bytes")
-        scratch = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        scratch = torch.empty(nat.query("wb_fit_scratch_bytes", A.size, n_open), dtype=torch.uint8, device=dev)
         splits_d = torch.empty(n_open * nat.FIT_SPLIT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
         slot_p = slot.ctypes.data_as(C.c_void_p)
-        nat.check(lib.wb_fit_level_launch(stream, nat.ptr(xt), N, F, nat.ptr(q_d), nat.ptr(cls_d), nat.ptr(node_d), base,
-                                          len(level), slot_p, n_open, nat.ptr(allowed_d[key]), A.size, nat.ptr(scratch),
-                                          need.value, nat.ptr(splits_d)), "wb_fit_level_launch")
-        nat.check(lib.wb_fit_route_launch(stream, nat.ptr(xt), N, F, nat.ptr(node_d), base, len(level), slot_p, n_open,
-                                          nat.ptr(splits_d), child_base), "wb_fit_route_launch")
+        nat.launch("wb_fit_level_launch", xt, N, F, q_d, cls_d, node_d, base, len(level), slot_p, n_open, allowed_d[key], A.size,
+                   scratch, scratch.numel(), splits_d)
+        nat.launch("wb_fit_route_launch", xt, N, F, node_d, base, len(level), slot_p, n_open, splits_d, child_base)
         return splits_d.cpu().numpy().view(nat.FIT_SPLIT_DTYPE), node_d.cpu().numpy()
     return search
 

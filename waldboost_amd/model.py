@@ -473,8 +473,7 @@ class Model:
         Xd, wdt = channel_tensor(X, dev)
         H = torch.empty(n, dtype=torch.float32, device=dev)
         mask = torch.empty(n, dtype=torch.uint8, device=dev)
-        nat.check(nat.load().wb_samples_predict_launch(nat.stream_ptr(), dm.handle, nat.ptr(Xd), wdt, n, nat.ptr(H),
-                                                       nat.ptr(mask)), "wb_samples_predict_launch")
+        nat.launch("wb_samples_predict_launch", dm.handle, Xd, wdt, n, H, mask)
         return H.cpu().numpy(), mask.cpu().numpy().astype(bool)
 
     def stage_scores(self, X, reject=False, device=False):
@@ -553,7 +552,6 @@ class _SingleLevel:
 
     def __init__(self, u, v, C, dtype=np.float32):
         import torch
-        self.lib = nat.load()
         self.dev = nat.require_gpu()
         if u >= 65536 or v >= 65536:
             raise ValueError("channel image larger than 65535 pixels per side")
@@ -562,15 +560,14 @@ class _SingleLevel:
         t[0]["u"], t[0]["v"], t[0]["chn_off"] = u, v, 0
         self.levels = torch.from_numpy(t.view(np.uint8).copy()).to(self.dev)
         self.dtype = np.dtype(dtype)
-        self.tdtype = torch.uint8 if self.dtype == np.uint8 else torch.float32
-        self.wb_dtype = nat.WB_DTYPE_U8 if self.dtype == np.uint8 else nat.WB_DTYPE_F32
+        self.tdtype, self.wb_dtype = nat.window_codes(self.dtype)
         self.X = torch.empty((max(u * v * C, 1) + 16,), dtype=self.tdtype, device=self.dev)   # + spare bytes (see wb_cascade_launch)
         self.detb = _engine.DetBuffer(1 << 10, self.dev)
         self._tiles = {}
 
     def load(self, X):
         import torch
-        if isinstance(X, torch.Tensor):
+        if nat.is_tensor(X):
             self.X[:self.u * self.v * self.C].copy_(X.to(self.tdtype).reshape(-1))
         else:
             self.X[:self.u * self.v * self.C].copy_(torch.from_numpy(np.ascontiguousarray(X, self.dtype).reshape(-1)))
@@ -589,10 +586,8 @@ class _SingleLevel:
             self.detb.zero()
             alive.zero_()
             if n_tiles:
-                nat.check(self.lib.wb_cascade_launch(nat.stream_ptr(), dm.handle, nat.ptr(self.X), self.wb_dtype, 0,
-                                                     1, nat.ptr(self.levels), 1, nat.ptr(tiles), n_tiles,
-                                                     nat.ptr(self.detb.recs), nat.ptr(self.detb.counts), self.detb.cap,
-                                                     nat.ptr(alive)), "wb_cascade_launch")
+                nat.launch("wb_cascade_launch", dm.handle, self.X, self.wb_dtype, 0, 1, self.levels, 1, tiles, n_tiles, self.detb.recs,
+                           self.detb.counts, self.detb.cap, alive)
             need = self.detb.max_count()
             if need <= self.detb.cap:
                 break

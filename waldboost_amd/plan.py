@@ -29,7 +29,7 @@ def chan_tile(chan_func, shrink):
     import ctypes as C
     from . import _native as nat
     tu, tv = C.c_int(), C.c_int()
-    nat.check(nat.load().wb_channels_tile(int(chan_func), int(shrink), C.byref(tu), C.byref(tv)), "wb_channels_tile")
+    nat.call("wb_channels_tile", int(chan_func), int(shrink), C.byref(tu), C.byref(tv))
     return tu.value, tv.value
 
 

@@ -17,8 +17,6 @@ What runs where (DESIGN.md 4.15 has the rule, tests/regress_reference.py states 
   the windows where they lie in the resident pyramid -- no crop is materialised -- followed by non-maximum suppression of
   the refined boxes.
 """
-import ctypes as C
-
 import numpy as np
 
 from . import _native as nat
@@ -39,15 +37,10 @@ def _dtype_of(dtype):
     try:
         dt = np.dtype(dtype)
     except TypeError:
-        dt = np.dtype(str(dtype).replace("torch.", ""))
+        dt = np.dtype(nat.dtype_name(dtype))
     if dt not in (np.float32, np.uint8):
         raise NotImplementedError(f"channel windows are float32 or uint8, got {dt}")
     return dt
-
-
-def _codes(dt):
-    import torch
-    return (torch.uint8, nat.WB_DTYPE_U8) if dt == np.uint8 else (torch.float32, nat.WB_DTYPE_F32)
 
 
 def targets(mined, gt_boxes_per_image, scales):
@@ -149,19 +142,17 @@ class BoxRegressor:
         """The offsets of crops X (N, m, n, C), float32 or uint8, ndarray or device tensor, as a device float64 (N, 4) tensor
         (wb_regress_predict_launch).  No host synchronisation when X is a device tensor."""
         import torch
-        on_device = isinstance(X, torch.Tensor)
-        if not on_device:
-            X = np.ascontiguousarray(X)
+        if not nat.is_tensor(X):
+            X = np.asarray(X)
         if len(X.shape) != 4 or tuple(int(x) for x in X.shape[1:]) != self.input_shape:
             raise ValueError(f"crops of shape {tuple(X.shape)}, expected (N,) + {self.input_shape}")
-        tdt, wdt = _codes(_dtype_of(X.dtype))
+        _dtype_of(X.dtype)                                  # (refuses another dtype before a GPU is asked for)
         dev = nat.require_gpu()
-        Xd = (X if on_device else torch.from_numpy(X)).to(dev, tdt).contiguous()
+        Xd, wdt = nat.window_tensor(X, dev)
         N = int(Xd.shape[0])
         m, n, Cc = self.input_shape
         out = torch.empty((N, 4), dtype=torch.float64, device=dev)
-        nat.check(nat.load().wb_regress_predict_launch(nat.stream_ptr(), nat.ptr(Xd), wdt, N, m, n, Cc, nat.ptr(self.weights_on(dev)),
-                                                       nat.ptr(out)), "wb_regress_predict_launch")
+        nat.launch("wb_regress_predict_launch", Xd, wdt, N, m, n, Cc, self.weights_on(dev), out)
         return out
 
     def predict(self, X):
@@ -182,16 +173,15 @@ class Accumulator:
         self.dev = nat.require_gpu()
         self.S = torch.zeros((self.D + 5, self.D + 5), dtype=torch.float64, device=self.dev)
         self.n = 0
-        self._scratch = None
+        self._scratch = nat.Scratch()
         # rows per launch: whole chunks, the scratch bounded
-        per_chunk = C.c_size_t()
-        nat.check(nat.load().wb_gram_scratch_bytes(nat.WB_GRAM_CHUNK, self.D, C.byref(per_chunk)), "wb_gram_scratch_bytes")
-        self._rows = max(_SCRATCH_BYTES // per_chunk.value, 1) * nat.WB_GRAM_CHUNK
+        per_chunk = nat.query("wb_gram_scratch_bytes", nat.WB_GRAM_CHUNK, self.D)
+        self._rows = max(_SCRATCH_BYTES // per_chunk, 1) * nat.WB_GRAM_CHUNK
 
     def add(self, X, T):
         """S += A^T A of device tensors X (N, m, n, C) in the accumulator's dtype and T (N, 4) float64.  No host wait."""
         import torch
-        if not (isinstance(X, torch.Tensor) and isinstance(T, torch.Tensor)):
+        if not (nat.is_tensor(X) and nat.is_tensor(T)):
             raise TypeError("Accumulator.add takes device tensors")
         if len(X.shape) != 4 or tuple(int(x) for x in X.shape[1:]) != self.shape:
             raise ValueError(f"windows of shape {tuple(X.shape)}, expected (N,) + {self.shape}")
@@ -202,17 +192,11 @@ class Accumulator:
             raise ValueError(f"targets of shape {tuple(T.shape)} and {T.dtype}, expected ({N}, 4) float64")
         if N == 0:
             return
-        lib = nat.load()
-        tdt, wdt = _codes(self.dtype)
-        X, T = X.to(self.dev).contiguous(), T.to(self.dev).contiguous()
+        (X, wdt), T = nat.window_tensor(X, self.dev), T.to(self.dev).contiguous()
         for at in range(0, N, self._rows):
             k = min(self._rows, N - at)
-            need = C.c_size_t()
-            nat.check(lib.wb_gram_scratch_bytes(k, self.D, C.byref(need)), "wb_gram_scratch_bytes")
-            if self._scratch is None or self._scratch.numel() < need.value:
-                self._scratch = torch.empty(need.value, dtype=torch.uint8, device=self.dev)
-            nat.check(lib.wb_gram_launch(nat.stream_ptr(), nat.ptr(X[at:]), wdt, nat.ptr(T[at:]), k, self.D, nat.ptr(self.S),
-                                         nat.ptr(self._scratch), self._scratch.numel()), "wb_gram_launch")
+            scratch = self._scratch.on(self.dev, nat.query("wb_gram_scratch_bytes", k, self.D))
+            nat.launch("wb_gram_launch", X[at:], wdt, T[at:], k, self.D, self.S, scratch, scratch.numel())
         self.n += N
 
     def add_mined(self, mined, gt_boxes_per_image, scales):
@@ -288,7 +272,6 @@ def detect_and_refine(image, model, regressor, iou_threshold=None, score_thresho
         return finish(Boxes(np.zeros((0, 4), np.float32), scores=np.zeros(0, np.float32)), how)
     eng, found = scanned
     N = int(found["scores"].size)
-    lib = nat.load()
     dev = nat.require_gpu()
     m, n, Cc = regressor.input_shape
     det = np.zeros(N, nat.DET_DTYPE)
@@ -297,10 +280,9 @@ def detect_and_refine(image, model, regressor, iou_threshold=None, score_thresho
                            inv_scale=np.ascontiguousarray(eng.inv_scales(), np.float32))
     out = nat.Block.empty(dev, boxes=((N, 4), np.float32), err=(1, np.int32))
     out.tensor("err").zero_()
-    nat.check(lib.wb_regress_apply_launch(nat.stream_ptr(), nat.ptr(eng.chn), eng.spec.wb_dtype, eng.chn_stride, 1, inp.ptr["table"],
-                                          eng.plan.n_levels, Cc, inp.ptr["det"], N, m, n, nat.ptr(regressor.weights_on(dev)),
-                                          inp.ptr["inv_scale"], inp.ptr["inv64"], None, out.ptr["boxes"], out.ptr["err"]),
-              "wb_regress_apply_launch")
+    nat.launch("wb_regress_apply_launch", eng.chn, eng.spec.wb_dtype, eng.chn_stride, 1, inp.ptr["table"], eng.plan.n_levels, Cc,
+               inp.ptr["det"], N, m, n, regressor.weights_on(dev), inp.ptr["inv_scale"], inp.ptr["inv64"], None, out.ptr["boxes"],
+               out.ptr["err"])
     host = out.host()                                       # wait 2
     if int(host["err"][0]):
         raise RuntimeError("detect_and_refine: a detection's window lies outside its pyramid level")

@@ -26,22 +26,16 @@ from .boxes import Boxes, concatenate, iou
 
 # --------------------------------------------------------------------------------------- crops
 def _np_dtype(chns):
-    return np.dtype(str(chns.dtype).replace("torch.", ""))
+    return np.dtype(nat.dtype_name(chns))
 
 
 def gather_samples_device(chns, rs, cs, shape):
     """Crops of `shape` = (m, n, C) at the origins (rs[i], cs[i]) of the channel image `chns`
     (ndarray or device tensor, float32 / uint8) as a device tensor (N, m, n, C)."""
     import torch
-    lib = nat.load()
     dev = nat.require_gpu()
-    dt = _np_dtype(chns)
-    if dt == np.uint8:
-        tdt, wdt = torch.uint8, nat.WB_DTYPE_U8
-    elif dt == np.float32:
-        tdt, wdt = torch.float32, nat.WB_DTYPE_F32
-    else:
-        raise TypeError(f"channel image must be float32 or uint8 (as produced by channel_pyramid), got {dt}")
+    if nat.window_codes(chns) is None:
+        raise TypeError(f"channel image must be float32 or uint8 (as produced by channel_pyramid), got {_np_dtype(chns)}")
     u, v, C = (int(x) for x in chns.shape)
     m, n = int(shape[0]), int(shape[1])
     rows = np.asarray(rs).reshape(-1).astype(np.int64)
@@ -49,12 +43,10 @@ def gather_samples_device(chns, rs, cs, shape):
     if rows.size and (rows.min() < 0 or cols.min() < 0 or rows.max() + m > u or cols.max() + n > v):
         # the reference slices without range checks and would build a ragged object array here
         raise IndexError("sample window outside the channel image")
-    src = chns if isinstance(chns, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(chns))
-    src = src.to(dev, tdt).contiguous()
+    src, wdt = nat.window_tensor(chns, dev)
     pos = torch.from_numpy(np.stack([rows, cols]).astype(np.int32)).to(dev)
-    out = torch.empty((rows.size, m, n, C), dtype=tdt, device=dev)
-    nat.check(lib.wb_gather_samples_launch(nat.stream_ptr(), nat.ptr(src), wdt, u, v, C, nat.ptr(pos[0]), nat.ptr(pos[1]),
-                                           rows.size, m, n, nat.ptr(out)), "wb_gather_samples_launch")
+    out = torch.empty((rows.size, m, n, C), dtype=src.dtype, device=dev)
+    nat.launch("wb_gather_samples_launch", src, wdt, u, v, C, pos[0], pos[1], rows.size, m, n, out)
     return out
 
 
@@ -341,18 +333,17 @@ class LabelledBatch:
         that is not waited for here: non-zero when a window lies outside its pyramid level."""
         import torch
         assert hasattr(self, "ptr"), "LabelledBatch.mined comes after run_channels and upload"
-        eng, lib, m, n, dev = self.eng, self.eng.lib, self.m, self.n, self.dev
+        eng, m, n, dev = self.eng, self.m, self.n, self.dev
         N = int(rows.shape[0])
         rows = order_rows(rows)
         crops = torch.empty((N, m, n, self.C), dtype=eng.chn.dtype, device=dev)
         err = torch.zeros(1, dtype=torch.int32, device=dev)
-        nat.check(lib.wb_mine_gather_launch(nat.stream_ptr(), nat.ptr(eng.chn), eng.spec.wb_dtype, eng.chn_stride, self.B, self.ptr["table"],
-                                            self.L, self.C, nat.ptr(rows), N, m, n, nat.ptr(crops), nat.ptr(err)), "wb_mine_gather_launch")
+        nat.launch("wb_mine_gather_launch", eng.chn, eng.spec.wb_dtype, eng.chn_stride, self.B, self.ptr["table"], self.L, self.C, rows,
+                   N, m, n, crops, err)
         det = rows[:, :4].contiguous()
         boxes = torch.empty((N, 4), dtype=torch.float32, device=dev)
         scores = torch.empty(N, dtype=torch.float32, device=dev)
-        nat.check(lib.wb_boxes_launch(nat.stream_ptr(), nat.ptr(det), N, self.ptr["inv_scale"], m, n, nat.ptr(boxes), nat.ptr(scores)),
-                  "wb_boxes_launch")
+        nat.launch("wb_boxes_launch", det, N, self.ptr["inv_scale"], m, n, boxes, scores)
         rc = rows[:, 2]
         return MinedSamples(samples=crops, scores=scores, tp_label=rows[:, 7].clone(), instance_id=rows[:, 6].clone(),
                             image=rows[:, 0].clone(), level=rows[:, 1].clone(), row=rc & 0xFFFF, col=(rc >> 16) & 0xFFFF, boxes=boxes,
@@ -386,7 +377,6 @@ def mine_batch(model, images, gt_boxes_per_image, tp=True, fp=True, min_tp_iou=0
     counters twice as in every scan, the number of chosen rows with the scan statistics, the gather's error word); neither
     records, pyramid nor crops leave the device.  Images too small for any level, or no detections: an empty result
     without a mining launch."""
-    import ctypes as C
     import torch
     from . import engine as _engine
     b = LabelledBatch(model, images, gt_boxes_per_image, "mine_batch")
@@ -410,16 +400,12 @@ def mine_batch(model, images, gt_boxes_per_image, tp=True, fp=True, min_tp_iou=0
     k_tp = min(int(max_tp_candidates), total) if tp else 0
     k_fp = min(int(max_fp_candidates), total) if fp else 0
     room = min(total, B * L * (k_tp + k_fp))
-    need = C.c_size_t()
-    nat.check(eng.lib.wb_mine_scratch_bytes(total, B, L, C.byref(need)), "wb_mine_scratch_bytes")
-    scratch = torch.empty(need.value, dtype=torch.uint8, device=dev)
+    scratch = torch.empty(nat.query("wb_mine_scratch_bytes", total, B, L), dtype=torch.uint8, device=dev)
     rows = torch.empty((max(room, 1), 8), dtype=torch.int32, device=dev)
     n_rows = torch.zeros(1, dtype=torch.int32, device=dev)
-    nat.check(eng.lib.wb_mine_select_launch(nat.stream_ptr(), nat.ptr(recs), total, b.ptr["inv_scale"], L, m, n, b.ptr["gt"], b.ptr["gt_off"],
-                                            b.ptr["ignore"], b.gt.shape[0], b.ptr["serial"], B, float(min_tp_iou), float(max_fp_iou),
-                                            int(max_tp_candidates), int(max_fp_candidates), int(bool(tp)), int(bool(fp)),
-                                            int(seed) & 0xFFFFFFFF, nat.ptr(scratch), scratch.numel(), nat.ptr(rows), room, nat.ptr(n_rows)),
-              "wb_mine_select_launch")
+    nat.launch("wb_mine_select_launch", recs, total, b.ptr["inv_scale"], L, m, n, b.ptr["gt"], b.ptr["gt_off"], b.ptr["ignore"],
+               b.gt.shape[0], b.ptr["serial"], B, float(min_tp_iou), float(max_fp_iou), int(max_tp_candidates), int(max_fp_candidates),
+               int(bool(tp)), int(bool(fp)), int(seed) & 0xFFFFFFFF, scratch, scratch.numel(), rows, room, n_rows)
     h = torch.cat([n_rows, stt.alive.reshape(-1)]).cpu().numpy()      # one wait: the chosen rows' number and the statistics
     N = int(h[0])
     model.n_weak += int(h[1:].reshape(stt.alive.shape)[:, :, :T].astype(np.int64).sum())
@@ -501,9 +487,8 @@ class DeviceSamplePool(object):
         N = int(X.shape[0])
         H = torch.empty(N, dtype=torch.float32, device=X.device)
         mask = torch.empty(N, dtype=torch.uint8, device=X.device)
-        wdt = nat.WB_DTYPE_U8 if X.dtype == torch.uint8 else nat.WB_DTYPE_F32
-        nat.check(nat.load().wb_samples_predict_launch(nat.stream_ptr(), model.device_cascade().handle, nat.ptr(X), wdt, N, nat.ptr(H),
-                                                       nat.ptr(mask)), "wb_samples_predict_launch")
+        X, wdt = nat.window_tensor(X, X.device)
+        nat.launch("wb_samples_predict_launch", model.device_cascade().handle, X, wdt, N, H, mask)
         self.samples.scores = H
 
     def remove_low_scoring(self, min_score=-np.inf):

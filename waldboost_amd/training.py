@@ -9,7 +9,7 @@ gini criterion, best splitter) trains on the GPU: the sort of every feature colu
 search, routing and re-partitioning of each tree level are HIP kernels (csrc/wb_cart.hip, launched
 by ``_level_search``); the class weights, the leaf decisions, the pre-order numbering and the node
 predictions -- the reference's own NumPy expressions -- run on the host, around the growth loop
-this learner shares with the FPGA flavour's (``_grow.grow``; ``check_weights``, ``is_tensor``,
+this learner shares with the FPGA flavour's (``_grow.grow``; ``check_weights``,
 ``stage`` and ``MAX_DEPTH`` live there too).  tests/cart_reference.py is the NumPy statement of
 what it computes.  ``waldboost_amd.fpga.DTree`` (csrc/wb_fit.hip) is the FPGA
 flavour's learner on uint8 samples.
@@ -26,7 +26,7 @@ import pickle
 import numpy as np
 
 from . import _native as nat
-from ._grow import MAX_DEPTH, check_weights, grow, is_tensor, stage
+from ._grow import MAX_DEPTH, check_weights, grow, stage
 from .compare import channel_tensor
 
 logger = logging.getLogger(__name__)
@@ -169,7 +169,6 @@ class DTree:
         """Leaf prediction for the windows with origins (rs[i], cs[i]) of channel image
         X[u,v,C] (reference training.py:84-96)."""
         import torch
-        lib = nat.load()
         dev = nat.require_gpu()
         rs = np.asarray(rs)
         cs = np.asarray(cs)
@@ -184,15 +183,12 @@ class DTree:
         cd = torch.from_numpy(cs.astype(np.int32)).to(dev)
         out = torch.empty(rs.size, dtype=torch.float32, device=dev)
         f, t, l, r, p = self._device_arrays(dev)
-        nat.check(lib.wb_tree_eval_launch(nat.stream_ptr(), nat.ptr(Xd), wb_dt, u, v, C, nat.ptr(rd), nat.ptr(cd), rs.size,
-                                          nat.ptr(f), nat.ptr(t), nat.ptr(l), nat.ptr(r), nat.ptr(p),
-                                          self.left.size, nat.ptr(out)), "wb_tree_eval_launch")
+        nat.launch("wb_tree_eval_launch", Xd, wb_dt, u, v, C, rd, cd, rs.size, f, t, l, r, p, self.left.size, out)
         return out.cpu().numpy()
 
     def apply(self, X):
         """Index of the leaf each sample X[i] (shape (m,n,C)) reaches (reference training.py:73-81)."""
         import torch
-        lib = nat.load()
         dev = nat.require_gpu()
         N, m, n, C = X.shape
         if N == 0:
@@ -203,8 +199,7 @@ class DTree:
         Xd, wb_dt = channel_tensor(X, dev)
         out = torch.empty(N, dtype=torch.int32, device=dev)
         f, t, l, r, p = self._device_arrays(dev)
-        nat.check(lib.wb_tree_apply_launch(nat.stream_ptr(), nat.ptr(Xd), wb_dt, N, m, n, C, nat.ptr(f), nat.ptr(t),
-                                           nat.ptr(l), nat.ptr(r), self.left.size, nat.ptr(out)), "wb_tree_apply_launch")
+        nat.launch("wb_tree_apply_launch", Xd, wb_dt, N, m, n, C, f, t, l, r, self.left.size, out)
         return out.cpu().numpy().astype("i")
 
     def predict(self, X):
@@ -221,8 +216,8 @@ _FIT_KEYS = ("max_depth", "min_samples_leaf", "min_samples_split", "criterion", 
 
 
 def _cart_check_samples(X, name):
-    if not (isinstance(X, np.ndarray) or is_tensor(X)) or str(X.dtype).replace("torch.", "") not in ("float32", "uint8"):
-        what = str(getattr(X, "dtype", type(X).__name__)).replace("torch.", "")
+    if not (isinstance(X, np.ndarray) or nat.is_tensor(X)) or nat.window_codes(X) is None:
+        what = nat.dtype_name(X) if hasattr(X, "dtype") else type(X).__name__
         raise NotImplementedError(f"training.DTree.fit: no kernel for {what} samples ({name}); float32 or uint8 ndarrays or "
                                   "device tensors (N, m, n, C) are accepted")
 
@@ -364,28 +359,23 @@ def _level_search(X0, X1, F, Y, q, scale, min_leaf):
     """The level search of ``fit_detail`` on the GPU (csrc/wb_cart.hip), for ``_grow.grow``: stages the samples, sorts every
     column once, and per level launches the scan, the pick, the routing and the re-partitioning of the sorted columns."""
     import torch
-    lib = nat.load()
     dev = nat.require_gpu()
     N = Y.size
     xt, q_d, cls_d, node_d = stage(X0, X1, F, torch.float32, q, Y, dev)
     if not bool(torch.isfinite(xt).all()):
         raise ValueError("training.DTree.fit: the samples must be finite")
     orders = [torch.empty((F, N), dtype=torch.int32, device=dev) for _ in range(2)]        # sorted by value within each node: in, out
-    stream = nat.stream_ptr()
-    nat.check(lib.wb_cart_sort_launch(stream, nat.ptr(xt), N, F, nat.ptr(orders[0])), "wb_cart_sort_launch")
+    nat.launch("wb_cart_sort_launch", xt, N, F, orders[0])
     hp = lambda values, dt: np.array(values, dt).ctypes.data_as(C.c_void_p)
 
     def search(depth, level, opened, child_base):
         n_open = len(opened)
-        need = C.c_size_t()
-        nat.check(lib.wb_cart_scratch_bytes(F, n_open, C.byref(need)), "wb_cart_scratch_bytes")
-        scratch = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        scratch = torch.empty(nat.query("wb_cart_scratch_bytes", F, n_open), dtype=torch.uint8, device=dev)
         splits_d = torch.empty(n_open * nat.CART_SPLIT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-        nat.check(lib.wb_cart_level_launch(
-            stream, nat.ptr(xt), N, F, nat.ptr(q_d), nat.ptr(cls_d), nat.ptr(orders[0]), nat.ptr(orders[1]), nat.ptr(node_d), n_open,
-            hp([nd["begin"] for nd in opened], np.int32), hp([nd["begin"] + nd["samples"].size for nd in opened], np.int32),
-            hp([nd["T0"] for nd in opened], np.uint64), hp([nd["T1"] for nd in opened], np.uint64), scale, min_leaf, child_base,
-            nat.ptr(scratch), need.value, nat.ptr(splits_d)), "wb_cart_level_launch")
+        nat.launch("wb_cart_level_launch", xt, N, F, q_d, cls_d, orders[0], orders[1], node_d, n_open,
+                   hp([nd["begin"] for nd in opened], np.int32), hp([nd["begin"] + nd["samples"].size for nd in opened], np.int32),
+                   hp([nd["T0"] for nd in opened], np.uint64), hp([nd["T1"] for nd in opened], np.uint64), scale, min_leaf, child_base,
+                   scratch, scratch.numel(), splits_d)
         orders.reverse()
         return splits_d.cpu().numpy().view(nat.CART_SPLIT_DTYPE), node_d.cpu().numpy()
     return search

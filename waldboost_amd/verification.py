@@ -71,7 +71,7 @@ class Verifier:
             raise ValueError(f"input_shape must be (m, n, C), got {input_shape!r}")
         self.input_shape = shape
         self.epsilon = float(epsilon)
-        self._scratch = {}          # device index -> feature scratch
+        self._scratch = nat.Scratch()          # the feature scratch
         self.set_weights(arrays)
 
     def set_weights(self, arrays):
@@ -148,59 +148,45 @@ class Verifier:
         key = dev.index
         if key not in self._device:
             m, n, Cc = self.input_shape
-            count = C.c_int64()
-            nat.check(nat.load().wb_verify_weights_floats(m, n, Cc, C.byref(count)), "wb_verify_weights_floats")
-            assert count.value == self._packed.size, (count.value, self._packed.size)
+            count = nat.query("wb_verify_weights_floats", m, n, Cc)
+            assert count == self._packed.size, (count, self._packed.size)
             self._device[key] = torch.from_numpy(self._packed).to(dev)
         return self._device[key]
 
-    def _scratch_on(self, dev, nbytes):
-        import torch
-        have = self._scratch.get(dev.index)
-        if have is None or have.numel() < nbytes:
-            have = self._scratch[dev.index] = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
-        return have
-
     # ---- inference
     def _checked(self, inputs):
-        import torch
         try:
             samples, scores = inputs
         except (TypeError, ValueError):
             raise ValueError("predict takes [samples, scores]") from None
-        on_device = isinstance(samples, torch.Tensor)
+        on_device = nat.is_tensor(samples)
         if not on_device:
             samples = np.asarray(samples)
-        if not isinstance(scores, torch.Tensor):
+        if not nat.is_tensor(scores):
             scores = np.asarray(scores)
         if len(samples.shape) != 4 or tuple(samples.shape[1:]) != self.input_shape:
             raise ValueError(f"samples of shape {tuple(samples.shape)}, expected (N,) + {self.input_shape}")
-        dt = np.dtype(str(samples.dtype).replace("torch.", "")) if on_device else np.asarray(samples).dtype
-        if dt not in (np.float32, np.uint8):
-            raise NotImplementedError(f"samples must be float32 or uint8, got {dt}")
-        if not on_device:
-            samples = np.ascontiguousarray(samples)
-            if dt == np.float32 and not np.isfinite(samples).all():
-                raise ValueError("samples hold non-finite values")
+        if nat.window_codes(samples) is None:
+            raise NotImplementedError(f"samples must be float32 or uint8, got {nat.dtype_name(samples)}")
+        if not on_device and samples.dtype == np.float32 and not np.isfinite(samples).all():
+            raise ValueError("samples hold non-finite values")
         N = int(samples.shape[0])
         if tuple(scores.shape) not in ((N,), (N, 1)):
             raise ValueError(f"scores of shape {tuple(scores.shape)}, expected ({N},) or ({N}, 1)")
-        return samples, scores, N, dt
+        return samples, scores, N
 
     def predict_device(self, inputs, batch_size=None):
         """predict with the result left on the device: a float32 tensor (N, 1).  No host synchronisation when samples and
         scores are device tensors."""
         import torch
-        samples, scores, N, dt = self._checked(inputs)
+        samples, scores, N = self._checked(inputs)
         if batch_size is not None and int(batch_size) < 1:
             raise ValueError("batch_size must be positive")
-        lib = nat.load()
         dev = nat.require_gpu()
         m, n, Cc = self.input_shape
         weights = self._weights_on(dev)                     # (refuses a window shape the kernels do not take)
-        tdt, wdt = (torch.uint8, nat.WB_DTYPE_U8) if dt == np.uint8 else (torch.float32, nat.WB_DTYPE_F32)
-        X = (samples if isinstance(samples, torch.Tensor) else torch.from_numpy(samples)).to(dev, tdt).contiguous()
-        H = scores if isinstance(scores, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(scores, np.float32))
+        X, wdt = nat.window_tensor(samples, dev)
+        H = scores if nat.is_tensor(scores) else torch.from_numpy(np.ascontiguousarray(scores, np.float32))
         H = H.to(dev, torch.float32).reshape(-1).contiguous()
         out = torch.empty((N, 1), dtype=torch.float32, device=dev)
         if N == 0:
@@ -208,14 +194,11 @@ class Verifier:
         F = _flat_features(self.input_shape)
         chunk = int(batch_size) if batch_size is not None else max(64, _SCRATCH_BYTES // (4 * F) // 64 * 64)
         chunk = min(chunk, N)
-        need = C.c_size_t()
-        nat.check(lib.wb_verify_scratch_bytes(m, n, Cc, chunk, C.byref(need)), "wb_verify_scratch_bytes")
-        scratch = self._scratch_on(dev, need.value)
+        scratch = self._scratch.on(dev, nat.query("wb_verify_scratch_bytes", m, n, Cc, chunk))
         flat = out.reshape(-1)
         for at in range(0, N, chunk):
             k = min(chunk, N - at)
-            nat.check(lib.wb_verify_launch(nat.stream_ptr(), nat.ptr(X[at:]), wdt, k, m, n, Cc, nat.ptr(weights), nat.ptr(H[at:]),
-                                           nat.ptr(scratch), scratch.numel(), nat.ptr(flat[at:])), "wb_verify_launch")
+            nat.launch("wb_verify_launch", X[at:], wdt, k, m, n, Cc, weights, H[at:], scratch, scratch.numel(), flat[at:])
         return out
 
     def predict(self, inputs, batch_size=None):
@@ -267,41 +250,35 @@ class Trainer:
         self.seed = int(np.random.SeedSequence(seed).generate_state(1)[0]) if seed is None else int(seed) & 0xFFFFFFFF
         self.hyper = nat.WbVerifyTrainHyper(lr=float(lr), beta1=0.9, beta2=0.999, adam_epsilon=1e-7, momentum=float(momentum),
                                             bn_epsilon=verifier.epsilon, dropout=float(dropout), seed=self.seed, reserved=0)
-        lib = nat.load()
-        m, n, Cc = verifier.input_shape
-        count = C.c_int64()
-        nat.check(lib.wb_verify_train_param_floats(m, n, Cc, C.byref(count)), "wb_verify_train_param_floats")
+        count = nat.query("wb_verify_train_param_floats", *verifier.input_shape)
         flat = np.concatenate([a.reshape(-1) for a in verifier.arrays]).astype(np.float32)
-        assert flat.size == count.value, (flat.size, count.value)
+        assert flat.size == count, (flat.size, count)
         dev = nat.require_gpu()
         self.device = dev
         self.params = torch.from_numpy(flat).to(dev)
         self.adam_m = torch.zeros_like(self.params)
         self.adam_v = torch.zeros_like(self.params)
         self.t = torch.zeros(2, dtype=torch.int32, device=dev)
-        self._scratch = None
-        self._scratch_batch = 0
+        self._scratch = nat.Scratch()
 
     # ---- the pool
     def _pool(self, X, H, Y):
         """(X, x_dtype code, H, Y, N) on the device, checked."""
         import torch
-        on_device = isinstance(X, torch.Tensor)
+        on_device = nat.is_tensor(X)
         if not on_device:
             X = np.asarray(X)
         if len(X.shape) != 4 or tuple(X.shape[1:]) != self.verifier.input_shape or X.shape[0] < 1:
             raise ValueError(f"samples of shape {tuple(X.shape)}, expected (N,) + {self.verifier.input_shape} with N >= 1")
-        dt = np.dtype(str(X.dtype).replace("torch.", ""))
-        if dt not in (np.float32, np.uint8):
-            raise NotImplementedError(f"samples must be float32 or uint8, got {dt}")
-        if not on_device and dt == np.float32 and not np.isfinite(X).all():
+        if nat.window_codes(X) is None:
+            raise NotImplementedError(f"samples must be float32 or uint8, got {nat.dtype_name(X)}")
+        if not on_device and X.dtype == np.float32 and not np.isfinite(X).all():
             raise ValueError("samples hold non-finite values")
         N = int(X.shape[0])
-        tdt, wdt = (torch.uint8, nat.WB_DTYPE_U8) if dt == np.uint8 else (torch.float32, nat.WB_DTYPE_F32)
-        Xd = (X if on_device else torch.from_numpy(np.ascontiguousarray(X))).to(self.device, tdt).contiguous()
+        Xd, wdt = nat.window_tensor(X, self.device)
         vecs = []
         for name, v in (("scores", H), ("targets", Y)):
-            if not isinstance(v, torch.Tensor):
+            if not nat.is_tensor(v):
                 v = np.ascontiguousarray(v, np.float32)
                 if not np.isfinite(v).all():
                     raise ValueError(f"{name} hold non-finite values")
@@ -311,16 +288,6 @@ class Trainer:
             vecs.append(v.to(self.device, torch.float32).reshape(-1).contiguous())
         return Xd, wdt, vecs[0], vecs[1], N
 
-    def _scratch_for(self, B):
-        import torch
-        if self._scratch is None or self._scratch_batch != B:
-            m, n, Cc = self.verifier.input_shape
-            need = C.c_size_t()
-            nat.check(nat.load().wb_verify_train_scratch_bytes(m, n, Cc, B, C.byref(need)), "wb_verify_train_scratch_bytes")
-            self._scratch = torch.empty(need.value, dtype=torch.uint8, device=self.device)
-            self._scratch_batch = B
-        return self._scratch
-
     def _steps(self, pool, idx, grads=None):
         """idx (steps, B) int32 on the device -> the device losses (steps,).  No host wait."""
         import torch
@@ -328,13 +295,10 @@ class Trainer:
         steps, B = (int(x) for x in idx.shape)
         m, n, Cc = self.verifier.input_shape
         losses = torch.empty(steps, dtype=torch.float32, device=self.device)
-        lib = nat.load()
-        scratch = self._scratch_for(B) if steps else None
+        scratch = self._scratch.on(self.device, nat.query("wb_verify_train_scratch_bytes", m, n, Cc, B)) if steps else None
         for s in range(steps):
-            nat.check(lib.wb_verify_train_step(nat.stream_ptr(), nat.ptr(Xd), wdt, nat.ptr(Hd), nat.ptr(Yd), N, nat.ptr(idx[s]), B,
-                                               m, n, Cc, nat.ptr(self.params), nat.ptr(self.adam_m), nat.ptr(self.adam_v),
-                                               nat.ptr(self.t), C.byref(self.hyper), nat.ptr(scratch), scratch.numel(),
-                                               nat.ptr(losses[s:]), nat.ptr(grads)), "wb_verify_train_step")
+            nat.launch("wb_verify_train_step", Xd, wdt, Hd, Yd, N, idx[s], B, m, n, Cc, self.params, self.adam_m, self.adam_v,
+                       self.t, C.byref(self.hyper), scratch, scratch.numel(), losses[s:], grads)
         return losses
 
     def upload(self, X, H, Y):
@@ -343,7 +307,7 @@ class Trainer:
 
     def _indices(self, idx, N):
         import torch
-        if isinstance(idx, torch.Tensor):
+        if nat.is_tensor(idx):
             host = idx.detach().cpu().numpy()
         else:
             host = np.asarray(idx)
@@ -422,8 +386,8 @@ def train(M, X0, H0, X1, H1, epochs=10, batch_size=64, steps=1000, *, lr=1e-4, s
     if N0 < 1 or N1 < 1:
         raise ValueError("both classes need samples")
     both = [X0, X1]
-    if any(isinstance(x, torch.Tensor) for x in both):
-        both = [x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x)) for x in both]
+    if any(nat.is_tensor(x) for x in both):
+        both = [x if nat.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x)) for x in both]
         if both[0].dtype != both[1].dtype:
             raise ValueError("X0 and X1 must have one dtype")
         X = torch.cat([x.to(trainer.device) for x in both])
@@ -432,7 +396,7 @@ def train(M, X0, H0, X1, H1, epochs=10, batch_size=64, steps=1000, *, lr=1e-4, s
         if both[0].dtype != both[1].dtype:
             raise ValueError("X0 and X1 must have one dtype")
         X = np.concatenate(both)
-    host = lambda v: v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+    host = lambda v: v.detach().cpu().numpy() if nat.is_tensor(v) else np.asarray(v)
     H = np.concatenate([host(H0).reshape(-1), host(H1).reshape(-1)]).astype(np.float32)
     Y = np.concatenate([-np.ones(N0, np.float32), np.ones(N1, np.float32)])
     pool = trainer.upload(X, H, Y)
@@ -466,7 +430,6 @@ def detect_and_verify(image, model, verifier):
         return [], []
     eng, found = scanned
     N = int(found["scores"].size)
-    lib = nat.load()
     dev = nat.require_gpu()
     m, n, Cc = verifier.input_shape
     tdt, wdt = eng.chn.dtype, eng.spec.wb_dtype
@@ -481,8 +444,6 @@ def detect_and_verify(image, model, verifier):
         chns = eng.level_tensor(0, int(level[a]))
         assert chns.is_contiguous() and chns.dtype == tdt
         u, v, _ = (int(x) for x in chns.shape)
-        nat.check(lib.wb_gather_samples_launch(nat.stream_ptr(), nat.ptr(chns), wdt, u, v, Cc, nat.ptr(sent[0, a:]),
-                                               nat.ptr(sent[1, a:]), int(b - a), m, n, nat.ptr(crops[a:])),
-                  "wb_gather_samples_launch")
+        nat.launch("wb_gather_samples_launch", chns, wdt, u, v, Cc, sent[0, a:], sent[1, a:], int(b - a), m, n, crops[a:])
     scores = verifier.predict_device([crops, sent[2].view(torch.float32)])
     return found["boxes"], scores.cpu().numpy().reshape(-1)              # wait 2
